@@ -6,10 +6,12 @@ One "step" = one full frame through the hot path (primary + shadow + reflection 
 one rank per GPU: buckets are dealt round-robin to ranks, each rank renders its buckets, the bucket buffers
 are all-gathered over RCCL/xGMI and assembled into the frame on every rank (part of the timed step).
 
-Prints ONE JSON line on rank 0 with the driver's contract plus `roofline`, `cpu_baseline`, `verified` (the timed frame
-compared bit for bit with the CPU oracle's) and -- outside the timed headline -- `first_frame_ms`, `critical_path_ms` and
-`extras`: the fixed 2^24-ray synthetic workload of SURVEY 8(d) (at any N: sharded by contiguous ray ranges, hits all-gathered
-over RCCL) and, at N = 1, BASELINE configs 3, 4 and 5 at their real frame sizes.
+Prints ONE JSON line on rank 0 with the driver's contract.  A plain run sets up, warms up, times the K steps and prints it;
+`--dump-outputs DIR` writes the frame of the last timed step and its ray counters to DIR/*.npy.  With `--full` the line also
+carries `roofline`, `cpu_baseline`, `verified` (the timed frame compared bit for bit with the CPU oracle's) and -- outside the
+timed headline -- `first_frame_ms`, `critical_path_ms` and `extras`: the fixed 2^24-ray synthetic workload of SURVEY 8(d) (at
+any N: sharded by contiguous ray ranges, hits all-gathered over RCCL) and, at N = 1, BASELINE configs 3, 4 and 5 at their real
+frame sizes.
 
 The headline `ms_per_step` is the STEADY STATE of a repeated frame: from the second frame of a shape on, the pixel blocks
 are started most-expensive-first using the cycle counts the previous frame reported (every block is rendered in full every
@@ -156,6 +158,16 @@ def cpu_baseline(seconds: float) -> dict:
                   f"std::experimental::simd + jthreads), so gpu_over_cpu is flattered by up to that much",
         "frame_ms": best * 1e3,
     }
+
+
+def dump_outputs(path: str, frame, counters: dict) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the frame (float32 [h, w, 3], 24.9 MB at
+    1920x1080) and the frame's counters (float64, in the order of rtk.Counters: rays, primary, hits, ...)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float32))
+    np.save(os.path.join(path, "counters.npy"), np.array(list(counters.values()), dtype=np.float64))
 
 
 def event_ms(torch, stream, fn, n):
@@ -351,7 +363,14 @@ def main() -> None:
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra workloads (synthetic 2^24 rays, configs 3-5)")
     ap.add_argument("--no-verify", action="store_true", help="skip the comparison of the timed frame with the CPU oracle's")
     ap.add_argument("--pipeline-depth", type=int, default=2, help="N>1: frames in flight (1 = render, gather, assemble back to back)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline: first-frame times, per-ray work counters and the roofline, the "
+                         "check of the timed frame against the CPU oracle, the extra workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR: frame.npy (float32 [h, w, 3]) and counters.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -383,7 +402,7 @@ def main() -> None:
 
     # ---- untimed: the first frame of a shape on a fresh accelerator (no cost-feedback order yet)
     first_frame_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         cold = rtk.KdTreeSimdAccel(rtk.parse_scene_file(SCENE), device=local_rank)
         # context, uploads, code load: a small frame through the kernel the timed frame will use (a 64x64 frame would pick the
         # 8-wave kernel by itself, and the first launch of a kernel pays for loading its code)
@@ -436,12 +455,17 @@ def main() -> None:
     # ---- untimed: per-ray work counters of this rank's share (for the algorithmic-byte figure).
     # collect_stats=2 counts what the timed kernel actually visits (its occlusion queries stop at the first answering hit);
     # collect_stats=1 counts what the reference algorithm visits for the same frame (every ray traced to the end).
-    stats_cfg = rtk.RenderConfig(**{**cfg.__dict__, "collect_stats": 1})
-    accel.render_frame_device(stats_cfg, local.data_ptr(), stream.cuda_stream)
-    work_reference = accel.last_counters()
-    stats_cfg = rtk.RenderConfig(**{**cfg.__dict__, "collect_stats": 2})
-    accel.render_frame_device(stats_cfg, local.data_ptr(), stream.cuda_stream)
-    work = accel.last_counters()
+    # A plain run renders one untimed frame in their place: the kernel's code is loaded and the block order has its first cycle
+    # counts, as after the counting frames (the cost feedback does not tell them apart).
+    if args.full:
+        stats_cfg = rtk.RenderConfig(**{**cfg.__dict__, "collect_stats": 1})
+        accel.render_frame_device(stats_cfg, local.data_ptr(), stream.cuda_stream)
+        work_reference = accel.last_counters()
+        stats_cfg = rtk.RenderConfig(**{**cfg.__dict__, "collect_stats": 2})
+        accel.render_frame_device(stats_cfg, local.data_ptr(), stream.cuda_stream)
+        work = accel.last_counters()
+    else:
+        accel.render_frame_device(cfg, local.data_ptr(), stream.cuda_stream)
 
     for _ in range(args.warmup):
         step()
@@ -471,13 +495,18 @@ def main() -> None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
 
-    # ---- the frame that was just timed, checked: bit for bit the CPU oracle's frame (rank 0; for N > 1 the assembled frame)
+    # ---- the frame that was just timed (rank 0; for N > 1 the assembled frame), copied out before anything renders into it again
+    timed_frame = None
+    if rank == 0 and (args.dump_outputs or (args.full and not args.no_verify)):
+        timed_frame = (frame if pipe is None else pipe.last_frame()).detach().cpu().numpy()
+    counters = accel.last_counters()           # of the last timed step (this rank's share)
+
+    # ---- checked: bit for bit the CPU oracle's frame
     verified, verify_note = None, None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         import numpy as np
         import oracle
 
-        timed_frame = (frame if pipe is None else pipe.last_frame()).detach().cpu().numpy()
         oacc = oracle.Accel(oracle.Scene(oracle.load_crtscene(SCENE)), oracle.ACCEL_KD_SIMD)
         ref, ocn = oacc.render(WIDTH, HEIGHT, SPP, DEPTH, DIFFUSE, count_work=False)
         same = bool(np.array_equal(timed_frame.view(np.uint32), ref.view(np.uint32)))
@@ -487,26 +516,28 @@ def main() -> None:
                        f"oracle ray count {ocn['rays']}")
 
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / max(args.steps, 1)
-    rays_rank = accel.last_counters()["rays"]
-    critical_ms = accel.last_critical_path_ms()
-    tot = torch.tensor([float(elapsed), float(rays_rank), float(algorithmic_bytes(work)), float(kernel_ms), float(critical_ms)],
+    critical_ms = accel.last_critical_path_ms() if args.full else 0.0
+    names = list(counters)
+    tot = torch.tensor([float(elapsed), float(kernel_ms), float(critical_ms)] + [float(counters[n]) for n in names],
                        dtype=torch.float64, device="cuda")
     if use_dist:
         mx = tot.clone()
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         sm = tot.clone()
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
-        elapsed, kernel_ms, critical_ms = float(mx[0]), float(mx[3]), float(mx[4])
-        rays_total = float(sm[1])
-    else:
-        rays_total = float(tot[1])
+        elapsed, kernel_ms, critical_ms = float(mx[0]), float(mx[1]), float(mx[2])
+        tot = sm
+    frame_counters = {n: float(tot[3 + i]) for i, n in enumerate(names)}      # the whole frame's, summed over ranks
+    rays_total = frame_counters["rays"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_frame, frame_counters)
 
     if verified is not None and world == 1:
         verified = verified and (int(rays_total) == ocn["rays"])
     # the same first-frame measurement on another fresh accelerator, now that the timed loop has the GPU at its clocks: what of
     # first_frame_ms is launch order (no cost feedback yet) and what is a GPU woken from idle
     first_frame_busy_gpu_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         cold = rtk.KdTreeSimdAccel(rtk.parse_scene_file(SCENE), device=local_rank)
         cold.render_frame_device(rtk.RenderConfig(width=64, height=64, trace_mode=3 if args.trace_mode == 0 else args.trace_mode),
                                  frame.data_ptr(), stream.cuda_stream)
@@ -515,22 +546,13 @@ def main() -> None:
         first_frame_busy_gpu_ms = event_ms(torch, stream, lambda: cold.render_frame_device(cfg, frame.data_ptr(), stream.cuda_stream), 1)
         del cold
     extras_out = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras_out = {"synthetic_2p24": synthetic_extras(rtk, torch, dist, stream, rank, world)}      # every rank takes part
         if world == 1:
             extras_out["frames"] = frame_extras(rtk, torch, stream)
             extras_out["fast_traversal"] = fast_traversal_extras(rtk, torch, stream, frame)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        # the dominant kernel is k_render; one launch processes this rank's share of the frame
-        launch_bytes = algorithmic_bytes(work)
-        prof = committed_profile() if world == 1 else None
-        alg_gbps = launch_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-        valu = prof["counters"]["SQ_INSTS_VALU"] if prof else None
-        traffic = (prof["traffic"] or {}).get("hbm_bytes_per_launch") if prof else None
-        # the counters are only as good as the code they were taken from: a profile of other kernel sources gives no fraction
-        fresh = bool(prof and prof["current"])
-        achieved = valu / (kernel_ms * 1e-3) / 1e9 if (valu and kernel_ms > 0 and fresh) else None
         out = {
             "metric": "Mrays/s (intersect invocations per second), hw09/scene5 dragon 1920x1080 1spp",
             "value": rays_total / (elapsed / args.steps) / 1e6,
@@ -549,49 +571,61 @@ def main() -> None:
                        "parallelism": f"bucket-tiles x{world}" + (f"; a pipelined SEQUENCE of frames: the RCCL all-gather of frame k overlaps the rendering of frame k+1 "
                                                                   f"({args.pipeline_depth} frames in flight), every frame is rendered, gathered and assembled on every rank and the "
                                                                   f"pipeline is drained inside the timed region" if pipe is not None else ""),
-                       "headline": "steady state of a repeated frame (block launch order from the previous frame's cycle counts); see first_frame_ms"},
-            "first_frame_ms": first_frame_ms,
-            "first_frame_busy_gpu_ms": first_frame_busy_gpu_ms,
-            "critical_path_ms": critical_ms,
-            "roofline": {
-                # HBM does not bound this kernel (the tree is < 0.6 MB and cache resident: `traffic` is ~1 % of what the chip could
-                # move in a frame time), MFMA does not apply (no contraction).  What bounds it is VALU instruction issue and, above
-                # that, the frame's longest dependent chain (`critical_path_ms`, one 8x8 pixel block).
-                "bound": "valu_issue",
-                "achieved": achieved, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s",
-                "frac": (achieved / VALU_PEAK_GINSTR) if achieved else None,
-                "traffic": traffic if fresh else None,
-                "profile_matches_code": fresh if prof else None,
-                "profile_git_head": (prof["meta"].get("git_head") if prof else None), "code_hash": code_hash(),
-                "kernel": "k_render", "kernel_ms": kernel_ms,
-                "valu_instructions_per_launch": valu,
-                "counters_source": (f"{prof['path']} (rocprofv3 --pmc passes of this command, mean per k_render launch); peak = {N_SIMDS} SIMDs x "
-                                    f"{CLOCK_GHZ} GHz / {CYCLES_PER_WAVE_VALU} cycles per wave64 VALU instruction (MI355X_MICROARCH.md, Wave scheduling)") if prof else None,
-                "critical_path_frac": (critical_ms / kernel_ms) if kernel_ms > 0 else None,
-                "hbm": {"traffic_GBps": (traffic / (kernel_ms * 1e-3) / 1e9) if (traffic and kernel_ms > 0 and fresh) else None,
-                        "frac_of_8TBps": (traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and kernel_ms > 0 and fresh) else None},
-                "algorithmic": {
-                    "note": "SURVEY 8(d) accounting, informational: 32 B/node popped + 36 B/triangle tested + 64 B ray+hit.  These are bytes the "
-                            "algorithm REFERENCES, not bytes moved: one fetch serves a whole wave and the tree is cache resident, so the rate "
-                            "exceeds the HBM peak and is not a roofline",
-                    "bytes_per_launch": launch_bytes, "GBps": alg_gbps,
-                    "bytes_per_ray": launch_bytes / max(work["rays"], 1),
-                    "nodes_per_ray": work["nodes"] / max(work["rays"], 1), "tris_per_ray": work["tris"] / max(work["rays"], 1),
-                    "reference_algorithm_bytes_per_launch": algorithmic_bytes(work_reference),
-                    "reference_nodes_per_ray": work_reference["nodes"] / max(work_reference["rays"], 1),
-                    "reference_tris_per_ray": work_reference["tris"] / max(work_reference["rays"], 1),
-                },
-            },
+                       "headline": "steady state of a repeated frame (block launch order from the previous frame's cycle counts); see first_frame_ms (--full)"},
         }
-        out["verified"] = verified
-        out["verified_how"] = verify_note
+        if args.full:
+            # the dominant kernel is k_render; one launch processes this rank's share of the frame
+            launch_bytes = algorithmic_bytes(work)
+            prof = committed_profile() if world == 1 else None
+            alg_gbps = launch_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+            valu = prof["counters"]["SQ_INSTS_VALU"] if prof else None
+            traffic = (prof["traffic"] or {}).get("hbm_bytes_per_launch") if prof else None
+            # the counters are only as good as the code they were taken from: a profile of other kernel sources gives no fraction
+            fresh = bool(prof and prof["current"])
+            achieved = valu / (kernel_ms * 1e-3) / 1e9 if (valu and kernel_ms > 0 and fresh) else None
+            out.update({
+                "first_frame_ms": first_frame_ms,
+                "first_frame_busy_gpu_ms": first_frame_busy_gpu_ms,
+                "critical_path_ms": critical_ms,
+                "roofline": {
+                    # HBM does not bound this kernel (the tree is < 0.6 MB and cache resident: `traffic` is ~1 % of what the chip could
+                    # move in a frame time), MFMA does not apply (no contraction).  What bounds it is VALU instruction issue and, above
+                    # that, the frame's longest dependent chain (`critical_path_ms`, one 8x8 pixel block).
+                    "bound": "valu_issue",
+                    "achieved": achieved, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s",
+                    "frac": (achieved / VALU_PEAK_GINSTR) if achieved else None,
+                    "traffic": traffic if fresh else None,
+                    "profile_matches_code": fresh if prof else None,
+                    "profile_git_head": (prof["meta"].get("git_head") if prof else None), "code_hash": code_hash(),
+                    "kernel": "k_render", "kernel_ms": kernel_ms,
+                    "valu_instructions_per_launch": valu,
+                    "counters_source": (f"{prof['path']} (rocprofv3 --pmc passes of this command, mean per k_render launch); peak = {N_SIMDS} SIMDs x "
+                                        f"{CLOCK_GHZ} GHz / {CYCLES_PER_WAVE_VALU} cycles per wave64 VALU instruction (the MI355X's wave scheduling)") if prof else None,
+                    "critical_path_frac": (critical_ms / kernel_ms) if kernel_ms > 0 else None,
+                    "hbm": {"traffic_GBps": (traffic / (kernel_ms * 1e-3) / 1e9) if (traffic and kernel_ms > 0 and fresh) else None,
+                            "frac_of_8TBps": (traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and kernel_ms > 0 and fresh) else None},
+                    "algorithmic": {
+                        "note": "SURVEY 8(d) accounting, informational: 32 B/node popped + 36 B/triangle tested + 64 B ray+hit.  These are bytes the "
+                                "algorithm REFERENCES, not bytes moved: one fetch serves a whole wave and the tree is cache resident, so the rate "
+                                "exceeds the HBM peak and is not a roofline",
+                        "bytes_per_launch": launch_bytes, "GBps": alg_gbps,
+                        "bytes_per_ray": launch_bytes / max(work["rays"], 1),
+                        "nodes_per_ray": work["nodes"] / max(work["rays"], 1), "tris_per_ray": work["tris"] / max(work["rays"], 1),
+                        "reference_algorithm_bytes_per_launch": algorithmic_bytes(work_reference),
+                        "reference_nodes_per_ray": work_reference["nodes"] / max(work_reference["rays"], 1),
+                        "reference_tris_per_ray": work_reference["tris"] / max(work_reference["rays"], 1),
+                    },
+                },
+            })
+            out["verified"] = verified
+            out["verified_how"] = verify_note
         if world > 1:
             out["config"]["scaling_note"] = ("tile sharding of THIS frame is bounded by its longest 8x8 pixel block (critical_path_ms): predicted ~1.3x "
                                              "at any N (profiles/r02_rank_times.json: slowest rank 0.207 / 0.202 / 0.164 / 0.157 ms at N = 1 / 2 / 4 / 8); "
                                              "frames whose blocks are small against the frame scale: config 5's shape 6.0x kernel-only at 8 ranks")
         if extras_out is not None:
             out["extras"] = extras_out
-        if not args.no_cpu_baseline and world == 1:      # the CPU leg runs on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU leg runs on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out))

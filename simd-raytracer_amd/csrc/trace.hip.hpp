@@ -734,12 +734,20 @@ struct CullTally { uint32_t chunks, surv, tris; unsigned long long c_cull, c_sur
 #define RTK_TALLY_ARG
 #define RTK_TALLY_PASS
 #endif
+// `exit_t` (trace()): lanes whose candidate already answers their occlusion query drop out of the pass mask at the start of
+// every 64-triangle pass after the first, and the rest of the range is skipped once none is left.  (Checked after every
+// survivor instead, the compare and branch wait on tri_step's result and config 2 was 8 % slower.)
 __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint32_t first, const uint32_t lo, const uint32_t hi,
                                                   const Ray &r, const bool cull, const float eps, const bool pass,
-                                                  const uint32_t cidx, const BundleSet &BS, const bool scalar_surv, Cand &best RTK_TALLY_ARG) {
-    const unsigned long long pass_mask = __builtin_amdgcn_ballot_w64(pass);
+                                                  const uint32_t cidx, const BundleSet &BS, const bool scalar_surv, const float exit_t,
+                                                  Cand &best RTK_TALLY_ARG) {
+    unsigned long long pass_mask = __builtin_amdgcn_ballot_w64(pass);
     const uint32_t lane = __lane_id();
     for (uint32_t base = lo; base < hi; base += 64u) {
+        if (base != lo) {
+            pass_mask &= ~__builtin_amdgcn_ballot_w64(best.t <= exit_t);
+            if (pass_mask == 0ull) return;
+        }
 #ifdef RTK_DEBUG_PHASES
         const unsigned long long pc0 = __builtin_readcyclecounter();
 #endif
@@ -819,10 +827,11 @@ __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint3
 // leaf references [lo, hi): bundle-culled when the trace has bundles and the range is worth a 64-wide pass
 __device__ __forceinline__ void leaf_range(const TreeView &T, const uint32_t first, const uint32_t lo, const uint32_t hi,
                                            const Ray &r, const bool cull, const bool pass, const uint32_t cidx,
-                                           const BundleSet &BS, Cand &best RTK_TALLY_ARG) {
+                                           const BundleSet &BS, const float exit_t, Cand &best RTK_TALLY_ARG) {
     if (lo >= hi) return;
     if (BS.n != 0u && hi - lo >= kBundleMinTris)
-        leaf_range_bundle(reinterpret_cast<const float *>(T.tris), first, lo, hi, r, cull, T.eps, pass, cidx, BS, T.scalar_surv != 0, best RTK_TALLY_PASS);
+        leaf_range_bundle(reinterpret_cast<const float *>(T.tris), first, lo, hi, r, cull, T.eps, pass, cidx, BS, T.scalar_surv != 0,
+                          exit_t, best RTK_TALLY_PASS);
     else
         leaf_range_wave((cptr_f32)(const void *)T.tris, first, lo, hi, r, cull, T.eps, pass, best);
 }
@@ -836,7 +845,8 @@ __device__ __forceinline__ void leaf_range(const TreeView &T, const uint32_t fir
 // through a 500-triangle leaf) by SLICES without replicating traversal or shading work.
 struct GroupShared {
     float4 ray_o[64];            // origin xyz, w = the lane's bundle index; rewritten only when the owner starts a new ray
-    float4 ray_d[64];            // direction xyz
+    float4 ray_d[64];            // direction xyz, w = the lane's exit_t (read by the helpers at every leaf: a burst rewrites ray_d
+                                 // only before a trace, and every trace rewrites it before its first sliced leaf)
     float best_t[64];            // per-lane best t before the leaf
     unsigned long long pass_mask, cull_mask;
     uint32_t first, count;       // leaf references [first, first+count)
@@ -945,7 +955,8 @@ __device__ __forceinline__ void group_helper_loop(const TreeView &T, GroupShared
         mine.t = sh->best_t[lane]; mine.u = 0.f; mine.v = 0.f; mine.k = kMiss;
         uint32_t lo, hi;
         slice_range<SLICES>(count, slice, lo, hi);
-        leaf_range(T, first, lo, hi, r, ((cm >> lane) & 1ull) != 0ull, ((pm >> lane) & 1ull) != 0ull, cidx, BS, mine RTK_TALLY_PASS);
+        leaf_range(T, first, lo, hi, r, ((cm >> lane) & 1ull) != 0ull, ((pm >> lane) & 1ull) != 0ull, cidx, BS, sh->ray_d[lane].w,
+                   mine RTK_TALLY_PASS);
         sh->result[slice][lane] = make_float4(mine.t, mine.u, mine.v, __uint_as_float(mine.k));
         __syncthreads();                                                   // B2: results are in LDS
     }
@@ -960,13 +971,14 @@ __device__ __forceinline__ void group_post_exit(GroupShared *sh) {
 // into SLICES contiguous ranges, one per wave of the workgroup, and merged in range order with a strict '<'.
 template <int SLICES>
 __device__ __forceinline__ void process_leaf(const TreeView &T, const uint32_t a, const uint32_t b, const Ray &r, const bool cull,
-                                             const bool pass, const uint32_t cidx, const BundleSet &BS, Cand &best, SliceCtx &sx) {
+                                             const bool pass, const uint32_t cidx, const BundleSet &BS, Cand &best, SliceCtx &sx,
+                                             const float exit_t) {
     if (SLICES > 1 && b >= sx.min_tris) {
         GroupShared *sh = sx.sh;
         const uint32_t lane = __lane_id();
         if (sx.rays_dirty) {
             sh->ray_o[lane] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(cidx));
-            sh->ray_d[lane] = make_float4(r.d.x, r.d.y, r.d.z, 0.f);
+            sh->ray_d[lane] = make_float4(r.d.x, r.d.y, r.d.z, exit_t);
             if (lane == 0u) sh->n_bundles = BS.n;                          // the bundles themselves are in sh->bundles already
             sx.ray_gen += 1u;
             sx.rays_dirty = false;
@@ -980,7 +992,7 @@ __device__ __forceinline__ void process_leaf(const TreeView &T, const uint32_t a
         __syncthreads();                                       // B1: helpers start on their slices
         uint32_t lo0, hi0;
         slice_range<SLICES>(b, 0u, lo0, hi0);
-        leaf_range(T, a, lo0, hi0, r, cull, pass, cidx, BS, best RTK_SX_TALLY);
+        leaf_range(T, a, lo0, hi0, r, cull, pass, cidx, BS, exit_t, best RTK_SX_TALLY);
         __syncthreads();                                       // B2: helper results are in LDS
 #pragma unroll
         for (int s = 1; s < SLICES; ++s) {
@@ -988,7 +1000,7 @@ __device__ __forceinline__ void process_leaf(const TreeView &T, const uint32_t a
             if (c.x < best.t) { best.t = c.x; best.u = c.y; best.v = c.z; best.k = __float_as_uint(c.w); }
         }
     } else {
-        leaf_range(T, a, 0u, b, r, cull, pass, cidx, BS, best RTK_SX_TALLY);
+        leaf_range(T, a, 0u, b, r, cull, pass, cidx, BS, exit_t, best RTK_SX_TALLY);
     }
 }
 
@@ -1096,7 +1108,7 @@ __device__ __forceinline__ void trace_list(const TreeView &T, const Ray &r, cons
 #ifdef RTK_DEBUG_PHASES
             const unsigned long long ph0 = __builtin_readcyclecounter();
 #endif
-            process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx);
+            process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx, exit_t);
 #ifdef RTK_DEBUG_PHASES
             {
                 const unsigned long long ph1 = __builtin_readcyclecounter();
@@ -1172,7 +1184,7 @@ __device__ __forceinline__ uint32_t trace_wave(const TreeView &T, const Ray &r, 
 #ifdef RTK_DEBUG_PHASES
                 const unsigned long long ph0 = __builtin_readcyclecounter();
 #endif
-                process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx);
+                process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx, exit_t);
 #ifdef RTK_DEBUG_PHASES
                 {
                     const unsigned long long ph1 = __builtin_readcyclecounter();
@@ -1195,9 +1207,11 @@ __device__ __forceinline__ uint32_t trace_wave(const TreeView &T, const Ray &r, 
 constexpr uint32_t kAutoMinLanes = 12;
 
 // `exit_t` (per lane, default "never"): the caller only wants to know whether the closest hit has t <= exit_t
-// (is_occluded, render.hpp:110-131, for scenes without transmissive materials).  The lane then stops at the end of
-// the first leaf that gives it such a hit: what it has evaluated up to there is a PREFIX of what the reference
-// evaluates (same order, same pruning), the reference's closest hit can only be nearer, so the answer is the same.
+// (is_occluded, render.hpp:110-131, for scenes without transmissive materials).  The lane then stops once it has such a
+// hit: at the end of the leaf, or at the next 64-triangle pass of a bundle-culled leaf (leaf_range_bundle).  What it has
+// evaluated up to there is a PREFIX of what the reference evaluates (same order, same pruning), the reference's closest
+// hit can only be nearer, so the answer is the same.  (A helper's slice of a leaf is a prefix of the slice; the merge keeps
+// a t <= exit_t.)
 // `cls` (per lane): the caller's name for the coherent class the lane's ray belongs to (camera rays, shadow rays towards
 // light k, ...); with kClsHasApex set, `apex` is a point the lines of the class's rays (should) pass through.  Both only steer
 // the bundle culling, never a result.

@@ -151,7 +151,9 @@ __device__ __forceinline__ void trace_lane_from(const TreeView &T, const DevNode
             const bool pass = box & !(best.t < t_min);                     // kd_tree_simd.hpp:202-205
             if (STATS) { st.nodes += 1; st.boxpass += pass ? 1u : 0u; }
             const bool inner = (b == DEV_INNER);
-            if (pass & !inner) { leaf_first = a; leaf_count = b; n += 1; break; }
+            // an empty leaf (the opaque-only occlusion tree of RTK_TRAVERSAL_FAST keeps every node) is stepped over: only a
+            // leaf with triangles leaves this loop, so leaf_count == 0 below means the walk is done
+            if (pass & !inner & (b != 0u)) { leaf_first = a; leaf_count = b; n += 1; break; }
             n = (pass | !inner) ? n + 1 : a;
         }
         if (leaf_count == 0) break;

@@ -80,18 +80,21 @@ def test_env_switch(rtk, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [("scene8", SCENE8, dict(width=640, height=360, spp=2, max_ray_depth=10)),
-                                  ("hw15_scene2_gi", CONFIG_SCENES["hw15_scene2"],
-                                   dict(width=384, height=384, spp=4, max_ray_depth=5, diffuse_rays=1))], ids=lambda c: c[0])
+@pytest.mark.parametrize("case", [(name + tag, path, kw, deep)
+                                  for name, path, kw in [("scene8", SCENE8, dict(width=640, height=360, spp=2, max_ray_depth=10)),
+                                                         ("hw15_scene2_gi", CONFIG_SCENES["hw15_scene2"],
+                                                          dict(width=384, height=384, spp=4, max_ray_depth=5, diffuse_rays=1))]
+                                  for tag, deep in [("", None), ("_deep_lane", (0, 1)), ("_deep_auto", (0, 0))]], ids=lambda c: c[0])
 def test_fast_occlusion_through_transmissive_surfaces_is_one_query(rtk, case, monkeypatch):
     """RTK_TRAVERSAL_FAST on scenes with transmissive materials (rtk.h): the streaming pipeline's occlusion query is ONE any-hit query
     against the opaque triangles instead of is_occluded's stepping loop (render.hpp:110-131).  Fewer rays are traced, and the frame is
     the parity mode's except where the two rules really differ (an occluder within shadow_bias behind a transmissive surface, a ray
     grazing an occluder's edge): at most 1 pixel in 10,000 here (measured: 0).  RTK_FAST_OCCLUDERS=0 keeps the loop: the reference's
-    ray count again."""
+    ray count again.  The _deep cases also send the fast accels' levels through the per-lane walk (RTK_STREAM_DEEP_LEVEL / _MODE),
+    which must step over the occlusion tree's empty leaves."""
     import torch
 
-    name, path, kw = case
+    name, path, kw, deep = case
     sc = rtk.parse_scene_file(path)
     st = torch.cuda.current_stream().cuda_stream
 
@@ -103,6 +106,9 @@ def test_fast_occlusion_through_transmissive_surfaces_is_one_query(rtk, case, mo
         return out, acc.last_counters()["rays"]
 
     ref, ref_rays = frame(rtk.KdTreeSimdAccel(sc))
+    if deep is not None:                                                      # levels from deep[0] on: per lane (mode 1) or AUTO (0)
+        monkeypatch.setenv("RTK_STREAM_DEEP_LEVEL", str(deep[0]))
+        monkeypatch.setenv("RTK_STREAM_DEEP_MODE", str(deep[1]))
     fast, fast_rays = frame(rtk.KdTreeSimdAccel(sc, traversal=rtk.TRAVERSAL_FAST))
     assert fast_rays < ref_rays                                               # queries through the glass no longer cost a ray per surface
     differing = int((fast != ref).any(dim=2).sum())

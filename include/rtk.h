@@ -253,6 +253,43 @@ int rtk_accel_intersect_device(rtk_accel *accel, const rtk_ray *d_rays, size_t n
 int rtk_accel_intersect_stats(rtk_accel *accel, const rtk_ray *d_rays, size_t n, int cull, int trace_mode,
                               rtk_hit *d_out, rtk_counters *counters);
 
+/* ---- batched occlusion: replaces is_occluded(accel, ray, max_t) (render/render.hpp:110-131) ---- */
+/* Per query i, the reference's loop in float, in its operation order:
+ *     while (0.0f < max_t) {                      // false for NaN, <= 0, -0: RTK_OCC_CLEAR, nothing traced
+ *         h = intersect<cull = false>(ray)        // closest hit, as rtk_accel_intersect(cull = 0)
+ *         if (miss || max_t < h.t) -> RTK_OCC_CLEAR                                          (:117)
+ *         if (material of h.mesh is not RTK_MAT_REFRACTIVE) -> RTK_OCC_OCCLUDED              (material/queries.hpp:28-30)
+ *         ray.origin = (ray.origin + h.t * ray.direction) + shadow_bias * ray.direction      (:126-127)
+ *         max_t -= h.t
+ *     }
+ *     -> RTK_OCC_CLEAR
+ * max_t is in units of the ray parameter t (the reference's callers pass unit directions and the distance to the light;
+ * nothing here needs unit directions); max_t = +inf is a plain any-hit query.
+ * The reference's loop has no bound; a kernel needs one.  A query that has made RTK_OCCLUDED_MAX_STEPS closest-hit queries
+ * and would make another is answered RTK_OCC_STEP_LIMIT: "the reference would still be stepping" -- the only departure, and
+ * visible in the answer.  (With the reference's bias of 1e-4 the longest loop on the fixture scenes is 15; a negative bias
+ * re-hits the surface it just left and runs into the limit.)
+ * trace_mode: RTK_TRACE_AUTO, RTK_TRACE_LANE or RTK_TRACE_WAVE, identical bytes from all three; the frame-only modes and
+ * RTK_TRACE_REPACK are RTK_ERR_INVALID.  shadow_bias must be finite.  n == 0 is RTK_OK and touches nothing.  out / d_out
+ * holds one byte per query (no alignment demand; d_max_t: 4 bytes).
+ * An accel built with RTK_TRAVERSAL_FAST runs the same loop over its own front-to-back tree -- NOT the opaque-only shortcut
+ * tree of the streaming pipeline.  The closest t is the same in both orders, so on scenes without transmissive materials the
+ * answers are those of the parity mode; with them, a transmissive and an opaque triangle at EXACTLY the same t may resolve
+ * either way (the tie caveat of RTK_TRAVERSAL_FAST above), and with it that query's answer.
+ * n_intersections (host variant, may be NULL): the closest-hit queries the batch made, summed over its queries -- what the
+ * reference's intersect() call counter would have gone up by. */
+#define RTK_OCCLUDED_MAX_STEPS 1024
+enum { RTK_OCC_CLEAR = 0, RTK_OCC_OCCLUDED = 1, RTK_OCC_STEP_LIMIT = 2 };
+
+int rtk_accel_occluded(rtk_accel *accel, const rtk_ray *rays, const float *max_t, size_t n,
+                       float shadow_bias, int trace_mode, uint8_t *out,
+                       uint64_t *n_intersections /* may be NULL */);     /* host buffers, synchronous */
+/* launch only: no host synchronisation and no allocation (stream-capturable once the accel is on the device, i.e. after
+ * any compute call on it) */
+int rtk_accel_occluded_device(rtk_accel *accel, const rtk_ray *d_rays, const float *d_max_t, size_t n,
+                              float shadow_bias, int trace_mode, uint8_t *d_out,
+                              void *hip_stream);                          /* device buffers, stream-ordered */
+
 /* ---- frame: replaces render_frame<A,F> (render/render.hpp:18-108) with color_hit/is_occluded device-side ---- */
 /* number of floats the (rank-local) output of rtk_render_frame_device holds */
 int rtk_render_output_floats(const rtk_accel *accel, const rtk_render_params *p, size_t *n_floats);

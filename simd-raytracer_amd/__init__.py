@@ -3,6 +3,7 @@
 Names follow the reference (paths relative to /root/reference/include/raytracer/):
   parse_scene_file      io/json/loader.hpp:235-265
   KdTreeSimdAccel       render/accel/kd_tree_simd.hpp:63-98 (ctor from a scene, intersect<cull>)
+  KdTreeSimdAccel.occluded   render/render.hpp:110-131 (is_occluded)
   render_frame          render/render.hpp:18-108
   write_ppm             io/image/ppm.hpp:7-25
 
@@ -28,6 +29,8 @@ TEX_ALBEDO, TEX_EDGES, TEX_CHECKER, TEX_BITMAP = 0, 1, 2, 3
 TRACE_AUTO, TRACE_LANE, TRACE_WAVE, TRACE_GROUP4, TRACE_GROUP8, TRACE_GROUP16, TRACE_STREAM, TRACE_TWOPASS = 0, 1, 2, 3, 4, 5, 6, 7
 TRAVERSAL_REFERENCE, TRAVERSAL_FAST = 0, 1     # rtk.h RTK_TRAVERSAL_*: leaf order of the wave-cooperative walks (FAST is not the parity mode)
 TRACE_REPACK = 8        # batched intersect only: rays sorted by origin / direction cell before the trace (csrc/repack.hip)
+OCC_CLEAR, OCC_OCCLUDED, OCC_STEP_LIMIT = 0, 1, 2     # rtk.h RTK_OCC_*: answers of the batched occlusion query
+OCCLUDED_MAX_STEPS = 1024                             # rtk.h RTK_OCCLUDED_MAX_STEPS
 
 # every symbol include/rtk.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -37,6 +40,7 @@ ABI_SYMBOLS = [
     "rtk_scene_vertex_normals", "rtk_scene_destroy",
     "rtk_accel_build", "rtk_accel_tree_info", "rtk_accel_tree_dump", "rtk_accel_destroy",
     "rtk_accel_intersect", "rtk_accel_intersect_device", "rtk_accel_intersect_stats",
+    "rtk_accel_occluded", "rtk_accel_occluded_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
@@ -141,6 +145,8 @@ _L.rtk_accel_destroy.restype = None
 _L.rtk_accel_intersect.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]
 _L.rtk_accel_intersect_device.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp]
 _L.rtk_accel_intersect_stats.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(Counters)]
+_L.rtk_accel_occluded.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, _vp, C.POINTER(C.c_uint64)]
+_L.rtk_accel_occluded_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, _vp, _vp]
 _L.rtk_render_output_floats.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]
 _L.rtk_render_frame.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.POINTER(Counters)]
 _L.rtk_render_frame_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp]
@@ -361,6 +367,26 @@ class KdTreeSimdAccel:
         c = Counters()
         _check(_L.rtk_accel_intersect_stats(self._h, d_rays_ptr, n, 1 if cull else 0, trace_mode, d_hits_ptr, C.byref(c)))
         return c.as_dict()
+
+    # ---- is_occluded(accel, ray, max_t), batched
+    def occluded(self, rays: np.ndarray, max_t: np.ndarray, shadow_bias: float = 1e-4, trace_mode: int = TRACE_AUTO,
+                 count: bool = False):
+        """is_occluded (render/render.hpp:110-131) for rays [n,6] float32 and max_t [n] float32 in host memory ->
+        uint8[n] of OCC_CLEAR / OCC_OCCLUDED / OCC_STEP_LIMIT; with count=True also the number of closest-hit queries made."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        max_t = np.ascontiguousarray(max_t, np.float32).reshape(-1)
+        if max_t.shape[0] != rays.shape[0]:
+            raise ValueError("one max_t per ray")
+        out = np.zeros((rays.shape[0],), np.uint8)
+        n_int = C.c_uint64(0)
+        _check(_L.rtk_accel_occluded(self._h, rays.ctypes.data, max_t.ctypes.data, rays.shape[0], np.float32(shadow_bias),
+                                     trace_mode, out.ctypes.data, C.byref(n_int) if count else None))
+        return (out, int(n_int.value)) if count else out
+
+    def occluded_device(self, d_rays_ptr: int, d_max_t_ptr: int, n: int, d_out_ptr: int, shadow_bias: float = 1e-4,
+                        trace_mode: int = TRACE_AUTO, stream: int = 0) -> None:
+        _check(_L.rtk_accel_occluded_device(self._h, d_rays_ptr, d_max_t_ptr, n, np.float32(shadow_bias), trace_mode,
+                                            d_out_ptr, stream))
 
     # ---- frames
     def output_floats(self, cfg: RenderConfig) -> int:

@@ -12,6 +12,7 @@
 #include "kernels.hpp"
 #include "stream.hpp"
 #include "repack.hpp"
+#include "occluded.hpp"
 
 namespace rtk {
 
@@ -195,6 +196,11 @@ struct rtk_accel {
     bool rp_in_use = false;
     size_t rp_temp_bytes = 0, rp_cap = 0;
     unsigned fb_age = 0;             // frames rendered with the current order
+    // staging of the host variant of the occlusion batch (rtk_accel_occluded): grows, never shrinks
+    rtk_ray *oc_rays = nullptr;
+    float *oc_max_t = nullptr;
+    uint8_t *oc_out = nullptr;
+    size_t oc_cap = 0;
     hipStream_t last_stream = nullptr;
     uint64_t last_primary = 0;
     bool last_stats = false;
@@ -673,6 +679,7 @@ void rtk_accel_destroy(rtk_accel *a) {
         (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
         (void)hipFree(a->rp_bounds); (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
         (void)hipFree(a->fb_cost); (void)hipFree(a->fb_order); (void)hipFree(a->fb_bins);
+        (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
         for (auto &e : a->trial_ev) if (e) (void)hipEventDestroy(e);
         if (a->rp_done) (void)hipEventDestroy(a->rp_done);
         if (a->rp_probe_ev) (void)hipEventDestroy(a->rp_probe_ev);
@@ -840,6 +847,81 @@ int rtk_accel_intersect(rtk_accel *a, const rtk_ray *rays, size_t n, int cull, i
     (void)hipFree(d_rays); (void)hipFree(d_out);
     if (rc != RTK_OK) return rc;
     if (e != hipSuccess) return hip_fail(e, "intersect copy");
+    return RTK_OK;
+}
+
+// ---------------------------------------------------------------- batched occlusion
+
+// Word of the counter buffer the host variant counts its closest-hit queries in: the last of the four words behind the frame
+// counters (the first-frame prior's six 32-bit cursors fill the first three), so the counters of the most recent frame
+// (rtk_render_last_counters) stay as that frame left them.
+static constexpr int kOccludedCountWord = kCounterWords + 3;
+
+static int occluded_check(const rtk_accel *a, const void *rays, const void *max_t, size_t n, float shadow_bias, int mode, const void *out) {
+    if (!a) return fail(RTK_ERR_INVALID, "null accel");
+    if (!valid_mode(mode)) return fail(RTK_ERR_INVALID, "trace_mode of an occlusion batch must be RTK_TRACE_AUTO, RTK_TRACE_LANE or RTK_TRACE_WAVE");
+    if (!std::isfinite(shadow_bias)) return fail(RTK_ERR_INVALID, "shadow_bias must be finite");
+    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many queries for one launch");
+    if (n > 0 && (!rays || !max_t || !out)) return fail(RTK_ERR_INVALID, "null ray, max_t or answer buffer");
+    return RTK_OK;
+}
+
+static int occluded_launch(rtk_accel *a, const rtk_ray *d_rays, const float *d_max_t, size_t n, float shadow_bias, int mode,
+                           uint8_t *d_out, hipStream_t s, bool count) {
+    dev::OccludedArgs A;
+    A.tree = tree_view(a);
+    A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;
+    A.materials = a->d_materials;
+    A.rays = d_rays; A.max_t = d_max_t; A.out = d_out; A.n = n;
+    A.shadow_bias = shadow_bias;
+    A.has_refractive = a->has_refractive ? 1 : 0;
+    A.n_intersect = count ? a->d_counters + kOccludedCountWord : nullptr;
+    const hipError_t e = launch_occluded(A, mode, s);
+    if (e != hipSuccess) return hip_fail(e, "launch k_occluded");
+    return RTK_OK;
+}
+
+int rtk_accel_occluded_device(rtk_accel *a, const rtk_ray *d_rays, const float *d_max_t, size_t n, float shadow_bias, int mode,
+                              uint8_t *d_out, void *stream) {
+    int rc = occluded_check(a, d_rays, d_max_t, n, shadow_bias, mode, d_out);
+    if (rc != RTK_OK) return rc;
+    if (n == 0) return RTK_OK;
+    std::lock_guard<std::mutex> lock(a->mu);
+    rc = ensure_device(a);
+    if (rc != RTK_OK) return rc;
+    return occluded_launch(a, d_rays, d_max_t, n, shadow_bias, mode, d_out, static_cast<hipStream_t>(stream), false);
+}
+
+int rtk_accel_occluded(rtk_accel *a, const rtk_ray *rays, const float *max_t, size_t n, float shadow_bias, int mode, uint8_t *out,
+                       uint64_t *n_intersections) {
+    int rc = occluded_check(a, rays, max_t, n, shadow_bias, mode, out);
+    if (rc != RTK_OK) return rc;
+    if (n == 0) {
+        if (n_intersections) *n_intersections = 0;
+        return RTK_OK;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    rc = ensure_device(a);
+    if (rc != RTK_OK) return rc;
+    if (a->oc_cap < n) {
+        (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
+        a->oc_rays = nullptr; a->oc_max_t = nullptr; a->oc_out = nullptr; a->oc_cap = 0;
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_rays), n * sizeof(rtk_ray)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_max_t), n * sizeof(float)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_out), n));
+        a->oc_cap = n;
+    }
+    RTK_HIP(hipMemcpy(a->oc_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+    RTK_HIP(hipMemcpy(a->oc_max_t, max_t, n * sizeof(float), hipMemcpyHostToDevice));
+    if (n_intersections) RTK_HIP(hipMemsetAsync(a->d_counters + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
+    rc = occluded_launch(a, a->oc_rays, a->oc_max_t, n, shadow_bias, mode, a->oc_out, nullptr, n_intersections != nullptr);
+    if (rc != RTK_OK) return rc;
+    RTK_HIP(hipMemcpy(out, a->oc_out, n, hipMemcpyDeviceToHost));
+    if (n_intersections) {
+        unsigned long long h = 0;
+        RTK_HIP(hipMemcpy(&h, a->d_counters + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
+        *n_intersections = h;
+    }
     return RTK_OK;
 }
 

@@ -176,6 +176,19 @@ struct hip_accel {
         return res;
     }
 
+    // is_occluded(accel, rays[i], max_t[i]) (render/render.hpp:110-131) for a batch, one query per lane: RTK_OCC_CLEAR,
+    // RTK_OCC_OCCLUDED, or RTK_OCC_STEP_LIMIT for a query the reference would still be stepping after RTK_OCCLUDED_MAX_STEPS hits
+    [[nodiscard]] std::vector<std::uint8_t> occluded_batch(const std::vector<ray3<F>> &rays, const std::vector<F> &max_t, F shadow_bias) const {
+        if (max_t.size() != rays.size()) throw std::invalid_argument("hip_accel::occluded_batch: one max_t per ray");
+        std::vector<rtk_ray> in(rays.size());
+        for (std::size_t i = 0; i < rays.size(); ++i)
+            in[i] = rtk_ray{{rays[i].origin.x, rays[i].origin.y, rays[i].origin.z},
+                            {rays[i].direction.x, rays[i].direction.y, rays[i].direction.z}};
+        std::vector<std::uint8_t> out(rays.size());
+        check(rtk_accel_occluded(accel_.get(), in.data(), max_t.data(), in.size(), shadow_bias, RTK_TRACE_AUTO, out.data(), nullptr));
+        return out;
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running

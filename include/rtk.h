@@ -187,7 +187,9 @@ typedef struct {
                                      * every rank the same columns), bucket (bx, by) to rank (bx + by) % world_size */
     int32_t collect_stats;          /* 1 = also count nodes/leaves/triangles per ray, as the reference algorithm visits them
                                      * (slower kernel variant); 2 = count what the production path visits (its occlusion
-                                     * queries stop at the first answering hit when no material is transmissive; same frame) */
+                                     * queries stop at the first answering hit when no material is transmissive, and those
+                                     * whose light contribution is +-0 in every channel are counted in `rays` but not traced:
+                                     * RTK_SKIP_UNLIT_SHADOW; same frame, same `rays`) */
     /* Progressive accumulation (the spp loop of render/render.hpp:34-72 cut into passes): render samples
      * [sample_begin, sample_begin + sample_count) of every pixel.  sample_count == 0: all `spp` samples in one call.
      * A pass with sample_begin > 0 continues the running per-pixel sum the previous pass left in the output buffer (the
@@ -197,7 +199,8 @@ typedef struct {
 } rtk_render_params;
 
 typedef struct {
-    uint64_t rays;                  /* intersect() invocations (primary + shadow segments + reflection + refraction + GI) */
+    uint64_t rays;                  /* the reference's intersect() invocations (primary + shadow segments + reflection + refraction
+                                     * + GI), whether or not the production path had to traverse the tree to answer them */
     uint64_t primary;               /* camera rays */
     uint64_t hits;                  /* valid only with collect_stats */
     uint64_t nodes;                 /* tree nodes popped, per ray, summed           (collect_stats) */

@@ -313,7 +313,7 @@ class RenderConfig:
     trace_mode: int = TRACE_AUTO
     rank: int = 0
     world_size: int = 1
-    collect_stats: int = 0     # 1 (or True): per-ray work counters of the reference algorithm; 2: of the production path (early-exit occlusion queries)
+    collect_stats: int = 0     # 1 (or True): per-ray work counters of the reference algorithm; 2: of the production path (early-exit occlusion queries; unlit ones untraced, RTK_SKIP_UNLIT_SHADOW)
     sample_begin: int = 0      # progressive accumulation: this call renders samples [sample_begin, sample_begin + sample_count)
     sample_count: int = 0      # 0 = all spp samples in one call
 

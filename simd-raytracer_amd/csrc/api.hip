@@ -51,6 +51,7 @@ int upload(const std::vector<T> &src, T **dst) {
 struct rtk_knobs {
     uint32_t slice_min_tris = rtk::kSliceMinTrisDefault;   // RTK_SLICE_MIN_TRIS
     bool shadow_exit = true;                                // RTK_SHADOW_EARLY_EXIT
+    bool skip_unlit_shadow = true;                          // RTK_SKIP_UNLIT_SHADOW: occlusion queries that cannot change the pixel are not traced
     bool bundle_cull = true;                                // RTK_BUNDLE_CULL
     bool auto_trials = true;                                // RTK_AUTO_TRIALS
     bool cost_feedback = true;                              // RTK_COST_FEEDBACK
@@ -88,6 +89,7 @@ struct rtk_knobs {
         long v;
         if (geti("RTK_SLICE_MIN_TRIS", v) && v > 0) k.slice_min_tris = uint32_t(v);
         if (geti("RTK_SHADOW_EARLY_EXIT", v)) k.shadow_exit = v != 0;
+        if (geti("RTK_SKIP_UNLIT_SHADOW", v)) k.skip_unlit_shadow = v != 0;
         if (geti("RTK_BUNDLE_CULL", v)) k.bundle_cull = v != 0;
         if (geti("RTK_AUTO_TRIALS", v)) k.auto_trials = v != 0;
         if (geti("RTK_COST_FEEDBACK", v)) k.cost_feedback = v != 0;
@@ -976,6 +978,9 @@ static int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d
     // frame is bit-identical (trace.hip.hpp, `exit_t`), only the per-ray work counters shrink.  collect_stats == 1 counts the
     // reference's work (every ray traced to the end), collect_stats == 2 the work of the production path.
     A.shadow_exit = (a->knobs.shadow_exit && !a->has_refractive && p->collect_stats != 1) ? 1 : 0;
+    // Likewise an occlusion query whose light contribution is +-0 in every channel is counted in `rays` but not traced
+    // (common.hip.hpp, unlit_query): the same frame and ray count, less work under collect_stats 0 and 2.
+    A.skip_unlit = (a->knobs.skip_unlit_shadow && !a->has_refractive && p->collect_stats != 1) ? 1 : 0;
     A.occl_on = (a->occl_on && p->collect_stats == 0) ? 1 : 0;
     A.occl = A.tree;
     if (A.occl_on) {

@@ -92,6 +92,30 @@ __device__ __forceinline__ V3 sample_texture(const DevTexture *T, const DevTriUv
     return ((u2 + v2) % 2 == 0) ? a : b;
 }
 
+// Unlit occlusion queries (RenderArgs::skip_unlit).  The light loop (render.hpp:184-208, :213-236) computes
+// contrib = (intensity / area) * cosine, asks is_occluded, and adds `contrib * albedo` only if the answer is "clear".  When that
+// addend compares equal to 0.0f in all three channels (+0 or -0) the answer cannot change the pixel, so the ray is counted but
+// never traced, and the lane is treated as clear:
+//  1. x + (+-0) has the bits of x for every x that is not -0 (a NaN stays the NaN it was).  The sums the addend goes into
+//     (`final_color` there; acc, Frame::a[9..11] and k_combine's acc here) start as +0 and are only ever results of float
+//     additions; under round-to-nearest a sum is -0 only if both operands are -0, so a chain that starts at +0 never holds -0.
+//     Adding the +-0 (clear) and not adding it (occluded) give the same bits.
+//  2. The test is on the addend, not on the cosine: a NaN or infinite contrib or albedo (inf * 0) makes a NaN addend, which does
+//     not compare equal to zero, and the ray is traced as ever.  Lights of intensity 0, lights behind or in the plane of the
+//     surface and black albedos need no case of their own.
+//  3. is_occluded (render.hpp:110-131) has no effect but its accel.intersect calls: exactly one when 0 < radius and no material
+//     is transmissive -- still counted in `rays`.  With transmissive materials the number of calls depends on the walk, and the
+//     host leaves the rule off (as under collect_stats == 1, which reports the reference's per-ray work).
+// One float per lane carries the albedo to whoever computes contrib (the helper waves of a light burst): |contrib * a_c| =
+// round(|contrib| * |a_c|) is monotone in |a_c|, so all three channels are +-0 exactly when the channel of largest magnitude
+// is; a NaN channel never is, hence the NaN.  An infinite channel gives inf or NaN, never 0.
+__device__ __forceinline__ float albedo_reach(const V3 a) {
+    const float x = __builtin_fabsf(a.x), y = __builtin_fabsf(a.y), z = __builtin_fabsf(a.z);
+    const float m = x < y ? (y < z ? z : y) : (x < z ? z : x);
+    return (x != x || y != y || z != z) ? __builtin_nanf("") : m;
+}
+__device__ __forceinline__ bool unlit_query(const float contrib, const float reach) { return contrib * reach == 0.0f; }
+
 // Camera ray of pixel (px, py) (render.hpp:35-62); `key` is the sample's root key (draws 0 and 1 jitter the sample).
 __device__ __forceinline__ Ray camera_ray(const RenderArgs &A, const uint32_t px, const uint32_t py, const uint32_t key) {
     float rx = (float)px, ry = (float)py;

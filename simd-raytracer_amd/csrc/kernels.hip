@@ -130,7 +130,7 @@ __device__ __forceinline__ uint32_t burst_part(const V3 d, const bool in, const 
 template <int SLICES>
 struct ShadowBurstService {
     const RenderArgs &A;
-    float4 *res;             // [jobs][64] answers: contribution, clear, flags (bit 0: a ray was traced; bit 1: this job answers for the lane)
+    float4 *res;             // [jobs][64] answers: contribution, clear, flags (bit 0: a ray was asked for (counted); bit 1: this job answers for the lane)
     // Jobs (light, part) are handed out through a counter in LDS: a wave that is done takes the next one, so unequal jobs
     // (one half of a cone over the mesh, the other past it) even out.  Job 0 is the owner's own.
     __device__ __forceinline__ void operator()(GroupShared *sh, const uint32_t slice) const {
@@ -160,7 +160,10 @@ struct ShadowBurstService {
             const float cosine = (0.0f < d0) ? d0 : 0.0f;
             const float contrib = (L->intensity / area) * cosine;
             const bool mine = in_burst & (burst_part(ld, in_burst, plog) == part);
-            const bool q = mine & (0.0f < radius);                           // is_occluded's loop guard, render.hpp:114
+            const bool asked = mine & (0.0f < radius);                       // is_occluded's loop guard, render.hpp:114
+            // counted, not traced, when it cannot light the lane (unlit_query(); b.z = the lane's albedo_reach).  A job none of
+            // whose lanes is lit ends in trace() before any bundle is made.
+            const bool q = asked & !(A.skip_unlit != 0 && unlit_query(contrib, b.z));
             const Ray ray = make_ray(P + (A.shadow_bias * ld), ld);
             Stats st = {0, 0, 0, 0, 0, 0};
             SliceCtx sx = {nullptr, 0xFFFFFFFFu, 0u, true, 0u, group_private_bundles<SLICES>(sh, slice)};
@@ -169,7 +172,8 @@ struct ShadowBurstService {
                                                                   kClsHasApex | (0x100u + k), lp);
             bool clear = true;
             uint32_t fl = mine ? 2u : 0u;
-            if (q) { clear = (c.k == kMiss) | (radius < c.t); fl |= 1u; }   // render.hpp:117
+            if (asked) fl |= 1u;
+            if (q) clear = (c.k == kMiss) | (radius < c.t);                  // render.hpp:117
             res[job * 64u + lane] = make_float4(contrib, clear ? 1.0f : 0.0f, __uint_as_float(fl), 0.0f);
         }
     }
@@ -547,7 +551,14 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         // quotients are only read by the box tests of the query, and would otherwise sit in (or be spilled from) three
         // registers from the shading code to this point
         ray.inv = mk((1.0f / ray.d.x), (1.0f / ray.d.y), (1.0f / ray.d.z));
-        const bool in_root = kRootFirst ? enters_root(A.tree, ray, need) : need;
+        // An occlusion query whose contribution is +-0 whatever the answer is counted and consumed as ever (a miss: "clear", and
+        // the +-0 is added), but takes no part in the trace (common.hip.hpp, unlit_query): not in the root test either, so that an
+        // iteration of unlit lanes alone is `quiet`.  Each lane still spends one iteration per light: lanes that ran ahead on
+        // their own would stand at different lights, and a burst forms only when they all stand at the same one.
+        const float reach = albedo_reach(albedo);
+        const bool unlit = (A.skip_unlit != 0) & need & (pend == PEND_SHADOW) && unlit_query(contrib, reach);
+        const bool traced = need & !unlit;
+        const bool in_root = kRootFirst ? enters_root(A.tree, ray, traced) : traced;
         // light burst (ShadowBurstService): every lane about to query a light is at the same light, and more lights follow
         bool burst = false;
         uint32_t burst_k = 0u, burst_plog = 0u, burst_nl = 0u;
@@ -563,6 +574,21 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 burst_nl = left < kBurstMaxJobs ? left : kBurstMaxJobs;                      // lights of this burst
                 burst_plog = (burst_nl * 4u <= kBurstMaxJobs) ? 2u : (burst_nl * 2u <= kBurstMaxJobs) ? 1u : 0u;
                 burst = (__builtin_amdgcn_ballot_w64(sh_lane & ((uint32_t)light_k != burst_k)) == 0ull) & (1u < (burst_nl << burst_plog));
+                if (burst && A.skip_unlit != 0) {
+                    // no burst when no shadow lane is lit by any of its lights: nobody would trace anything
+                    bool lit = sh_lane & !unlit;
+                    for (uint32_t s = 1u; s < burst_nl; ++s) {
+                        const DevLight *L = A.lights + burst_k + s;                          // wave-uniform
+                        V3 ld = mk(L->pos[0], L->pos[1], L->pos[2]) - P;                     // the light loop body of ST_LIGHT, verbatim
+                        const float radius = length(ld);
+                        const float area = 4.0f * PI_F * radius * radius;
+                        ld = normalized(ld);
+                        const float d0 = dot(ld, ncos);
+                        const float cosine = (0.0f < d0) ? d0 : 0.0f;
+                        lit |= sh_lane & !unlit_query((L->intensity / area) * cosine, reach);
+                    }
+                    burst = wave_any(lit);
+                }
                 if (burst) burst_my_part = burst_part(ray.d, sh_lane, burst_plog);   // (every shadow lane of a burst is at light burst_k)
                 elsewhere = burst & sh_lane & (burst_my_part != 0u);
             }
@@ -613,7 +639,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
             if (burst) {
                 const uint32_t lane = fresh_lane();
                 group_sh->ray_o[lane] = make_float4(P.x, P.y, P.z, ncos.x);
-                group_sh->ray_d[lane] = make_float4(ncos.y, ncos.z, 0.f, 0.f);
+                group_sh->ray_d[lane] = make_float4(ncos.y, ncos.z, reach, 0.f);
                 if (lane == 0u) {
                     group_sh->pass_mask = burst_mask; group_sh->first = burst_k; group_sh->count = burst_plog | ((burst_nl << burst_plog) << 8);
                     group_sh->pad[0] = 1u;                                  // next job to hand out (job 0 is traced right here)
@@ -626,7 +652,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 __syncthreads();                                            // B1: the helpers start on their lights
                 sx.min_tris = 0xFFFFFFFFu;                                  // (they are busy: the owner's own leaves stay whole)
             }
-            cand = trace<MODE, STATS, kStage, SLICES, kRootFirst>(A.tree, lds_nodes, ray, cull, in_root & !elsewhere, st, sx, kAutoMinLanes, exit_t, cls, apex);
+            cand = trace<MODE, STATS, kStage, SLICES, kRootFirst>(A.tree, lds_nodes, ray, cull, in_root & !elsewhere, st, sx, kAutoMinLanes, exit_t, cls, apex);   // (in_root: no unlit lane)
 #ifdef RTK_DEBUG_PHASES
             const unsigned long long ph_w0 = __builtin_readcyclecounter();
 #endif

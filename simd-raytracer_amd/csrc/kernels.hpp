@@ -101,6 +101,7 @@ struct RenderArgs {
     const uint32_t *order_hdr;        // {n_workgroups, n}: see launch_order_by_cost
     const uint32_t *wg_list;          // [n_workgroups] a block id, or 0x80000000 | index into order_in of the first block of a packed workgroup
     int shadow_exit;                  // occlusion queries may stop at the first answering hit (no transmissive material; trace())
+    int skip_unlit;                   // occlusion queries whose light contribution is +-0 in every channel are counted but not traced (unlit_query())
     // RTK_TRAVERSAL_FAST on a scene with transmissive materials: `occl` is the tree without the transmissive triangles, and an occlusion
     // query of the streaming pipeline (k_shadow) is ONE any-hit query against it instead of is_occluded's stepping loop (rtk.h)
     int occl_on;

@@ -445,6 +445,13 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_shadow(StreamArgs S) 
         float max_t = radius;
         bool pending = valid & (0.0f < radius);                              // is_occluded's loop guard, render.hpp:114
         bool clear = true;
+        if (A.skip_unlit != 0 && pending) {
+            // a query that adds +-0 whatever its answer is counted and left "clear", not traced (common.hip.hpp, unlit_query);
+            // the albedo is the one k_combine multiplies by: the material's, or the sampled colour kept in the hit's node
+            const DevMaterial *m = A.materials + __float_as_uint(b.w);
+            const float *al = m->kind == RTK_MAT_TEXTURE ? S.ws.nodes[__float_as_uint(a.w)].value : m->albedo;
+            if (unlit_query(contrib, albedo_reach(mk(al[0], al[1], al[2])))) { pending = false; nrays += 1u; }
+        }
         while (wave_any(pending)) {
             // no transmissive material in the scene: the query may stop at the first hit nearer than the light (trace(), `exit_t`)
             // (occl_on: RTK_TRAVERSAL_FAST's tree of the opaque triangles -- nothing transmissive in it either)

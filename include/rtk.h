@@ -293,6 +293,51 @@ int rtk_accel_occluded_device(rtk_accel *accel, const rtk_ray *d_rays, const flo
                               float shadow_bias, int trace_mode, uint8_t *d_out,
                               void *hip_stream);                          /* device buffers, stream-ordered */
 
+/* ---- batched radiance: replaces `intersect<cull>(ray)` followed by color_hit(accel, hit, 0) (render/render.hpp:64-69, 133-308) ---- */
+typedef struct {
+    int32_t max_ray_depth;          /* config.hpp max_ray_depth; 0..16 as for frames */
+    int32_t diffuse_rays;           /* diffuse_reflection_ray_count */
+    uint32_t seed;                  /* fixed_rng_seed */
+    int32_t sample;                 /* which sample of `seed`'s sequence these rays are (see ids) */
+    float shadow_bias, reflection_bias, refraction_bias;
+    int32_t cull;                   /* the <cull> of the batch's own rays: 1 = as render_frame's camera rays (:64), 0 = as a secondary ray */
+    int32_t trace_mode;             /* RTK_TRACE_AUTO or RTK_TRACE_STREAM; everything else RTK_ERR_INVALID */
+} rtk_radiance_params;
+/* Per ray i, in float, in the reference's operation order:
+ *     h = intersect<cull>(rays[i])
+ *     c = h ? color_hit(accel, *h, 0) : background_color
+ *     rgb[i] = color{} += c                       // what render_frame leaves in a pixel at samples_per_pixel == 1
+ *                                                 // (render.hpp:33,66-72: a channel that is -0 comes out +0, "/ 1" changes nothing)
+ * One colour per ray, written in the caller's order; nothing accumulates across calls.  Rays need not share an origin and
+ * need not be normalised (the reference's own secondary rays are not always).  The scene's camera plays no part.
+ * Random numbers (diffuse GI only): a draw is keyed by a ray's position in its sample's ray tree, root key =
+ * f(seed, pixel index, sample).  Ray i gets the root key of pixel index `ids ? ids[i] : (uint32_t)i` at sample `p->sample`.  So the
+ * rays of rtk_camera_rays(.., sample s) with ids == NULL, cull = 1, sample = s give exactly sample s of rtk_render_frame with the
+ * same parameters, diffuse GI included; a caller's sum over s in order, divided by float(spp) (render.hpp:66-72), gives the
+ * frame.  Without diffuse rays ids, seed and sample cannot change a result.
+ * counters (host variant, may be NULL) as for a frame: rays = the reference's intersect() invocations the batch stands for,
+ * its own n level-0 rays included; primary = n; the collect_stats fields are 0.  The counters of the most recent frame
+ * (rtk_render_last_counters) are left alone.
+ * Occlusion queries inside the recursion are answered as in frames, with the same switches (they stop at the first
+ * answering hit when no material is transmissive; RTK_SKIP_UNLIT_SHADOW): same colours, same `rays`.  On an accel built with
+ * RTK_TRAVERSAL_FAST the call has the caveats frames have there (ties at exactly equal t, occlusion through transmissive
+ * surfaces answered from the opaque triangles); parity with the reference is claimed for RTK_TRAVERSAL_REFERENCE only.
+ * The batch runs through the streaming pipeline (RTK_TRACE_STREAM's; RTK_TRACE_AUTO means the same here) in chunks.  A chunk
+ * whose ray tree outgrows its queues is redone on the device by a per-ray kernel: slower, the same bits.
+ * Errors: a NULL accel or p, another trace_mode, max_ray_depth outside [0, 16], diffuse_rays < 0, sample < 0, a non-finite bias,
+ * n > 0 with NULL rays / rgb, ids == NULL with n > 2^32 -> RTK_ERR_INVALID, and the accel stays usable.  Then n == 0 -> RTK_OK,
+ * nothing touched, device or not.  Then no device -> RTK_ERR_NO_DEVICE.
+ * The host variant is synchronous.  The device variant is stream-ordered and never synchronises the host; it allocates
+ * (and then synchronises the device once) when a batch needs more queue space than any call before it on this accel.  It is
+ * NOT stream-capturable: the pipeline forks onto streams of its own.
+ * The queues belong to the accel and are shared with RTK_TRACE_STREAM frames.  A radiance batch (or such a frame) issued on
+ * another stream than the previous user of the queues waits for that user ON THE DEVICE (an event) before it touches them:
+ * calls on different streams are safe and take turns.  d_rays: 4-byte aligned, 24 bytes per ray; d_rgb: 4-byte aligned. */
+int rtk_accel_radiance(rtk_accel *accel, const rtk_ray *rays, const uint32_t *ids /* may be NULL */, size_t n,
+                       const rtk_radiance_params *p, float *rgb /* host [n][3] */, rtk_counters *counters /* may be NULL */);
+int rtk_accel_radiance_device(rtk_accel *accel, const rtk_ray *d_rays, const uint32_t *d_ids /* may be NULL */, size_t n,
+                              const rtk_radiance_params *p, float *d_rgb /* device [n][3] */, void *hip_stream);
+
 /* ---- frame: replaces render_frame<A,F> (render/render.hpp:18-108) with color_hit/is_occluded device-side ---- */
 /* number of floats the (rank-local) output of rtk_render_frame_device holds */
 int rtk_render_output_floats(const rtk_accel *accel, const rtk_render_params *p, size_t *n_floats);

@@ -4,6 +4,7 @@ Names follow the reference (paths relative to /root/reference/include/raytracer/
   parse_scene_file      io/json/loader.hpp:235-265
   KdTreeSimdAccel       render/accel/kd_tree_simd.hpp:63-98 (ctor from a scene, intersect<cull>)
   KdTreeSimdAccel.occluded   render/render.hpp:110-131 (is_occluded)
+  KdTreeSimdAccel.radiance   render/render.hpp:64-69, 133-308 (intersect<cull> + color_hit for caller-supplied rays)
   render_frame          render/render.hpp:18-108
   write_ppm             io/image/ppm.hpp:7-25
 
@@ -41,6 +42,7 @@ ABI_SYMBOLS = [
     "rtk_accel_build", "rtk_accel_tree_info", "rtk_accel_tree_dump", "rtk_accel_destroy",
     "rtk_accel_intersect", "rtk_accel_intersect_device", "rtk_accel_intersect_stats",
     "rtk_accel_occluded", "rtk_accel_occluded_device",
+    "rtk_accel_radiance", "rtk_accel_radiance_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
@@ -112,6 +114,12 @@ class RenderParams(C.Structure):
                 ("sample_begin", C.c_int32), ("sample_count", C.c_int32)]
 
 
+class RadianceParams(C.Structure):
+    _fields_ = [("max_ray_depth", C.c_int32), ("diffuse_rays", C.c_int32), ("seed", C.c_uint32), ("sample", C.c_int32),
+                ("shadow_bias", C.c_float), ("reflection_bias", C.c_float), ("refraction_bias", C.c_float),
+                ("cull", C.c_int32), ("trace_mode", C.c_int32)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rays", "primary", "hits", "nodes", "boxpass", "leaves", "tris", "packets16")]
 
@@ -147,6 +155,8 @@ _L.rtk_accel_intersect_device.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int
 _L.rtk_accel_intersect_stats.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.POINTER(Counters)]
 _L.rtk_accel_occluded.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, _vp, C.POINTER(C.c_uint64)]
 _L.rtk_accel_occluded_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, _vp, _vp]
+_L.rtk_accel_radiance.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceParams), _vp, C.POINTER(Counters)]
+_L.rtk_accel_radiance_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceParams), _vp, _vp]
 _L.rtk_render_output_floats.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]
 _L.rtk_render_frame.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.POINTER(Counters)]
 _L.rtk_render_frame_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp]
@@ -324,6 +334,25 @@ class RenderConfig:
                             int(self.collect_stats), self.sample_begin, self.sample_count)
 
 
+@dataclass
+class RadianceConfig:
+    """rtk_radiance_params: what color_hit needs of config.hpp:6-17, + the RNG sample and the <cull> of the batch's own rays."""
+    max_ray_depth: int = 5
+    diffuse_rays: int = 0
+    seed: int = 42
+    sample: int = 0            # which sample of `seed`'s sequence the rays are (with ids: the RNG root key of every ray)
+    shadow_bias: float = 1e-4
+    reflection_bias: float = 1e-4
+    refraction_bias: float = 1e-4
+    cull: bool = True          # True: as render_frame's camera rays (render.hpp:64); False: as a secondary ray
+    trace_mode: int = TRACE_AUTO
+
+    def to_c(self) -> RadianceParams:
+        return RadianceParams(self.max_ray_depth, self.diffuse_rays, self.seed, self.sample, np.float32(self.shadow_bias),
+                              np.float32(self.reflection_bias), np.float32(self.refraction_bias), 1 if self.cull else 0,
+                              self.trace_mode)
+
+
 class KdTreeSimdAccel:
     """kd_tree_simd_accel<float, eps, max_depth, max_leaf_size> (render/accel/kd_tree_simd.hpp:63-98).
 
@@ -387,6 +416,32 @@ class KdTreeSimdAccel:
                         trace_mode: int = TRACE_AUTO, stream: int = 0) -> None:
         _check(_L.rtk_accel_occluded_device(self._h, d_rays_ptr, d_max_t_ptr, n, np.float32(shadow_bias), trace_mode,
                                             d_out_ptr, stream))
+
+    # ---- intersect<cull>(ray) + color_hit(accel, hit, 0), batched
+    def radiance(self, rays: np.ndarray, ids: np.ndarray | None = None, cfg: RadianceConfig | None = None):
+        """The colour every ray sees (render/render.hpp:64-69, 133-308) for rays [n,6] float32 in host memory ->
+        ([n,3] float32, counters dict).  ids [n] uint32: the pixel index of each ray's RNG root key (None: the ray's index)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        if ids is not None:
+            ids = np.ascontiguousarray(ids)
+            if ids.shape != (n,):
+                raise ValueError("one id per ray")
+            if ids.dtype.kind not in "iu" or (n and (int(ids.min()) < 0 or int(ids.max()) > 0xFFFFFFFF)):
+                raise ValueError("ids are unsigned 32-bit pixel indices")
+            ids = np.ascontiguousarray(ids, np.uint32)
+        p = (cfg or RadianceConfig()).to_c()
+        rgb = np.zeros((n, 3), np.float32)
+        c = Counters()
+        _check(_L.rtk_accel_radiance(self._h, rays.ctypes.data, None if ids is None else ids.ctypes.data, n, C.byref(p),
+                                     rgb.ctypes.data, C.byref(c)))
+        return rgb, c.as_dict()
+
+    def radiance_device(self, d_rays_ptr: int, d_ids_ptr: int, n: int, d_rgb_ptr: int, cfg: RadianceConfig | None = None,
+                        stream: int = 0) -> None:
+        """Device buffers (d_ids_ptr 0 = no ids), stream-ordered; not capturable into a graph (rtk.h)."""
+        p = (cfg or RadianceConfig()).to_c()
+        _check(_L.rtk_accel_radiance_device(self._h, d_rays_ptr, d_ids_ptr or None, n, C.byref(p), d_rgb_ptr or None, stream))
 
     # ---- frames
     def output_floats(self, cfg: RenderConfig) -> int:

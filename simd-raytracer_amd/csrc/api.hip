@@ -203,6 +203,16 @@ struct rtk_accel {
     float *oc_max_t = nullptr;
     uint8_t *oc_out = nullptr;
     size_t oc_cap = 0;
+    // batched radiance (rtk_accel_radiance): one kCounterWords block per lane for a chunk's pipeline, then {rays, chunks redone} of the call
+    unsigned long long *d_rad_counters = nullptr;
+    // the streaming workspace's last user (a STREAM frame or a radiance batch) recorded ws_done: a radiance batch on any stream waits for it
+    hipEvent_t ws_done = nullptr;
+    bool ws_in_use = false;
+    // staging of the host variant of the radiance batch: grows, never shrinks
+    rtk_ray *rad_rays = nullptr;
+    uint32_t *rad_ids = nullptr;
+    float *rad_rgb = nullptr;
+    size_t rad_cap = 0;
     hipStream_t last_stream = nullptr;
     uint64_t last_primary = 0;
     bool last_stats = false;
@@ -682,6 +692,8 @@ void rtk_accel_destroy(rtk_accel *a) {
         (void)hipFree(a->rp_bounds); (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
         (void)hipFree(a->fb_cost); (void)hipFree(a->fb_order); (void)hipFree(a->fb_bins);
         (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
+        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb); (void)hipFree(a->d_rad_counters);
+        if (a->ws_done) (void)hipEventDestroy(a->ws_done);
         for (auto &e : a->trial_ev) if (e) (void)hipEventDestroy(e);
         if (a->rp_done) (void)hipEventDestroy(a->rp_done);
         if (a->rp_probe_ev) (void)hipEventDestroy(a->rp_probe_ev);
@@ -1093,6 +1105,9 @@ static int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d
             }
         }
         S.nodes_sorted = S.hits_sorted = S.bin_children = S.bin_hits = 0;
+        S.user_rays = nullptr; S.user_ids = nullptr; S.user_n = S.user_id0 = S.user_sample = S.user_cull = 0u;
+        // (a radiance batch, possibly on another stream, may still be in these queues: rtk.h, rtk_accel_radiance)
+        if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
         for (int j = 0; j < lanes; ++j) RTK_HIP(hipMemsetAsync(a->ws_lane[j].ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), s));
         // fork: lane 0 is the caller's stream, the other lanes wait for everything enqueued on it so far
         if (lanes > 1) {
@@ -1125,6 +1140,9 @@ static int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d
         F.only_if = a->ws.ctrl + dev::kCtrlOverflow;
         ef = launch_render(F, RTK_TRACE_GROUP4, p->collect_stats != 0, general, s);
         if (ef != hipSuccess) return hip_fail(ef, "launch fallback k_render");
+        if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
+        RTK_HIP(hipEventRecord(a->ws_done, s));
+        a->ws_in_use = true;
         if (a->knobs.stream_debug) {
             uint32_t h[dev::kCtrlWords];
             (void)hipStreamSynchronize(s);
@@ -1313,6 +1331,177 @@ int rtk_tiles_assemble_device(const rtk_accel *a, const rtk_render_params *p, co
     A.tiles_x = g.tiles_x; A.world = uint32_t(g.world); A.buckets_per_rank = g.buckets_per_rank; A.skew_q = g.skew_q;
     const hipError_t e = launch_assemble(A, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "launch k_assemble");
+    return RTK_OK;
+}
+
+// ---------------------------------------------------------------- batched radiance
+
+// Rays of one chunk at most: a chunk's ray tree goes through one lane's queues (32-bit node ids, ~120 B per node).
+static constexpr size_t kRadianceChunkRays = size_t(1) << 22;
+
+static int radiance_check(const rtk_accel *a, const void *rays, const void *ids, size_t n, const rtk_radiance_params *p, const void *rgb) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    if (p->trace_mode != RTK_TRACE_AUTO && p->trace_mode != RTK_TRACE_STREAM)
+        return fail(RTK_ERR_INVALID, "trace_mode of a radiance batch must be RTK_TRACE_AUTO or RTK_TRACE_STREAM");
+    if (p->max_ray_depth < 0 || p->max_ray_depth > kMaxRayDepth) return fail(RTK_ERR_INVALID, "max_ray_depth must be in [0, 16]");
+    if (p->diffuse_rays < 0 || p->diffuse_rays > 32767) return fail(RTK_ERR_INVALID, "diffuse_rays must be in [0, 32767]");
+    if (p->sample < 0) return fail(RTK_ERR_INVALID, "sample must be >= 0");
+    if (!std::isfinite(p->shadow_bias) || !std::isfinite(p->reflection_bias) || !std::isfinite(p->refraction_bias))
+        return fail(RTK_ERR_INVALID, "shadow_bias, reflection_bias and refraction_bias must be finite");
+    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many rays for one call");
+    if (n > 0 && (!rays || !rgb)) return fail(RTK_ERR_INVALID, "null ray or colour buffer");
+    if (!ids && n > (size_t(1) << 32)) return fail(RTK_ERR_INVALID, "more than 2^32 rays need explicit ids");
+    return RTK_OK;
+}
+
+// The batch cut into chunks, every chunk one run of the streaming pipeline (level 0 = the chunk's rays) on one of the accel's
+// lanes, followed by its counter fold and its overflow fallback.  Nothing here waits on the host.
+static int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
+                                float *d_rgb, hipStream_t s, uint32_t *n_chunks_out) {
+    dev::RenderArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.tree = tree_view(a);
+    A.materials = a->d_materials; A.lights = a->d_lights;
+    A.textures = a->d_textures; A.tri_uv = a->d_tri_uv; A.tex_pixels = a->d_tex_pixels;
+    A.n_lights = int(a->scene.lights.size());
+    A.has_refractive = a->has_refractive ? 1 : 0;
+    std::memcpy(A.background, a->scene.background, sizeof(A.background));
+    // one colour per ray: "sample 0 of 1" for k_combine, whatever sample the RNG keys name
+    A.spp = 1; A.sample_begin = 0; A.sample_end = 1; A.spp_f = 1.0f;
+    A.max_depth = p->max_ray_depth; A.diffuse_rays = p->diffuse_rays; A.seed = p->seed;
+    A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
+    A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
+    A.world = 1;
+    A.slice_min_tris = a->knobs.slice_min_tris;
+    // as render_device_impl without collect_stats
+    A.shadow_exit = (a->knobs.shadow_exit && !a->has_refractive) ? 1 : 0;
+    A.skip_unlit = (a->knobs.skip_unlit_shadow && !a->has_refractive) ? 1 : 0;
+    A.occl_on = a->occl_on ? 1 : 0;
+    A.occl = A.tree;
+    if (A.occl_on) {
+        A.occl.nodes = a->d_occl_nodes; A.occl.leaves = a->d_occl_leaves; A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
+        A.occl.tris = a->d_occl_tris; A.occl.tri_ids = a->d_occl_ids;
+    }
+    const bool forks = a->has_refractive || p->diffuse_rays > 0;
+    // chunk size and lanes: the rule of STREAM frames (render_device_impl) with a chunk in the place of a sample
+    const size_t factor = a->knobs.stream_node_factor > 0 ? size_t(a->knobs.stream_node_factor) : (forks ? 8 : 3);
+    const size_t bytes_per_node = sizeof(dev::RayRec) + sizeof(dev::NodeRes) + sizeof(uint32_t) +
+                                  (sizeof(dev::HitRec) + sizeof(uint32_t) + sizeof(float2) * (a->scene.lights.empty() ? 1 : a->scene.lights.size())) / 2 + 1;
+    const size_t budget = size_t(a->knobs.stream_mem_gb) << 30;
+    const size_t n64 = (n + 63) / 64 * 64;
+    size_t chunk = n64 < kRadianceChunkRays ? n64 : kRadianceChunkRays;
+    auto fits = [&](size_t c, size_t l) { return c * factor + 4096 <= 0xF0000000ull && (c * factor + 4096) * bytes_per_node * l <= budget; };
+    // a batch that has to be cut for the budget is cut so that every lane gets queues: the chunks then overlap as a frame's samples do
+    if (!fits(chunk, 1)) while (chunk > 64 && !fits(chunk, size_t(a->knobs.stream_lanes))) chunk = (chunk / 2 + 63) / 64 * 64;
+    const size_t nodes = chunk * factor + 4096;
+    const size_t n_chunks = (n + chunk - 1) / chunk;
+    int lanes = n_chunks < size_t(a->knobs.stream_lanes) ? int(n_chunks) : a->knobs.stream_lanes;
+    while (lanes > 1 && !fits(chunk, size_t(lanes))) lanes -= 1;
+    if (n_chunks_out) *n_chunks_out = uint32_t(n_chunks);
+    int rc = ensure_stream_ws(a, 0, nodes, a->scene.lights.size(), false, lanes);
+    if (rc != RTK_OK) return rc;
+    unsigned long long *total = nullptr;
+    {
+        const size_t words = size_t(dev::kStreamLanes) * kCounterWords + 2;
+        if (!a->d_rad_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_rad_counters), words * sizeof(unsigned long long)));
+        total = a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords;
+    }
+    // the queues belong to the accel: whoever used them last (a STREAM frame, a batch on another stream) finishes first, on the device
+    if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
+    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
+    a->ws_in_use = true;
+    RTK_HIP(hipMemsetAsync(total, 0, 2 * sizeof(unsigned long long), s));
+
+    dev::StreamArgs S;
+    std::memset(&S, 0, sizeof(S));
+    S.r = A; S.r.tree.scalar_surv = a->knobs.stream_scalar_surv ? 1 : 0;
+    S.key_dirs = p->diffuse_rays > 0 ? 1u : 0u; S.sample = 0; S.n_batch = 1; S.auto_min_lanes = a->knobs.auto_min_lanes;
+    S.n_lanes = 1;                                       // a chunk is judged on its own overflow word (k_combine, depth 0)
+    S.user_sample = uint32_t(p->sample); S.user_cull = p->cull ? 1u : 0u;
+    const int deep_level = a->knobs.stream_deep_level, deep_mode = a->knobs.stream_deep_mode;
+    const int sort_from = a->knobs.stream_sort_from >= 0 ? a->knobs.stream_sort_from : (forks ? 1 : 99);
+    {
+        const DevNode &root = a->tree.dev_nodes[0];
+        for (int k = 0; k < 3; ++k) {
+            const float ext = root.hi[k] - root.lo[k];
+            S.grid_lo[k] = root.lo[k];
+            S.grid_scale[k] = (ext > 0.f && ext < 3.0e38f) ? 16.0f / ext : 0.f;
+        }
+    }
+    if (lanes > 1) {
+        RTK_HIP(hipEventRecord(a->lane_fork, s));
+        for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork, 0));
+    }
+    const bool side = a->knobs.stream_side && lanes <= 2 && lanes <= a->knobs.stream_side_below;
+    for (size_t i = 0; i < n_chunks; ++i) {
+        const int j = int(i % size_t(lanes));
+        const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
+        const size_t first = i * chunk, cn = n - first < chunk ? n - first : chunk;
+        S.ws = a->ws_lane[j];
+        for (int k = 0; k < dev::kStreamLanes; ++k) S.lane_overflow[k] = S.ws.ctrl + dev::kCtrlOverflow;
+        S.user_rays = d_rays + first; S.user_ids = d_ids ? d_ids + first : nullptr;
+        S.user_n = uint32_t(cn); S.user_id0 = uint32_t(first);
+        S.n_root = uint32_t((cn + 63) / 64 * 64); S.n_level0 = S.n_root;
+        S.r.out = d_rgb + first * 3;
+        S.r.counters = a->d_rad_counters + size_t(j) * kCounterWords;
+        RTK_HIP(hipMemsetAsync(S.ws.ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), ls));      // the overflow word included: it is the chunk's
+        RTK_HIP(hipMemsetAsync(S.r.counters, 0, kCounterWords * sizeof(unsigned long long), ls));
+        hipError_t e = launch_stream_sample(S, false, deep_level, deep_mode, sort_from, ls, nullptr, nullptr, side ? &a->lane_side[j] : nullptr,
+                                            a->knobs.stream_slices > 0 ? a->knobs.stream_slices : a->stream_slices_auto);
+        if (e == hipSuccess) e = launch_radiance_fold(S, total, ls);
+        if (e == hipSuccess) e = launch_radiance_fallback(S, total, ls);
+        if (e != hipSuccess) return hip_fail(e, "launch radiance chunk");
+        if (j != 0) RTK_HIP(hipEventRecord(a->lane_done[j], ls));
+    }
+    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j], 0));
+    RTK_HIP(hipEventRecord(a->ws_done, s));
+    return RTK_OK;
+}
+
+int rtk_accel_radiance_device(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
+                              float *d_rgb, void *stream) {
+    int rc = radiance_check(a, d_rays, d_ids, n, p, d_rgb);
+    if (rc != RTK_OK) return rc;
+    if (n == 0) return RTK_OK;
+    std::lock_guard<std::mutex> lock(a->mu);
+    rc = ensure_device(a);
+    if (rc != RTK_OK) return rc;
+    return radiance_device_impl(a, d_rays, d_ids, n, p, d_rgb, static_cast<hipStream_t>(stream), nullptr);
+}
+
+int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, size_t n, const rtk_radiance_params *p, float *rgb,
+                       rtk_counters *counters) {
+    int rc = radiance_check(a, rays, ids, n, p, rgb);
+    if (rc != RTK_OK) return rc;
+    if (n == 0) {
+        if (counters) std::memset(counters, 0, sizeof(*counters));
+        return RTK_OK;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    rc = ensure_device(a);
+    if (rc != RTK_OK) return rc;
+    if (a->rad_cap < n) {
+        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb);
+        a->rad_rays = nullptr; a->rad_ids = nullptr; a->rad_rgb = nullptr; a->rad_cap = 0;
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rays), n * sizeof(rtk_ray)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_ids), n * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rgb), n * 3 * sizeof(float)));
+        a->rad_cap = n;
+    }
+    RTK_HIP(hipMemcpy(a->rad_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+    if (ids) RTK_HIP(hipMemcpy(a->rad_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    uint32_t n_chunks = 0;
+    rc = radiance_device_impl(a, a->rad_rays, ids ? a->rad_ids : nullptr, n, p, a->rad_rgb, nullptr, &n_chunks);
+    if (rc != RTK_OK) return rc;
+    RTK_HIP(hipMemcpy(rgb, a->rad_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    unsigned long long h[2] = {0, 0};
+    RTK_HIP(hipMemcpy(h, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
+    if (counters) {
+        std::memset(counters, 0, sizeof(*counters));
+        counters->rays = h[0]; counters->primary = n;
+    }
+    if (a->knobs.stream_debug)
+        std::fprintf(stderr, "[rtk radiance] rays %zu chunks %u redone %llu node_cap %u\n", n, n_chunks, h[1], a->ws.node_cap);
     return RTK_OK;
 }
 

@@ -172,9 +172,10 @@ __device__ __forceinline__ void store_ray(RayRec *dst, const V3 o, const V3 d, c
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// k_path: LEVEL0 = camera rays, one work unit per 8x8 pixel block (same bucket / rank mapping as k_render);
-// otherwise the depth-`level` nodes, units of 64 consecutive nodes drawn from a ticket.
-template <bool LEVEL0, bool STATS, int SLICES, int MODE>
+// k_path: SRC = PATH_CAMERA: camera rays, one work unit per 8x8 pixel block (same bucket / rank mapping as k_render);
+// PATH_USER: the caller's rays (rtk_accel_radiance), one work unit per 64 consecutive rays of the chunk;
+// PATH_QUEUE: the depth-`level` nodes, units of 64 consecutive nodes drawn from a ticket.
+template <int SRC, bool STATS, int SLICES, int MODE>
 __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
     const RenderArgs &A = S.r;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -224,6 +225,7 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
 
     // (a ticket is good for kTicketItems consecutive work units: the ticket word is one address every wave of the kernel pulls on)
     // (only where there are many units per wave: a short queue is better spread over all waves, one unit each)
+    constexpr bool LEVEL0 = SRC != PATH_QUEUE;
     const uint32_t kPer = (!LEVEL0 && n_items >= 16u * n_units_grid) ? kTicketItems : 1u;
     for (uint32_t tb = gunit; tb * kPer < n_items; tb = LEVEL0 ? n_items : next_item(ctrl + kCtrlTicket + level, n_units_grid))
     for (uint32_t item = tb * kPer; item < n_items && item < (tb + 1u) * kPer; ++item) {
@@ -237,7 +239,24 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
         uint32_t pix = 0xFFFFFFFFu, key = 0u;
         bool miss_bg = true;
         Ray ray;
-        if (LEVEL0) {
+        bool cull = false;
+        if (SRC == PATH_USER) {
+            // (24 B per lane at a 24 B stride: the wave's 1,536 B are consecutive, every line fetched is used whole)
+            const uint32_t i = item * 64u + lane;
+            valid = valid & (i < S.user_n);
+            cull = S.user_cull != 0u;
+            uint32_t id = 0u;
+            if (valid) {
+                const float *p = reinterpret_cast<const float *>(S.user_rays + i);
+                ray = make_ray(mk(p[0], p[1], p[2]), mk(p[3], p[4], p[5]));
+                id = S.user_ids != nullptr ? S.user_ids[i] : S.user_id0 + i;
+                pix = i;
+            } else {
+                ray = make_ray(mk(0.f, 0.f, 0.f), mk(1.f, 1.f, 1.f));
+            }
+            key = root_key(pcg_hash(A.seed), id, S.user_sample);
+        } else if (SRC == PATH_CAMERA) {
+            cull = true;
             const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
             const uint32_t n_blocks = S.n_root >> 6;                           // items [b * n_blocks, (b + 1) * n_blocks): sample b of the batch
             const uint32_t blk = item % n_blocks, in_batch = item / n_blocks;
@@ -261,7 +280,7 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
             miss_bg = (info & kRayMissBackground) != 0u;
             ray = make_ray(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z));
         }
-        const Cand c = trace<MODE, STATS, kStage, SLICES>(A.tree, lds_nodes, ray, LEVEL0, valid, st, sx, S.auto_min_lanes);
+        const Cand c = trace<MODE, STATS, kStage, SLICES>(A.tree, lds_nodes, ray, cull, valid, st, sx, S.auto_min_lanes);
         nrays += valid ? 1u : 0u;
 
         // ---- color_hit's material switch (render.hpp:133-308): node kind + the rays it spawns
@@ -685,12 +704,12 @@ __global__ void k_reset_counters_if(unsigned long long *counters, StreamArgs S) 
 
 namespace {
 
-template <bool LEVEL0, int SLICES, int MODE>
+template <int SRC, int SLICES, int MODE>
 void launch_path(const dev::StreamArgs &S, bool stats, unsigned units, hipStream_t s) {
     const unsigned blocks = SLICES > 1 ? units : (units + 3) / 4, threads = SLICES > 1 ? 64u * SLICES : 256u;
     const size_t lds = MODE != RTK_TRACE_WAVE ? (size_t)S.r.tree.n_nodes * sizeof(DevNode) : 0;
-    if (stats) hipLaunchKernelGGL((dev::k_path<LEVEL0, true, SLICES, MODE>), dim3(blocks), dim3(threads), lds, s, S);
-    else hipLaunchKernelGGL((dev::k_path<LEVEL0, false, SLICES, MODE>), dim3(blocks), dim3(threads), lds, s, S);
+    if (stats) hipLaunchKernelGGL((dev::k_path<SRC, true, SLICES, MODE>), dim3(blocks), dim3(threads), lds, s, S);
+    else hipLaunchKernelGGL((dev::k_path<SRC, false, SLICES, MODE>), dim3(blocks), dim3(threads), lds, s, S);
 }
 template <int SLICES, int MODE>
 void launch_shadow(const dev::StreamArgs &S, bool stats, unsigned units, hipStream_t s) {
@@ -728,13 +747,15 @@ hipError_t launch_stream_sample(const dev::StreamArgs &base, bool stats, int dee
         S.hits_sorted = (level >= sort_from_level && level < A.max_depth) ? 1u : 0u;
         S.bin_children = (level + 1 >= sort_from_level && level < A.max_depth) ? 1u : 0u;
         S.bin_hits = S.hits_sorted;
-        if (level == 0 && slices == 1) launch_path<true, 1, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
-        else if (level == 0) launch_path<true, 4, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
-        else if (!deep && slices == 2) launch_path<false, 2, RTK_TRACE_WAVE>(S, stats, group_units * 2u, s);
-        else if (!deep && slices == 1) launch_path<false, 1, RTK_TRACE_WAVE>(S, stats, wave_units, s);
-        else if (!deep) launch_path<false, 4, RTK_TRACE_WAVE>(S, stats, group_units, s);
-        else if (deep_mode == RTK_TRACE_LANE) launch_path<false, 1, RTK_TRACE_LANE>(S, stats, wave_units, s);
-        else launch_path<false, 1, RTK_TRACE_AUTO>(S, stats, wave_units, s);
+        if (level == 0 && S.user_rays != nullptr && slices == 1) launch_path<dev::PATH_USER, 1, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
+        else if (level == 0 && S.user_rays != nullptr) launch_path<dev::PATH_USER, 4, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
+        else if (level == 0 && slices == 1) launch_path<dev::PATH_CAMERA, 1, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
+        else if (level == 0) launch_path<dev::PATH_CAMERA, 4, RTK_TRACE_WAVE>(S, stats, S.n_level0 / 64u, s);
+        else if (!deep && slices == 2) launch_path<dev::PATH_QUEUE, 2, RTK_TRACE_WAVE>(S, stats, group_units * 2u, s);
+        else if (!deep && slices == 1) launch_path<dev::PATH_QUEUE, 1, RTK_TRACE_WAVE>(S, stats, wave_units, s);
+        else if (!deep) launch_path<dev::PATH_QUEUE, 4, RTK_TRACE_WAVE>(S, stats, group_units, s);
+        else if (deep_mode == RTK_TRACE_LANE) launch_path<dev::PATH_QUEUE, 1, RTK_TRACE_LANE>(S, stats, wave_units, s);
+        else launch_path<dev::PATH_QUEUE, 1, RTK_TRACE_AUTO>(S, stats, wave_units, s);
         if (level < A.max_depth && A.n_lights > 0) {
             if (S.hits_sorted) {
                 hipLaunchKernelGGL(dev::k_sort_scan, dim3(1), dim3(256), 0, s, S.ws.hit_bins);

@@ -97,7 +97,17 @@ struct StreamArgs {
     uint32_t bin_hits;       // k_path: histogram the shading points it appends
     uint32_t key_dirs;       // ray_sort_key: 1 = spend six of the fifteen key bits on the direction (frames with diffuse rays)
     float grid_lo[3], grid_scale[3];   // cell = clamp((p - lo) * scale, 0, 15)
+    // Level 0 from the caller's rays (rtk_accel_radiance, k_path<PATH_USER>): one chunk of a batch.  Node i of level 0 is ray i
+    // of the chunk and writes colour i of r.out; n_level0 = user_n rounded up to whole 64-ray work units.
+    const rtk_ray *user_rays;          // [user_n], null for frames
+    const uint32_t *user_ids;          // [user_n] pixel index of the RNG root key, or null: user_id0 + i
+    uint32_t user_n, user_id0;
+    uint32_t user_sample;              // sample of the RNG root key (`sample` above is the accumulation's: always 0 of 1 here)
+    uint32_t user_cull;                // the <cull> of the chunk's own rays (wave-uniform)
 };
+
+// where k_path takes a level's rays from
+enum : int { PATH_QUEUE = 0, PATH_CAMERA = 1, PATH_USER = 2 };
 
 }  // namespace dev
 
@@ -112,6 +122,13 @@ struct StreamSide {
 // `slices`: waves per 64-ray work unit of the queue-driven levels (4: an owner and three helpers that share its large leaves; 2; 1: no helpers)
 hipError_t launch_stream_sample(const dev::StreamArgs &base, bool stats, int deep_level, int deep_mode, int sort_from_level,
                                 hipStream_t s, hipEvent_t wait_before_emit, hipEvent_t done, const StreamSide *side, int slices = 4);
+// rtk_accel_radiance (radiance.hip), behind a chunk's pipeline on the chunk's stream.  `lane_counters` is the kCounterWords
+// block the chunk's pipeline counted in (S.r.counters), `total` = {rays of the call, chunks redone}:
+// launch_radiance_fold adds the chunk's rays to total[0] if its queues held, else 1 to total[1];
+// launch_radiance_fallback does nothing unless the chunk's overflow word (S.ws.ctrl[kCtrlOverflow]) is set; then it evaluates
+// color_hit for every ray of the chunk, one ray per lane with an explicit stack, writes the colours and counts into total[0].
+hipError_t launch_radiance_fold(const dev::StreamArgs &S, unsigned long long *total, hipStream_t s);
+hipError_t launch_radiance_fallback(const dev::StreamArgs &S, unsigned long long *total, hipStream_t s);
 // ORs the lanes' overflow words into lane 0's, then zeroes the ray counters if it is set (the megakernel that redoes the frame counts from scratch)
 hipError_t launch_stream_overflow_reset(const dev::StreamArgs &S, hipStream_t s);
 

@@ -189,6 +189,23 @@ struct hip_accel {
         return out;
     }
 
+    // `intersect<cull>(rays[i])` followed by color_hit(accel, hit, 0), or the background colour on a miss (render/render.hpp:64-69,
+    // 133-308), for a batch: the colour every ray sees, out[i] for rays[i].  ids (empty, or one per ray): the pixel index of each
+    // ray's RNG root key (diffuse GI only; empty = the ray's index).  params: default_radiance_params()
+    [[nodiscard]] std::vector<color<F>> radiance_batch(const std::vector<ray3<F>> &rays, const rtk_radiance_params &params,
+                                                       const std::vector<std::uint32_t> &ids = {}, rtk_counters *counters = nullptr) const {
+        if (!ids.empty() && ids.size() != rays.size()) throw std::invalid_argument("hip_accel::radiance_batch: one id per ray");
+        std::vector<rtk_ray> in(rays.size());
+        for (std::size_t i = 0; i < rays.size(); ++i)
+            in[i] = rtk_ray{{rays[i].origin.x, rays[i].origin.y, rays[i].origin.z},
+                            {rays[i].direction.x, rays[i].direction.y, rays[i].direction.z}};
+        std::vector<float> rgb(rays.size() * 3);
+        check(rtk_accel_radiance(accel_.get(), in.data(), ids.empty() ? nullptr : ids.data(), in.size(), &params, rgb.data(), counters));
+        std::vector<color<F>> out(rays.size());
+        for (std::size_t i = 0; i < rays.size(); ++i) out[i] = color<F>{rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]};
+        return out;
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running
@@ -214,6 +231,15 @@ struct hip_accel {
         p.spp = 1; p.max_ray_depth = 5; p.diffuse_rays = 0; p.seed = 42; p.fov_degrees = 90.0;
         p.shadow_bias = 1e-4f; p.reflection_bias = 1e-4f; p.refraction_bias = 1e-4f;
         p.trace_mode = RTK_TRACE_AUTO; p.world_size = 1;
+        return p;
+    }
+
+    // the same defaults for a radiance batch; cull = 1: the batch's rays are traced as render_frame's camera rays are
+    [[nodiscard]] static rtk_radiance_params default_radiance_params() noexcept {
+        rtk_radiance_params p{};
+        p.max_ray_depth = 5; p.diffuse_rays = 0; p.seed = 42; p.sample = 0;
+        p.shadow_bias = 1e-4f; p.reflection_bias = 1e-4f; p.refraction_bias = 1e-4f;
+        p.cull = 1; p.trace_mode = RTK_TRACE_AUTO;
         return p;
     }
 

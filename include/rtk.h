@@ -338,6 +338,32 @@ int rtk_accel_radiance(rtk_accel *accel, const rtk_ray *rays, const uint32_t *id
 int rtk_accel_radiance_device(rtk_accel *accel, const rtk_ray *d_rays, const uint32_t *d_ids /* may be NULL */, size_t n,
                               const rtk_radiance_params *p, float *d_rgb /* device [n][3] */, void *hip_stream);
 
+/* ---- dynamic geometry: the accel after scene<F>'s vertex positions changed (what re-running the kd_tree_simd_accel ctor,
+ *      kd_tree_simd.hpp:100-185, on the moved scene would hold) ----
+ * `vertices` has the layout of rtk_scene_desc.vertices: all meshes concatenated, rtk_scene_info.n_vertices rows.  Topology, uvs,
+ * materials, textures, lights, camera and rtk_accel_params stay as they were at rtk_accel_build.
+ * After RTK_OK everything observable through the accel is, bit for bit, what rtk_accel_build gives for a scene that differs from
+ * the accel's only in `vertices` (same params, same environment knobs): rtk_accel_tree_info / _tree_dump, every rtk_accel_intersect*,
+ * rtk_accel_occluded* and rtk_accel_radiance* result, every frame through every RTK_TRACE_* engine and its counters' `rays`.
+ * RTK_TRAVERSAL_FAST accels included (their leaf orders and, with transmissive materials, the opaque-only occlusion tree are rebuilt).
+ * The tree is REBUILT, not refitted, and on the device: triangles, smooth vertex normals, boxes, the level-by-level split and the
+ * leaves' packets (csrc/build.hip); the host numbers the few hundred nodes.  The handle, its streams and its grown workspaces
+ * survive; the cost-feedback launch order and RTK_TRACE_AUTO's engine trial start over, as on a new accel.
+ * Ordering: the call SYNCHRONISES THE DEVICE AT ENTRY (nothing issued earlier, on any stream, can still be reading what it
+ * replaces), then works on `hip_stream` (the host variant: the null stream).  It blocks the host once more, to read back the node
+ * table and the flags; a further time only when a buffer has to grow (the first call on an accel, a tree larger than any before).  A build
+ * that outgrows its node or reference capacity is noticed on the device and repeated with more room; the flag tells what the level
+ * that did not fit needed, so a much deeper tree than any before can take several such repeats (at most 16), each a rebuild and a
+ * host block.  Capacities are kept, so the calls after it pay nothing.
+ * Work issued on the accel afterwards, on any stream, sees the new geometry: it waits on the device for an event recorded
+ * behind the update's last kernel.  NOT stream-capturable.
+ * Errors, in this order: NULL accel or pointer -> RTK_ERR_INVALID; no usable device -> RTK_ERR_NO_DEVICE (there is no CPU path; an
+ * accel that has not been on the device yet goes there first); a non-finite coordinate -> RTK_ERR_INVALID (the host variant looks
+ * before it touches the device, the device variant learns it from a flag its first kernel raises).  After any error the accel is
+ * exactly as before the call and stays usable: the new geometry is built into buffers of its own and swapped in at the end. */
+int rtk_accel_update_vertices(rtk_accel *accel, const float *vertices /* host [n_vertices][3] */);
+int rtk_accel_update_vertices_device(rtk_accel *accel, const float *d_vertices /* device [n_vertices][3] */, void *hip_stream);
+
 /* ---- frame: replaces render_frame<A,F> (render/render.hpp:18-108) with color_hit/is_occluded device-side ---- */
 /* number of floats the (rank-local) output of rtk_render_frame_device holds */
 int rtk_render_output_floats(const rtk_accel *accel, const rtk_render_params *p, size_t *n_floats);

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "rtk_accel_intersect", "rtk_accel_intersect_device", "rtk_accel_intersect_stats",
     "rtk_accel_occluded", "rtk_accel_occluded_device",
     "rtk_accel_radiance", "rtk_accel_radiance_device",
+    "rtk_accel_update_vertices", "rtk_accel_update_vertices_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
@@ -157,6 +158,8 @@ _L.rtk_accel_occluded.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int,
 _L.rtk_accel_occluded_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, _vp, _vp]
 _L.rtk_accel_radiance.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceParams), _vp, C.POINTER(Counters)]
 _L.rtk_accel_radiance_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceParams), _vp, _vp]
+_L.rtk_accel_update_vertices.argtypes = [_vp, _vp]
+_L.rtk_accel_update_vertices_device.argtypes = [_vp, _vp, _vp]
 _L.rtk_render_output_floats.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]
 _L.rtk_render_frame.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.POINTER(Counters)]
 _L.rtk_render_frame_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp]
@@ -442,6 +445,23 @@ class KdTreeSimdAccel:
         """Device buffers (d_ids_ptr 0 = no ids), stream-ordered; not capturable into a graph (rtk.h)."""
         p = (cfg or RadianceConfig()).to_c()
         _check(_L.rtk_accel_radiance_device(self._h, d_rays_ptr, d_ids_ptr or None, n, C.byref(p), d_rgb_ptr or None, stream))
+
+    # ---- dynamic geometry: the accel of the same scene with its vertices moved (rtk.h, csrc/build.hip)
+    def update_vertices(self, vertices: np.ndarray) -> None:
+        """vertices: [n_vertices, 3] float32 in host memory, all meshes concatenated as in SceneDesc.  The tree is rebuilt on the
+        device; afterwards the accel is bit for bit the one a new build of the moved scene would give."""
+        vertices = np.asarray(vertices)
+        n = self.scene.info.n_vertices
+        if vertices.dtype != np.float32:
+            raise ValueError("vertices must be float32")
+        if vertices.shape != (n, 3):
+            raise ValueError(f"vertices must have shape ({n}, 3)")
+        vertices = np.ascontiguousarray(vertices)
+        _check(_L.rtk_accel_update_vertices(self._h, vertices.ctypes.data))
+
+    def update_vertices_device(self, d_vertices_ptr: int, stream: int = 0) -> None:
+        """d_vertices_ptr: device float32 [n_vertices, 3]; stream-ordered on `stream`, blocks the host once; not capturable (rtk.h)."""
+        _check(_L.rtk_accel_update_vertices_device(self._h, d_vertices_ptr or None, stream))
 
     # ---- frames
     def output_floats(self, cfg: RenderConfig) -> int:

@@ -1,10 +1,11 @@
 // Host kd-tree build (kd_tree_simd.hpp:100-185) and flattening into the device layout.
-// Serial and cheap (thousands of triangles, depth <= max_depth); stays on the host as in the reference.
+// Serial and cheap (thousands of triangles, depth <= max_depth): rtk_accel_build does it on the host as in the reference.
+// rtk_accel_update_vertices rebuilds on the device (build.hip); of that tree only the numbering of the nodes is done here.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
-#include "rtk_internal.hpp"
+#include "build_nodes.hpp"
 
 namespace rtk {
 
@@ -154,6 +155,75 @@ void build_fast_leaf_orders(HostTree &t) {
     t.dev_leaves_fast.clear();
     t.dev_leaves_fast.reserve(t.dev_leaves.size() * 8);
     for (unsigned oct = 0; oct < 8u; ++oct) leaves_front_to_back(t, 0, oct, t.dev_leaves_fast, leaf_slot);
+}
+
+namespace {
+
+// Reference numbering of a device-built tree: Builder::build creates child0 and its whole subtree before child1, so a node's
+// number is its position in that pre-order walk, and leaf_refs is the leaves' lists in the same order.
+void number_reference_order(const dev::BuildNode *bn, int32_t b, int depth, HostTree &t, std::vector<int32_t> &build_id) {
+    const dev::BuildNode &s = bn[b];
+    const size_t at = t.nodes.size();
+    HostNode n;
+    n.box.mn = {s.lo[0], s.lo[1], s.lo[2]};
+    n.box.mx = {s.hi[0], s.hi[1], s.hi[2]};
+    n.depth = depth;
+    if (depth > t.depth) t.depth = depth;
+    t.nodes.push_back(n);
+    build_id.push_back(b);
+    if (s.axis == dev::kBuildLeaf) {
+        // (leaf_start: the caller, once every leaf's size is known in this order)
+        t.nodes[at].leaf_start = 0;
+        t.nodes[at].leaf_count = int32_t(s.count);
+        return;
+    }
+    if (s.child0 >= 0) { t.nodes[at].child0 = int32_t(t.nodes.size()); number_reference_order(bn, s.child0, depth + 1, t, build_id); }
+    if (s.child1 >= 0) { t.nodes[at].child1 = int32_t(t.nodes.size()); number_reference_order(bn, s.child1, depth + 1, t, build_id); }
+}
+
+// flatten() for a tree whose triangles stay on the device: the nodes and skip links, and one copy job per leaf.
+void flatten_jobs(HostTree &t, int32_t node, const dev::BuildNode *bn, const std::vector<int32_t> &build_id, uint32_t &n_refs,
+                  std::vector<dev::GatherLeaf> &gather) {
+    const HostNode &hn = t.nodes[size_t(node)];
+    const size_t at = t.dev_nodes.size();
+    DevNode dn;
+    dn.lo[0] = hn.box.mn.x; dn.lo[1] = hn.box.mn.y; dn.lo[2] = hn.box.mn.z;
+    dn.hi[0] = hn.box.mx.x; dn.hi[1] = hn.box.mx.y; dn.hi[2] = hn.box.mx.z;
+    dn.a = 0; dn.b = DEV_INNER;
+    t.dev_nodes.push_back(dn);
+    if (hn.leaf_start >= 0) {
+        const dev::BuildNode &s = bn[build_id[size_t(node)]];
+        t.dev_nodes[at].a = n_refs;
+        t.dev_nodes[at].b = uint32_t(hn.leaf_count);
+        dev::GatherLeaf g{};
+        g.src = s.start; g.count = s.count; g.dst = n_refs; g.dst_ref = uint32_t(hn.leaf_start);
+        g.pad[0] = s.c0;                                                 // opaque triangles of the leaf (api.hip places dst_occl)
+        gather.push_back(g);
+        n_refs += s.count;
+        t.dev_leaves.push_back(t.dev_nodes[at]);
+        return;
+    }
+    if (hn.child1 >= 0) flatten_jobs(t, hn.child1, bn, build_id, n_refs, gather);
+    if (hn.child0 >= 0) flatten_jobs(t, hn.child0, bn, build_id, n_refs, gather);
+    t.dev_nodes[at].a = uint32_t(t.dev_nodes.size());
+}
+
+}  // namespace
+
+void tree_from_build_nodes(const dev::BuildNode *bn, HostTree &out, std::vector<dev::GatherLeaf> &gather) {
+    out.nodes.clear(); out.dev_nodes.clear(); out.dev_leaves.clear(); out.dev_leaves_fast.clear();
+    out.depth = 0;
+    gather.clear();
+    std::vector<int32_t> build_id;
+    number_reference_order(bn, 0, 0, out, build_id);
+    int32_t at = 0;
+    for (HostNode &n : out.nodes) {
+        if (n.leaf_start < 0) continue;
+        n.leaf_start = at;
+        at += n.leaf_count;
+    }
+    uint32_t n_refs = 0;
+    flatten_jobs(out, 0, bn, build_id, n_refs, gather);
 }
 
 int build_tree(const rtk_scene &scene, int max_depth, int max_leaf, HostTree &out, std::string &err) {

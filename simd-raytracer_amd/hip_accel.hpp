@@ -206,6 +206,37 @@ struct hip_accel {
         return out;
     }
 
+    // The accel after the scene's vertex positions changed: what constructing a new accel from the moved scene would hold, rebuilt
+    // on the device (rtk_accel_update_vertices).  `vertices`: all meshes concatenated in mesh order, as many as the scene has.
+    // CAUTION: this overload moves the ACCEL ONLY.  *scene_ptr stays the old scene, and intersect / intersect_batch fill
+    // hit.face_normal and hit.uvs from it (to_hit): distances, u, v, hit_normal and mesh_idx are the moved scene's, face_normal is
+    // the OLD triangle's.  It is meant for callers that use render_frame / radiance_batch / occluded_batch or never read
+    // face_normal; everyone else moves a copy of the scene and calls update_vertices(moved_scene) below, which swaps scene_ptr.
+    void update_vertices(const std::vector<vec3<F>> &vertices) {
+        std::size_t n = 0;
+        for (const auto &mesh : scene_ptr->meshes) n += mesh.vertices.size();
+        if (vertices.size() != n) throw std::invalid_argument("hip_accel::update_vertices: one position per vertex of the scene");
+        std::vector<float> flat;
+        flat.reserve(n * 3 + 3);
+        for (const auto &v : vertices) { flat.push_back(v.x); flat.push_back(v.y); flat.push_back(v.z); }
+        if (flat.empty()) flat.push_back(0.f);            // (an empty scene still hands over a pointer)
+        check(rtk_accel_update_vertices(accel_.get(), flat.data()));
+    }
+
+    // The same from a moved copy of the scene (same meshes, same triangles, other vertex positions); scene_ptr then points to it.
+    void update_vertices(std::shared_ptr<const scene<F>> moved) {
+        if (!moved || moved->meshes.size() != scene_ptr->meshes.size()) throw std::invalid_argument("hip_accel::update_vertices: another topology");
+        std::vector<vec3<F>> vertices;
+        for (std::size_t m = 0; m < moved->meshes.size(); ++m) {
+            if (moved->meshes[m].vertices.size() != scene_ptr->meshes[m].vertices.size() ||
+                moved->meshes[m].triangles.size() != scene_ptr->meshes[m].triangles.size())
+                throw std::invalid_argument("hip_accel::update_vertices: another topology");
+            vertices.insert(vertices.end(), moved->meshes[m].vertices.begin(), moved->meshes[m].vertices.end());
+        }
+        update_vertices(vertices);
+        scene_ptr = std::move(moved);
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running

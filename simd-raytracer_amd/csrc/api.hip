@@ -1,259 +1,19 @@
 // C-ABI of the rtk engine (include/rtk.h).  Owns device buffers, validates operands against what the
 // kernels and their grids assume, and never lets an exception cross the boundary.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
 
-#include "kernels.hpp"
-#include "stream.hpp"
-#include "repack.hpp"
-#include "occluded.hpp"
-#include "build.hpp"
+#include "accel.hpp"
 
 namespace rtk {
 
 static thread_local std::string g_last_error;
 void set_error(const std::string &msg) { g_last_error = msg; }
 
-namespace {
-
-int fail(int code, const std::string &msg) { set_error(msg); return code; }
-
-int hip_fail(hipError_t e, const char *what) {
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return RTK_ERR_HIP;
-}
-
-#define RTK_HIP(call)                                        \
-    do {                                                     \
-        const hipError_t e_ = (call);                        \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);    \
-    } while (0)
-
-template <typename T>
-int upload(const std::vector<T> &src, T **dst) {
-    *dst = nullptr;
-    const size_t bytes = (src.empty() ? 1 : src.size()) * sizeof(T);
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(dst), bytes));
-    if (!src.empty()) RTK_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return RTK_OK;
-}
-
-}  // namespace
-}  // namespace rtk
-
-// Environment knobs (all optional).  Read ONCE, when an accel is built: nothing on the launch path
-// calls getenv.
-struct rtk_knobs {
-    uint32_t slice_min_tris = rtk::kSliceMinTrisDefault;   // RTK_SLICE_MIN_TRIS
-    bool shadow_exit = true;                                // RTK_SHADOW_EARLY_EXIT
-    bool skip_unlit_shadow = true;                          // RTK_SKIP_UNLIT_SHADOW: occlusion queries that cannot change the pixel are not traced
-    bool bundle_cull = true;                                // RTK_BUNDLE_CULL
-    bool auto_trials = true;                                // RTK_AUTO_TRIALS
-    bool cost_feedback = true;                              // RTK_COST_FEEDBACK
-    unsigned resort_every = 16;                             // RTK_COST_RESORT_EVERY
-    uint32_t light_cycles = 140000u;                        // RTK_LIGHT_BELOW_CYCLES
-    uint32_t order_floor_cycles = 20000u;                   // RTK_ORDER_FLOOR_CYCLES
-    bool batch_scalar_surv = false;                         // RTK_BATCH_SCALAR_SURV: the same in the batched intersect
-    bool stream_scalar_surv = true;                         // RTK_STREAM_SCALAR_SURV: survivors through the scalar cache in the streaming kernels
-    bool repack = true;                                     // RTK_REPACK: RTK_TRACE_AUTO may sort large incoherent ray batches
-    bool raster_tiles = true;                               // RTK_RASTER_TILES: coherent batches that are rows of camera rays go to the waves as 8x8 blocks
-    int repack_skip_bits = 6;                               // RTK_REPACK_SKIP_BITS: low key bits left unsorted when <= 3 dimensions vary (0..14)
-    bool repack_full_bounds = false;                        // RTK_REPACK_FULL_BOUNDS: key cells from the bounds of all rays, not of a sample
-    int repack_skip_bits2 = 14;                             // RTK_REPACK_SKIP_BITS2: the same when <= 2 dimensions vary (0..22)
-    bool repack_dirs3 = false;                              // RTK_REPACK_DIRS3: directions enter the sort keys as three components even when all rays share an origin
-    int repack_trace = -1;                                  // RTK_REPACK_TRACE: strategy for a sorted batch (0 auto, 1 lane, 2 wave; default: by the probe)
-    size_t group8_below = 9000;                             // RTK_GROUP8_BELOW_BLOCKS
-    int stream_node_factor = 0;                             // RTK_STREAM_NODE_FACTOR (0 = default)
-    int stream_deep_level = 99, stream_deep_mode = RTK_TRACE_AUTO;   // RTK_STREAM_DEEP_LEVEL / _MODE
-    uint32_t auto_min_lanes = 12;                           // RTK_AUTO_MIN_LANES
-    int stream_sort_from = -1;                              // RTK_STREAM_SORT_FROM (-1 = default)
-    bool stream_debug = false;                              // RTK_STREAM_DEBUG
-    bool stream_side = true;                                // RTK_STREAM_SIDE: k_shadow on side streams
-    int stream_lanes = 4;                                   // RTK_STREAM_LANES: batches of a frame in flight at once (1..kStreamLanes); 8 measured no faster
-    int stream_slices = 0;                                  // RTK_STREAM_SLICES: waves per work unit of the streaming levels (1, 2, 4; 0 = by the tree's leaf sizes)
-    int stream_batch = 0;                                   // RTK_STREAM_BATCH: samples traced together per launch (stream.hpp; 0 = the pass split evenly over the lanes)
-    int stream_mem_gb = 96;                                 // RTK_STREAM_MEM_GB: budget for the queues of all batches in flight
-    int stream_side_below = 2;                              // RTK_STREAM_SIDE_BELOW: k_shadow on side streams while at most this many samples are in flight
-    bool first_frame_prior = true;                          // RTK_FIRST_FRAME_PRIOR: launch order of a shape's first frame from k_block_prior
-    bool fast_occluders = true;                             // RTK_FAST_OCCLUDERS: RTK_TRAVERSAL_FAST answers occlusion through transmissive surfaces from the opaque triangles alone
-    bool traversal_fast = false;                            // RTK_TRAVERSAL_FAST: front-to-back leaf order (rtk.h; NOT the parity mode)
-
-    static rtk_knobs from_env() {
-        rtk_knobs k;
-        auto geti = [](const char *name, long &out) { const char *e = std::getenv(name); if (!e || !*e) return false; out = std::atol(e); return true; };
-        long v;
-        if (geti("RTK_SLICE_MIN_TRIS", v) && v > 0) k.slice_min_tris = uint32_t(v);
-        if (geti("RTK_SHADOW_EARLY_EXIT", v)) k.shadow_exit = v != 0;
-        if (geti("RTK_SKIP_UNLIT_SHADOW", v)) k.skip_unlit_shadow = v != 0;
-        if (geti("RTK_BUNDLE_CULL", v)) k.bundle_cull = v != 0;
-        if (geti("RTK_AUTO_TRIALS", v)) k.auto_trials = v != 0;
-        if (geti("RTK_COST_FEEDBACK", v)) k.cost_feedback = v != 0;
-        if (geti("RTK_COST_RESORT_EVERY", v) && v > 0) k.resort_every = unsigned(v);
-        if (geti("RTK_LIGHT_BELOW_CYCLES", v) && v >= 0) k.light_cycles = uint32_t(v);
-        if (geti("RTK_ORDER_FLOOR_CYCLES", v) && v >= 0) k.order_floor_cycles = uint32_t(v);
-        if (geti("RTK_REPACK", v)) k.repack = v != 0;
-        if (geti("RTK_RASTER_TILES", v)) k.raster_tiles = v != 0;
-        if (geti("RTK_REPACK_FULL_BOUNDS", v)) k.repack_full_bounds = v != 0;
-        if (geti("RTK_REPACK_SKIP_BITS2", v) && v >= 0 && v <= 22) k.repack_skip_bits2 = int(v);
-        if (geti("RTK_REPACK_DIRS3", v)) k.repack_dirs3 = v != 0;
-        if (geti("RTK_REPACK_SKIP_BITS", v) && v >= 0 && v <= 14) k.repack_skip_bits = int(v);
-        if (geti("RTK_STREAM_SCALAR_SURV", v)) k.stream_scalar_surv = v != 0;
-        if (geti("RTK_BATCH_SCALAR_SURV", v)) k.batch_scalar_surv = v != 0;
-        if (geti("RTK_REPACK_TRACE", v) && (v == RTK_TRACE_AUTO || v == RTK_TRACE_WAVE || v == RTK_TRACE_LANE)) k.repack_trace = int(v);
-        if (geti("RTK_GROUP8_BELOW_BLOCKS", v) && v >= 0) k.group8_below = size_t(v);
-        if (geti("RTK_STREAM_NODE_FACTOR", v) && v >= 1) k.stream_node_factor = int(v);
-        if (geti("RTK_STREAM_DEEP_LEVEL", v)) k.stream_deep_level = int(v);
-        if (geti("RTK_STREAM_DEEP_MODE", v)) k.stream_deep_mode = int(v);
-        if (geti("RTK_AUTO_MIN_LANES", v) && v > 0 && v <= 64) k.auto_min_lanes = uint32_t(v);
-        if (geti("RTK_STREAM_SORT_FROM", v)) k.stream_sort_from = int(v);
-        if (geti("RTK_STREAM_DEBUG", v)) k.stream_debug = v != 0;
-        if (geti("RTK_STREAM_SIDE", v)) k.stream_side = v != 0;
-        if (geti("RTK_TRAVERSAL_FAST", v)) k.traversal_fast = v != 0;
-        if (geti("RTK_FIRST_FRAME_PRIOR", v)) k.first_frame_prior = v != 0;
-        if (geti("RTK_STREAM_SLICES", v) && (v == 0 || v == 1 || v == 2 || v == 4)) k.stream_slices = int(v);
-        if (geti("RTK_STREAM_BATCH", v) && v >= 0 && v <= 4096) k.stream_batch = int(v);
-        if (geti("RTK_STREAM_MEM_GB", v) && v >= 1 && v <= 256) k.stream_mem_gb = int(v);
-        if (geti("RTK_FAST_OCCLUDERS", v)) k.fast_occluders = v != 0;
-        if (geti("RTK_STREAM_SIDE_BELOW", v) && v >= 0) k.stream_side_below = int(v);
-        if (geti("RTK_STREAM_LANES", v) && v >= 1 && v <= rtk::dev::kStreamLanes) k.stream_lanes = int(v);
-        return k;
-    }
-};
-
-namespace rtk {
-enum { G_NODES, G_LEAVES, G_FAST, G_TRIS, G_IDS, G_SHADE, G_LREFS, G_ONODES, G_OLEAVES, G_OTRIS, G_OIDS, kGeomBufs };
-}
-
-struct rtk_accel {
-    rtk_knobs knobs;
-    bool coords_small = false;        // every leaf-reference coordinate is below kBundleLimit: bundle culling cannot overflow
-    rtk_scene scene;                  // private copy: the caller may free its scene (kd_tree_simd.hpp:106-107 copies too)
-    rtk::HostTree tree;
-    rtk_accel_params params;
-    bool has_refractive = false;
-    // device residency (lazy: built on first compute call so host-only use needs no GPU)
-    bool on_device = false;
-    int device = -1;
-    rtk::DevNode *d_nodes = nullptr;
-    rtk::DevNode *d_leaves = nullptr;
-    // RTK_TRAVERSAL_FAST on a scene with transmissive materials: the tree again with the opaque triangles only (occlusion queries, k_shadow)
-    rtk::DevNode *d_occl_nodes = nullptr, *d_occl_leaves = nullptr;
-    rtk::DevTri *d_occl_tris = nullptr;
-    uint32_t *d_occl_ids = nullptr;
-    uint32_t occl_n_leaves = 0;
-    bool occl_on = false;
-    rtk::DevNode *d_leaves_fast = nullptr;    // RTK_TRAVERSAL_FAST: 8 front-to-back orders of the leaves (null in the parity mode)
-    bool fast_traversal = false;
-    // Streaming pipeline: waves per 64-ray work unit.  Helper waves pay where a ray meets large leaves (hw11/scene8, a
-    // triangle reference sits in a leaf of 258 on average: 23.3 ms with three helpers, 36.6 without) and cost where it does not
-    // (hw15/scene2, 109: 64.1 ms with, 47.8 without -- the helpers' wave slots are worth more as owners of further units).
-    int stream_slices_auto = 4;
-    rtk::DevTri *d_tris = nullptr;
-    uint32_t *d_tri_ids = nullptr;
-    rtk::DevShade *d_shade = nullptr;
-    rtk::DevMaterial *d_materials = nullptr;
-    rtk::DevLight *d_lights = nullptr;
-    rtk::DevTexture *d_textures = nullptr;
-    rtk::DevTriUv *d_tri_uv = nullptr;
-    uint8_t *d_tex_pixels = nullptr;
-    unsigned long long *d_counters = nullptr;     // 8 x u64 in rtk_counters order + kRayCounterShards ray-count shards
-    // streaming-pipeline workspace (grown on demand)
-    // one per sample lane (stream.hpp kStreamLanes); `ws` = lane 0; all lanes share lane 0's sumbuf
-    rtk::dev::StreamWs ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};
-    rtk::dev::StreamWs ws_lane[rtk::dev::kStreamLanes] = {};
-    int ws_lanes = 0;
-    hipStream_t lane_stream[rtk::dev::kStreamLanes] = {};
-    hipEvent_t lane_done[rtk::dev::kStreamLanes] = {};
-    hipEvent_t lane_fork = nullptr;
-    rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane
-    size_t ws_pixels = 0, ws_lights = 0, ws_nodes = 0;
-    bool ws_sum = false;
-    // two-pass workspace
-    float4 *tp_prim = nullptr;
-    uint32_t *tp_bins = nullptr;       // [kCostBins] counts, [1] n_listed
-    uint32_t *tp_bin_list = nullptr, *tp_order = nullptr;
-    size_t tp_pixels = 0, tp_tiles = 0;
-    // cost feedback (megakernel frames): per-pixel-block cost of the last frame of shape fb_sig, and the order made from it
-    uint32_t *fb_cost = nullptr, *fb_order = nullptr;
-    uint8_t *fb_bins = nullptr;
-    size_t fb_units = 0;
-    uint64_t fb_sig[4] = {0, 0, 0, 0};
-    // RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (render_device_impl)
-    hipEvent_t trial_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t trial_sig[3] = {0, 0, 0};
-    int trial_state = 0;
-    // number of workgroups in fb_order's workgroup list, read back behind the sort that made it (pinned host word + event)
-    uint32_t *fb_nwgs_host = nullptr;
-    hipEvent_t fb_nwgs_ev = nullptr;
-    bool fb_nwgs_pending = false, fb_nwgs_known = false;
-    bool fb_valid = false;           // fb_cost holds the costs of a frame of shape fb_sig
-    bool fb_order_valid = false;     // fb_order was made from such costs
-    // ray repacking workspace (batched intersect, repack.hip)
-    uint32_t *rp_bounds = nullptr, *rp_keys = nullptr, *rp_idx = nullptr;
-    void *rp_temp = nullptr;
-    uint32_t *rp_host = nullptr;     // pinned: the probe's words as the host sees them
-    hipEvent_t rp_probe_ev = nullptr;
-    hipEvent_t rp_done = nullptr;    // recorded behind the k_intersect that walks rp_idx: the next repack on any stream waits for it
-    bool rp_in_use = false;
-    size_t rp_temp_bytes = 0, rp_cap = 0;
-    unsigned fb_age = 0;             // frames rendered with the current order
-    // staging of the host variant of the occlusion batch (rtk_accel_occluded): grows, never shrinks
-    rtk_ray *oc_rays = nullptr;
-    float *oc_max_t = nullptr;
-    uint8_t *oc_out = nullptr;
-    size_t oc_cap = 0;
-    // batched radiance (rtk_accel_radiance): one kCounterWords block per lane for a chunk's pipeline, then {rays, chunks redone} of the call
-    unsigned long long *d_rad_counters = nullptr;
-    // the streaming workspace's last user (a STREAM frame or a radiance batch) recorded ws_done: a radiance batch on any stream waits for it
-    hipEvent_t ws_done = nullptr;
-    bool ws_in_use = false;
-    // staging of the host variant of the radiance batch: grows, never shrinks
-    rtk_ray *rad_rays = nullptr;
-    uint32_t *rad_ids = nullptr;
-    float *rad_rgb = nullptr;
-    size_t rad_cap = 0;
-    // rtk_accel_update_vertices (build.hip).  The geometry buffers exist twice: an update builds into the spare set and swaps it
-    // with the active one (d_nodes ... d_occl_ids, d_leaf_refs) at the end, so a failed update leaves the accel as it was and a
-    // steady animation allocates nothing.  Capacities in bytes; buffers grow, never shrink.
-    void *spare[rtk::kGeomBufs] = {};
-    size_t spare_cap[rtk::kGeomBufs] = {}, active_cap[rtk::kGeomBufs] = {};
-    int32_t *d_leaf_refs = nullptr;            // leaf_refs in reference order, written by the device build
-    bool refs_on_device = false;               // tree.leaf_refs (and every per-triangle host array) lives on the device only
-    int32_t n_leaf_refs_dev = 0;
-    bool up_static = false;                    // the tables of the constant topology below are made
-    uint32_t *up_index = nullptr, *up_inc_off = nullptr, *up_inc = nullptr;
-    uint8_t *up_opaque = nullptr;
-    float *up_verts = nullptr;                 // staging of the host variant
-    rtk::DevTri *up_tris = nullptr;            // per triangle
-    float *up_tbox = nullptr;
-    uint32_t *up_ref_id = nullptr, *up_ref_node = nullptr;
-    size_t up_cap_refs = 0, up_cap_nodes = 0;
-    uint8_t *up_table = nullptr, *up_table_host = nullptr;     // BuildHdr + BuildNode[up_cap_nodes]; the host copy is pinned
-    rtk::dev::GatherLeaf *up_gather = nullptr;
-    size_t up_gather_cap = 0;
-    uint8_t *up_stage = nullptr;               // pinned: the small tables on their way up
-    size_t up_stage_cap = 0;
-    hipEvent_t geom_ready = nullptr;           // recorded behind an update's last kernel: later work on any stream waits for it
-    bool geom_pending = false;
-    hipStream_t last_stream = nullptr;
-    uint64_t last_primary = 0;
-    bool last_stats = false;
-    std::mutex mu;
-};
-
-namespace rtk {
-namespace {
-
-// `s`: the stream the caller is about to issue work on.  It waits for the geometry of the last rtk_accel_update_vertices
-// (which was built on that call's stream) unless that has completed already.
-int ensure_device(rtk_accel *a, hipStream_t s = nullptr) {
+int ensure_device(rtk_accel *a, hipStream_t s) {
     if (a->on_device) {
         RTK_HIP(hipSetDevice(a->device));
         if (a->geom_pending) {
@@ -271,13 +31,12 @@ int ensure_device(rtk_accel *a, hipStream_t s = nullptr) {
     if (dev >= count) return fail(RTK_ERR_INVALID, "device ordinal out of range");
     RTK_HIP(hipSetDevice(dev));
     a->device = dev;
-    int rc;
-    if ((rc = upload(a->tree.dev_nodes, &a->d_nodes)) != RTK_OK) return rc;
-    if ((rc = upload(a->tree.dev_leaves, &a->d_leaves)) != RTK_OK) return rc;
-    if (a->fast_traversal && (rc = upload(a->tree.dev_leaves_fast, &a->d_leaves_fast)) != RTK_OK) return rc;
-    if ((rc = upload(a->tree.dev_tris, &a->d_tris)) != RTK_OK) return rc;
-    if ((rc = upload(a->tree.dev_tri_ids, &a->d_tri_ids)) != RTK_OK) return rc;
-    if ((rc = upload(a->tree.dev_shade, &a->d_shade)) != RTK_OK) return rc;
+    RTK_TRY(upload(a->tree.dev_nodes, &a->d_nodes));
+    RTK_TRY(upload(a->tree.dev_leaves, &a->d_leaves));
+    if (a->fast_traversal) RTK_TRY(upload(a->tree.dev_leaves_fast, &a->d_leaves_fast));
+    RTK_TRY(upload(a->tree.dev_tris, &a->d_tris));
+    RTK_TRY(upload(a->tree.dev_tri_ids, &a->d_tri_ids));
+    RTK_TRY(upload(a->tree.dev_shade, &a->d_shade));
     if (a->fast_traversal && a->has_refractive && a->knobs.fast_occluders) {
         // occlusion through transmissive surfaces as ONE query against what is not transmissive (rtk.h, RTK_TRAVERSAL_FAST): the same
         // nodes, their leaves without the transmissive triangles; leaves left empty drop out of the leaf list
@@ -298,19 +57,19 @@ int ensure_device(rtk_accel *a, hipStream_t s = nullptr) {
         }
         if (tris.empty()) { tris.push_back(t.dev_tris.empty() ? DevTri{} : t.dev_tris[0]); ids.push_back(0u); }      // (nothing opaque: keep the pointers valid)
         if (leaves.empty()) { DevNode n = nodes.empty() ? DevNode{} : nodes[0]; n.a = 0u; n.b = 0u; leaves.push_back(n); }
-        if ((rc = upload(nodes, &a->d_occl_nodes)) != RTK_OK) return rc;
-        if ((rc = upload(leaves, &a->d_occl_leaves)) != RTK_OK) return rc;
-        if ((rc = upload(tris, &a->d_occl_tris)) != RTK_OK) return rc;
-        if ((rc = upload(ids, &a->d_occl_ids)) != RTK_OK) return rc;
+        RTK_TRY(upload(nodes, &a->d_occl_nodes));
+        RTK_TRY(upload(leaves, &a->d_occl_leaves));
+        RTK_TRY(upload(tris, &a->d_occl_tris));
+        RTK_TRY(upload(ids, &a->d_occl_ids));
         a->occl_n_leaves = uint32_t(leaves.size());
         a->occl_on = true;
     }
-    if ((rc = upload(a->scene.materials, &a->d_materials)) != RTK_OK) return rc;
-    if ((rc = upload(a->scene.lights, &a->d_lights)) != RTK_OK) return rc;
+    RTK_TRY(upload(a->scene.materials, &a->d_materials));
+    RTK_TRY(upload(a->scene.lights, &a->d_lights));
     if (!a->scene.textures.empty()) {
-        if ((rc = upload(a->scene.textures, &a->d_textures)) != RTK_OK) return rc;
-        if ((rc = upload(a->tree.dev_tri_uv, &a->d_tri_uv)) != RTK_OK) return rc;
-        if (!a->scene.tex_pixels.empty() && (rc = upload(a->scene.tex_pixels, &a->d_tex_pixels)) != RTK_OK) return rc;
+        RTK_TRY(upload(a->scene.textures, &a->d_textures));
+        RTK_TRY(upload(a->tree.dev_tri_uv, &a->d_tri_uv));
+        if (!a->scene.tex_pixels.empty()) RTK_TRY(upload(a->scene.tex_pixels, &a->d_tex_pixels));
     }
     // (+ 4 words behind the counters: the six cursors of the first-frame prior, zeroed by the same fill as the counters)
     RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_counters), (kCounterWords + 4) * sizeof(unsigned long long)));
@@ -332,153 +91,6 @@ dev::TreeView tree_view(const rtk_accel *a) {
     return t;
 }
 
-// (Re)allocates the streaming workspace for `pixels` output pixels.  Allocation synchronises the device, so it only
-// happens when a larger frame (or more lights / multi-sample) is requested than ever before on this accel.
-// The streams the streaming pipeline's lanes (and their k_shadow side kernels) run on belong to the PROCESS and are made once
-// per device, in the order the first accel needs them.  HIP deals a process's streams to a handful of hardware queues; lanes
-// that land on one queue take turns instead of overlapping, and which queue a stream gets depends on how many were made before
-// it.  With streams made (and destroyed) per accel, the second accel of a process ran the same kernels on the same rays up to
-// 60 % slower (hw11/scene8 23 -> 37 ms, hw15/scene2 47 -> 58 ms per pass; GPU_MAX_HW_QUEUES=2: 72 ms): its lanes shared queues.
-struct LaneStreams {
-    hipStream_t lane[rtk::dev::kStreamLanes] = {};
-    hipStream_t side[rtk::dev::kStreamLanes][2] = {};
-};
-std::mutex g_lane_mu;
-LaneStreams g_lane_streams[16];
-
-hipError_t lane_streams_for(int device, int lanes, LaneStreams **out) {
-    if (device < 0 || device >= 16) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lock(g_lane_mu);
-    LaneStreams &L = g_lane_streams[device];
-    for (int j = 0; j < lanes && j < rtk::dev::kStreamLanes; ++j) {
-        hipError_t e = hipSuccess;
-        if (j > 0 && !L.lane[j]) e = hipStreamCreateWithFlags(&L.lane[j], hipStreamNonBlocking);
-        for (int par = 0; par < 2 && e == hipSuccess; ++par)
-            if (!L.side[j][par]) e = hipStreamCreateWithFlags(&L.side[j][par], hipStreamNonBlocking);
-        if (e != hipSuccess) return e;
-    }
-    *out = &L;
-    return hipSuccess;
-}
-
-void free_stream_ws(rtk_accel *a) {
-    (void)hipFree(a->ws.sumbuf);
-    for (int j = 0; j < dev::kStreamLanes; ++j) {
-        dev::StreamWs &w = a->ws_lane[j];
-        (void)hipFree(w.rays); (void)hipFree(w.nodes); (void)hipFree(w.hits); (void)hipFree(w.contrib); (void)hipFree(w.ctrl);
-        (void)hipFree(w.node_bins); (void)hipFree(w.hit_bins); (void)hipFree(w.node_order); (void)hipFree(w.hit_order);
-        w = dev::StreamWs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};
-    }
-    a->ws = a->ws_lane[0];
-    a->ws_lanes = 0; a->ws_pixels = 0; a->ws_nodes = 0; a->ws_lights = 0; a->ws_sum = false;
-}
-
-int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes) {
-    if (lights == 0) lights = 1;
-    if (lanes < 1) lanes = 1;
-    if (pixels <= a->ws_pixels && nodes <= a->ws_nodes && lights <= a->ws_lights && (!need_sum || a->ws_sum) && lanes <= a->ws_lanes) return RTK_OK;
-    const size_t np = pixels > a->ws_pixels ? pixels : a->ws_pixels;
-    const size_t nn = nodes > a->ws_nodes ? nodes : a->ws_nodes;
-    const size_t nl = lights > a->ws_lights ? lights : a->ws_lights;
-    const int nlanes = lanes > a->ws_lanes ? lanes : a->ws_lanes;
-    const bool sum = need_sum || a->ws_sum;
-    if (nn > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "frame too large for the streaming pipeline's 32-bit node ids");
-    RTK_HIP(hipDeviceSynchronize());
-    free_stream_ws(a);
-    const size_t nh = nn / 2 + 64;                            // every shading point belongs to a distinct node
-    float *sumbuf = nullptr;
-    if (sum) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&sumbuf), np * 3 * sizeof(float)));
-    for (int j = 0; j < nlanes; ++j) {
-        dev::StreamWs &w = a->ws_lane[j];
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.rays), nn * sizeof(dev::RayRec)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.nodes), nn * sizeof(dev::NodeRes)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hits), nh * sizeof(dev::HitRec)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.contrib), nh * nl * sizeof(float2)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.ctrl), dev::kCtrlWords * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_bins), dev::kSortBins * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_bins), dev::kSortBins * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_order), nn * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_order), nh * sizeof(uint32_t)));
-        w.sumbuf = sumbuf;
-        w.node_cap = uint32_t(nn); w.hit_cap = uint32_t(nh);
-        if (!a->lane_done[j]) RTK_HIP(hipEventCreateWithFlags(&a->lane_done[j], hipEventDisableTiming));
-        for (int par = 0; par < 2; ++par) {
-            if (!a->lane_side[j].ready[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].ready[par], hipEventDisableTiming));
-            if (!a->lane_side[j].done[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].done[par], hipEventDisableTiming));
-        }
-    }
-    if (!a->lane_fork) RTK_HIP(hipEventCreateWithFlags(&a->lane_fork, hipEventDisableTiming));
-    {   // the process's lane streams (see LaneStreams); the events that order them stay this accel's own
-        LaneStreams *L = nullptr;
-        RTK_HIP(lane_streams_for(a->device, nlanes, &L));
-        for (int j = 0; j < nlanes; ++j) {
-            a->lane_stream[j] = L->lane[j];
-            a->lane_side[j].stream[0] = L->side[j][0]; a->lane_side[j].stream[1] = L->side[j][1];
-        }
-    }
-    a->ws = a->ws_lane[0];
-    a->ws_lanes = nlanes; a->ws_pixels = np; a->ws_nodes = nn; a->ws_lights = nl; a->ws_sum = sum;
-    return RTK_OK;
-}
-
-int ensure_twopass_ws(rtk_accel *a, size_t pixels, size_t tiles) {
-    if (pixels <= a->tp_pixels && tiles <= a->tp_tiles) return RTK_OK;
-    const size_t np = pixels > a->tp_pixels ? pixels : a->tp_pixels, nt = tiles > a->tp_tiles ? tiles : a->tp_tiles;
-    RTK_HIP(hipDeviceSynchronize());
-    (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
-    a->tp_prim = nullptr; a->tp_bins = nullptr; a->tp_bin_list = nullptr; a->tp_order = nullptr;
-    a->tp_pixels = 0; a->tp_tiles = 0;
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_prim), np * sizeof(float4)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bins), (kCostBins + 1) * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bin_list), size_t(kCostBins) * nt * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_order), nt * sizeof(uint32_t)));
-    a->tp_pixels = np; a->tp_tiles = nt;
-    return RTK_OK;
-}
-
-bool valid_mode(int m) { return m == RTK_TRACE_AUTO || m == RTK_TRACE_LANE || m == RTK_TRACE_WAVE; }
-bool valid_batch_mode(int m) { return valid_mode(m) || m == RTK_TRACE_REPACK; }
-bool valid_frame_mode(int m) { return valid_mode(m) || m == RTK_TRACE_GROUP4 || m == RTK_TRACE_GROUP8 || m == RTK_TRACE_GROUP16 ||
-           m == RTK_TRACE_STREAM || m == RTK_TRACE_TWOPASS; }
-
-struct FrameGeom {
-    uint32_t width, height, bucket, tiles_x, tiles_y, n_buckets, blocks_side, buckets_per_rank;
-    uint32_t skew_q;                   // kernels.hpp rank_bucket(): 0 = round robin, else tiles_x / world (diagonal deal)
-    int rank, world;
-    int sample_begin, sample_end;      // this call renders samples [sample_begin, sample_end) (rtk_render_params.sample_begin/_count)
-};
-
-int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    const int64_t w = p->width > 0 ? p->width : a->scene.width;
-    const int64_t h = p->height > 0 ? p->height : a->scene.height;
-    if (w <= 0 || h <= 0 || w > 65536 || h > 65536) return fail(RTK_ERR_INVALID, "image size must be in [1, 65536]");
-    if (p->spp < 1) return fail(RTK_ERR_INVALID, "spp must be >= 1");
-    if (p->max_ray_depth < 0 || p->max_ray_depth > kMaxRayDepth)
-        return fail(RTK_ERR_INVALID, "max_ray_depth must be in [0, 16]");
-    if (p->diffuse_rays < 0 || p->diffuse_rays > 32767) return fail(RTK_ERR_INVALID, "diffuse_rays must be in [0, 32767]");
-    if (!valid_frame_mode(p->trace_mode)) return fail(RTK_ERR_INVALID, "unknown trace_mode");
-    if (p->sample_begin < 0 || p->sample_count < 0 || p->sample_begin >= p->spp ||
-        int64_t(p->sample_begin) + p->sample_count > p->spp)
-        return fail(RTK_ERR_INVALID, "sample_begin / sample_count must select samples inside [0, spp)");
-    if (p->sample_count == 0 && p->sample_begin != 0) return fail(RTK_ERR_INVALID, "sample_count == 0 means all samples: sample_begin must be 0");
-    g.sample_begin = p->sample_begin;
-    g.sample_end = p->sample_count == 0 ? p->spp : p->sample_begin + p->sample_count;
-    g.world = p->world_size > 1 ? p->world_size : 1;
-    g.rank = p->world_size > 1 ? p->rank : 0;
-    if (g.rank < 0 || g.rank >= g.world) return fail(RTK_ERR_INVALID, "rank must be in [0, world_size)");
-    g.width = uint32_t(w); g.height = uint32_t(h);
-    g.bucket = uint32_t(a->scene.bucket_size > 0 ? a->scene.bucket_size : 64);
-    g.tiles_x = (g.width + g.bucket - 1) / g.bucket;
-    g.tiles_y = (g.height + g.bucket - 1) / g.bucket;
-    g.n_buckets = g.tiles_x * g.tiles_y;
-    g.blocks_side = (g.bucket + 7) / 8;
-    g.buckets_per_rank = (g.n_buckets + uint32_t(g.world) - 1) / uint32_t(g.world);
-    g.skew_q = (g.world > 1 && g.tiles_x % uint32_t(g.world) == 0u) ? g.tiles_x / uint32_t(g.world) : 0u;
-    return RTK_OK;
-}
-
-}  // namespace
 }  // namespace rtk
 
 using namespace rtk;
@@ -657,11 +269,7 @@ int rtk_accel_build(const rtk_scene *scene, const rtk_accel_params *params, rtk_
         }
         for (const DevMaterial &m : a->scene.materials) if (m.kind == RTK_MAT_REFRACTIVE) a->has_refractive = true;
         a->knobs = rtk_knobs::from_env();
-        {
-            double refs = 0.0, sq = 0.0;                        // size of the leaf a random triangle reference lives in
-            for (const DevNode &l : a->tree.dev_leaves) { refs += double(l.b); sq += double(l.b) * double(l.b); }
-            a->stream_slices_auto = (refs > 0.0 && sq / refs < 150.0) ? 1 : 4;
-        }
+        a->stream_slices_auto = stream_slices_for(a->tree);
         a->fast_traversal = a->params.traversal == RTK_TRAVERSAL_FAST || a->knobs.traversal_fast;
         if (a->fast_traversal) build_fast_leaf_orders(a->tree);
         a->coords_small = true;
@@ -757,1143 +365,6 @@ void rtk_accel_destroy(rtk_accel *a) {
     delete a;
 }
 
-// ---------------------------------------------------------------- dynamic geometry (build.hip)
-
-namespace {
-
-// Grows a device buffer to at least `need` bytes (with head room; the old contents are not kept).  Freeing synchronises the
-// device: this is the "second block" of an update, taken only when a buffer has to grow.
-int grow_dev(void **p, size_t *cap, size_t need) {
-    if (need == 0) need = 1;
-    if (*p != nullptr && need <= *cap) return RTK_OK;
-    (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 2 + 256;
-    RTK_HIP(hipMalloc(p, n));
-    *cap = n;
-    return RTK_OK;
-}
-
-int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
-    if (*p != nullptr && need <= *cap) return RTK_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 2 + 256;
-    RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(p), n, hipHostMallocDefault));
-    *cap = n;
-    return RTK_OK;
-}
-
-// What an update needs of the topology, which never changes: vertex ids per triangle over the concatenated vertex array, the
-// vertex -> (triangle, corner) incidence lists and which triangles are opaque.  Made on the first update, kept.
-int ensure_update_static(rtk_accel *a) {
-    if (a->up_static) return RTK_OK;
-    const size_t nv = size_t(a->scene.n_vertices), nt = size_t(a->scene.n_triangles);
-    if (nt * 3 > 0xFFFFFFF0ull || nv > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "scene too large for the device build's 32-bit indices");
-    std::vector<uint32_t> index(nt * 3), off(nv + 1, 0u), inc(nt * 3);
-    std::vector<uint8_t> opaque(nt, uint8_t(1));
-    size_t voff = 0, t = 0;
-    for (const HostMesh &m : a->scene.meshes) {
-        const bool refr = size_t(m.material) < a->scene.materials.size() && a->scene.materials[size_t(m.material)].kind == RTK_MAT_REFRACTIVE;
-        for (size_t ti = 0; ti < m.indices.size() / 3; ++ti, ++t) {
-            for (size_t k = 0; k < 3; ++k) index[t * 3 + k] = uint32_t(voff + m.indices[ti * 3 + k]);
-            opaque[t] = refr ? 0 : 1;
-        }
-        voff += m.vertices.size();
-    }
-    if (voff != nv || t != nt) return fail(RTK_ERR_INVALID, "internal: the accel's scene copy lost its vertices");
-    // Incidence lists by counting sort over (triangle, corner) in ascending order: each vertex's list ascends by triangle and
-    // keeps duplicates, which is the order mesh.hpp:36-38 adds the face normals in (build.hip, k_build_normals).
-    for (uint32_t v : index) off[size_t(v) + 1] += 1u;
-    for (size_t v = 0; v < nv; ++v) off[v + 1] += off[v];
-    {
-        std::vector<uint32_t> cur(off.begin(), off.end() - 1);
-        for (size_t e = 0; e < nt * 3; ++e) inc[cur[index[e]]++] = uint32_t(e);
-    }
-    int rc;
-    // (a call that failed half way left what it had made: made once, never twice)
-    if (!a->up_index && (rc = upload(index, &a->up_index)) != RTK_OK) { (void)hipFree(a->up_index); a->up_index = nullptr; return rc; }
-    if (!a->up_inc_off && (rc = upload(off, &a->up_inc_off)) != RTK_OK) { (void)hipFree(a->up_inc_off); a->up_inc_off = nullptr; return rc; }
-    if (!a->up_inc && (rc = upload(inc, &a->up_inc)) != RTK_OK) { (void)hipFree(a->up_inc); a->up_inc = nullptr; return rc; }
-    if (!a->up_opaque && (rc = upload(opaque, &a->up_opaque)) != RTK_OK) { (void)hipFree(a->up_opaque); a->up_opaque = nullptr; return rc; }
-    if (!a->geom_ready) RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
-    const HostTree &T = a->tree;
-    auto bytes = [](size_t n, size_t each) { return (n == 0 ? 1 : n) * each; };
-    a->active_cap[G_NODES] = bytes(T.dev_nodes.size(), sizeof(DevNode));
-    a->active_cap[G_LEAVES] = bytes(T.dev_leaves.size(), sizeof(DevNode));
-    a->active_cap[G_FAST] = a->d_leaves_fast ? bytes(T.dev_leaves_fast.size(), sizeof(DevNode)) : 0;
-    a->active_cap[G_TRIS] = bytes(T.dev_tris.size(), sizeof(DevTri));
-    a->active_cap[G_IDS] = bytes(T.dev_tri_ids.size(), sizeof(uint32_t));
-    a->active_cap[G_SHADE] = bytes(T.dev_shade.size(), sizeof(DevShade));
-    // (the opaque-only copy was uploaded at its exact size, which is not kept: 0 makes the first update allocate its own)
-    a->up_static = true;
-    return RTK_OK;
-}
-
-int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
-    int rc = ensure_update_static(a);
-    if (rc != RTK_OK) return rc;
-    const uint32_t nv = uint32_t(a->scene.n_vertices), nt = uint32_t(a->scene.n_triangles);
-    const bool occl = a->occl_on;
-    // per-triangle scratch (the triangle count never changes: allocated once) and the new shading records
-    if (!a->up_tris) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tris), std::max<size_t>(1, nt) * sizeof(DevTri)));
-    if (!a->up_tbox) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tbox), std::max<size_t>(1, nt) * 6 * sizeof(float)));
-    if ((rc = grow_dev(&a->spare[G_SHADE], &a->spare_cap[G_SHADE], size_t(nt) * sizeof(DevShade))) != RTK_OK) return rc;
-    // Capacities of the build: a tree of depth d has at most 2^(d+1) - 1 nodes; the lists of all levels lie one behind the
-    // other, a level's lists together are about as long as leaf_refs.  Both are checked on the device; a build that does not fit
-    // raises a flag, and is repeated with more room.
-    const size_t max_nodes = (size_t(1) << (a->params.max_depth + 1)) - 1;
-    size_t want_nodes = a->up_cap_nodes ? a->up_cap_nodes : std::max<size_t>(1024, 4 * a->tree.dev_nodes.size());
-    size_t want_refs = a->up_cap_refs ? a->up_cap_refs
-                                      : std::max<size_t>(4096, 2 * size_t(nt) * size_t(std::min(a->params.max_depth, 12) + 2));
-    dev::BuildHdr hdr;
-    for (int attempt = 0;; ++attempt) {
-        if (want_nodes > max_nodes) want_nodes = max_nodes;
-        if (attempt > 16 || want_refs > 0x7FFFFFF0ull) return fail(RTK_ERR_INVALID, "tree too large for 32-bit node/triangle indices");
-        if (want_refs < nt) want_refs = nt;
-        if (want_nodes != a->up_cap_nodes || !a->up_table) {
-            const size_t bytes = sizeof(dev::BuildHdr) + want_nodes * sizeof(dev::BuildNode);
-            (void)hipFree(a->up_table); a->up_table = nullptr; a->up_cap_nodes = 0;
-            if (a->up_table_host) (void)hipHostFree(a->up_table_host);
-            a->up_table_host = nullptr;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_table), bytes));
-            RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->up_table_host), bytes, hipHostMallocDefault));
-            a->up_cap_nodes = want_nodes;
-        }
-        if (want_refs != a->up_cap_refs || !a->up_ref_id) {
-            (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);
-            a->up_ref_id = a->up_ref_node = nullptr; a->up_cap_refs = 0;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_id), want_refs * sizeof(uint32_t)));
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_node), want_refs * sizeof(uint32_t)));
-            a->up_cap_refs = want_refs;
-        }
-        dev::BuildArgs B;
-        B.verts = d_verts; B.n_verts = nv; B.n_tris = nt;
-        B.index = a->up_index; B.inc_off = a->up_inc_off; B.inc = a->up_inc;
-        B.opaque = occl ? a->up_opaque : nullptr;
-        B.shade_old = a->d_shade; B.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
-        B.tris = a->up_tris; B.tbox = a->up_tbox;
-        B.ref_id = a->up_ref_id; B.ref_node = a->up_ref_node;
-        B.cap_refs = uint32_t(a->up_cap_refs); B.cap_nodes = uint32_t(a->up_cap_nodes);
-        B.max_depth = a->params.max_depth; B.max_leaf = a->params.max_leaf_size;
-        B.hdr = reinterpret_cast<dev::BuildHdr *>(a->up_table);
-        B.nodes = reinterpret_cast<dev::BuildNode *>(a->up_table + sizeof(dev::BuildHdr));
-        const hipError_t e = launch_build(B, s);
-        if (e != hipSuccess) return hip_fail(e, "launch device build");
-        // the one place an update blocks the host: flags, sizes and the node table
-        RTK_HIP(hipMemcpyAsync(a->up_table_host, a->up_table, sizeof(dev::BuildHdr) + a->up_cap_nodes * sizeof(dev::BuildNode), hipMemcpyDeviceToHost, s));
-        RTK_HIP(hipStreamSynchronize(s));
-        std::memcpy(&hdr, a->up_table_host, sizeof(hdr));
-        const uint32_t raised = ~hdr.ok;
-        if (raised & dev::kBuildNonFinite) return fail(RTK_ERR_INVALID, "vertices must be finite");
-        if ((raised & (dev::kBuildRefOverflow | dev::kBuildNodeOverflow)) == 0u) break;
-        if (raised & dev::kBuildNodeOverflow) want_nodes = std::max<size_t>(2 * a->up_cap_nodes, 2 * size_t(hdr.need_nodes));
-        if (raised & dev::kBuildRefOverflow) want_refs = std::max<size_t>(2 * a->up_cap_refs, 2 * size_t(hdr.need_refs));
-    }
-    // numbering on the host (kdtree.cpp): reference order, traversal order with skip links, leaf offsets in both, FAST orders
-    const dev::BuildNode *bn = reinterpret_cast<const dev::BuildNode *>(a->up_table_host + sizeof(dev::BuildHdr));
-    HostTree T;
-    std::vector<dev::GatherLeaf> gather;
-    tree_from_build_nodes(bn, T, gather);
-    if (T.nodes.size() != hdr.n_nodes) return fail(RTK_ERR_INVALID, "internal: the device build's node table is not a tree");
-    if (a->fast_traversal) build_fast_leaf_orders(T);
-    size_t n_refs = 0;
-    for (const dev::GatherLeaf &g : gather) n_refs += g.count;
-    if (n_refs > 0x7FFFFFFFull) return fail(RTK_ERR_INVALID, "tree too large for 32-bit node/triangle indices");
-    std::vector<DevNode> onodes, oleaves;
-    size_t n_opaque = 0;
-    if (occl) {                                                         // as ensure_device: the same nodes, their leaves without the transmissive triangles
-        onodes = T.dev_nodes;
-        size_t li = 0;
-        for (DevNode &n : onodes) {
-            if (n.b == DEV_INNER) continue;
-            dev::GatherLeaf &g = gather[li++];                          // (dev_leaves and gather are both the leaves in dev_nodes' order)
-            g.dst_occl = uint32_t(n_opaque);
-            n.a = uint32_t(n_opaque); n.b = g.pad[0];
-            n_opaque += g.pad[0];
-            if (n.b != 0u) oleaves.push_back(n);
-        }
-        if (oleaves.empty()) { DevNode n = onodes[0]; n.a = 0u; n.b = 0u; oleaves.push_back(n); }
-    }
-    for (dev::GatherLeaf &g : gather) g.pad[0] = 0u;
-    // room in the spare set
-    void **sp = a->spare;
-    size_t *sc = a->spare_cap;
-    if ((rc = grow_dev(&sp[G_NODES], &sc[G_NODES], T.dev_nodes.size() * sizeof(DevNode))) != RTK_OK) return rc;
-    if ((rc = grow_dev(&sp[G_LEAVES], &sc[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode))) != RTK_OK) return rc;
-    if (a->fast_traversal && (rc = grow_dev(&sp[G_FAST], &sc[G_FAST], T.dev_leaves_fast.size() * sizeof(DevNode))) != RTK_OK) return rc;
-    if ((rc = grow_dev(&sp[G_TRIS], &sc[G_TRIS], n_refs * sizeof(DevTri))) != RTK_OK) return rc;
-    if ((rc = grow_dev(&sp[G_IDS], &sc[G_IDS], n_refs * sizeof(uint32_t))) != RTK_OK) return rc;
-    if ((rc = grow_dev(&sp[G_LREFS], &sc[G_LREFS], n_refs * sizeof(int32_t))) != RTK_OK) return rc;
-    if (occl) {
-        if ((rc = grow_dev(&sp[G_ONODES], &sc[G_ONODES], onodes.size() * sizeof(DevNode))) != RTK_OK) return rc;
-        if ((rc = grow_dev(&sp[G_OLEAVES], &sc[G_OLEAVES], oleaves.size() * sizeof(DevNode))) != RTK_OK) return rc;
-        if ((rc = grow_dev(&sp[G_OTRIS], &sc[G_OTRIS], std::max<size_t>(1, n_opaque) * sizeof(DevTri))) != RTK_OK) return rc;
-        if ((rc = grow_dev(&sp[G_OIDS], &sc[G_OIDS], std::max<size_t>(1, n_opaque) * sizeof(uint32_t))) != RTK_OK) return rc;
-    }
-    {
-        size_t gcap = a->up_gather_cap * sizeof(dev::GatherLeaf);
-        if ((rc = grow_dev(reinterpret_cast<void **>(&a->up_gather), &gcap, gather.size() * sizeof(dev::GatherLeaf))) != RTK_OK) return rc;
-        a->up_gather_cap = gcap / sizeof(dev::GatherLeaf);
-    }
-    // the small tables go up through one pinned buffer (the copies are stream-ordered and the host does not wait for them)
-    struct Up { const void *src; void *dst; size_t bytes; };
-    const Up ups[] = {
-        {T.dev_nodes.data(), sp[G_NODES], T.dev_nodes.size() * sizeof(DevNode)},
-        {T.dev_leaves.data(), sp[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode)},
-        {T.dev_leaves_fast.data(), sp[G_FAST], a->fast_traversal ? T.dev_leaves_fast.size() * sizeof(DevNode) : 0},
-        {gather.data(), a->up_gather, gather.size() * sizeof(dev::GatherLeaf)},
-        {onodes.data(), sp[G_ONODES], onodes.size() * sizeof(DevNode)},
-        {oleaves.data(), sp[G_OLEAVES], oleaves.size() * sizeof(DevNode)},
-    };
-    size_t total = 0;
-    for (const Up &u : ups) total += (u.bytes + 63) & ~size_t(63);
-    if ((rc = grow_pinned(&a->up_stage, &a->up_stage_cap, total)) != RTK_OK) return rc;
-    size_t at = 0;
-    for (const Up &u : ups) {
-        if (u.bytes == 0) continue;
-        std::memcpy(a->up_stage + at, u.src, u.bytes);
-        RTK_HIP(hipMemcpyAsync(u.dst, a->up_stage + at, u.bytes, hipMemcpyHostToDevice, s));
-        at += (u.bytes + 63) & ~size_t(63);
-    }
-    dev::GatherArgs G;
-    G.leaves = a->up_gather; G.n_leaves = uint32_t(gather.size());
-    G.ref_id = a->up_ref_id; G.tris_in = a->up_tris; G.opaque = occl ? a->up_opaque : nullptr;
-    G.tris = static_cast<DevTri *>(sp[G_TRIS]); G.tri_ids = static_cast<uint32_t *>(sp[G_IDS]); G.leaf_refs = static_cast<int32_t *>(sp[G_LREFS]);
-    G.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); G.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]);
-    const hipError_t eg = launch_gather(G, s);
-    if (eg != hipSuccess) return hip_fail(eg, "launch k_build_gather");
-    if (occl && n_opaque == 0) {                                        // nothing opaque: keep the pointers valid, as ensure_device does
-        if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp[G_OTRIS], sp[G_TRIS], sizeof(DevTri), hipMemcpyDeviceToDevice, s));
-        else RTK_HIP(hipMemsetAsync(sp[G_OTRIS], 0, sizeof(DevTri), s));
-        RTK_HIP(hipMemsetAsync(sp[G_OIDS], 0, sizeof(uint32_t), s));
-    }
-    RTK_HIP(hipEventRecord(a->geom_ready, s));
-    // ---- nothing below fails: swap the sets and bring the host's picture of the accel up to date
-    void **act[kGeomBufs] = {reinterpret_cast<void **>(&a->d_nodes), reinterpret_cast<void **>(&a->d_leaves), reinterpret_cast<void **>(&a->d_leaves_fast),
-                             reinterpret_cast<void **>(&a->d_tris), reinterpret_cast<void **>(&a->d_tri_ids), reinterpret_cast<void **>(&a->d_shade),
-                             reinterpret_cast<void **>(&a->d_leaf_refs), reinterpret_cast<void **>(&a->d_occl_nodes), reinterpret_cast<void **>(&a->d_occl_leaves),
-                             reinterpret_cast<void **>(&a->d_occl_tris), reinterpret_cast<void **>(&a->d_occl_ids)};
-    for (int i = 0; i < kGeomBufs; ++i) {
-        if (i == G_FAST && !a->fast_traversal) continue;
-        if (i >= G_ONODES && !occl) continue;
-        std::swap(*act[i], a->spare[i]);
-        std::swap(a->active_cap[i], a->spare_cap[i]);
-    }
-    a->geom_pending = true;
-    a->occl_n_leaves = occl ? uint32_t(oleaves.size()) : 0u;
-    a->tree.nodes = std::move(T.nodes);
-    a->tree.dev_nodes = std::move(T.dev_nodes);
-    a->tree.dev_leaves = std::move(T.dev_leaves);
-    a->tree.dev_leaves_fast = std::move(T.dev_leaves_fast);
-    a->tree.depth = T.depth;
-    // what the host held per triangle, per reference and per vertex describes the old geometry: dropped, not left to lie
-    // (rtk_accel_tree_dump fetches leaf_refs from the device)
-    std::vector<HostTriangle>().swap(a->tree.triangles);
-    std::vector<int32_t>().swap(a->tree.leaf_refs);
-    std::vector<DevTri>().swap(a->tree.dev_tris);
-    std::vector<uint32_t>().swap(a->tree.dev_tri_ids);
-    std::vector<DevShade>().swap(a->tree.dev_shade);
-    for (HostMesh &m : a->scene.meshes) { std::vector<Vec3>().swap(m.vertices); std::vector<Vec3>().swap(m.vertex_normals); }
-    a->refs_on_device = true;
-    a->n_leaf_refs_dev = int32_t(n_refs);
-    a->coords_small = (~hdr.ok & dev::kBuildCoordsBig) == 0u;
-    {
-        double refs = 0.0, sq = 0.0;                                    // as rtk_accel_build
-        for (const DevNode &l : a->tree.dev_leaves) { refs += double(l.b); sq += double(l.b) * double(l.b); }
-        a->stream_slices_auto = (refs > 0.0 && sq / refs < 150.0) ? 1 : 4;
-    }
-    // the launch order learnt from the old silhouette and the engines' trial on it say nothing about the new geometry
-    a->fb_valid = false; a->fb_order_valid = false; a->fb_age = 0;
-    a->fb_nwgs_pending = false; a->fb_nwgs_known = false;
-    a->trial_state = 0;
-    return RTK_OK;
-}
-
-}  // namespace
-
-int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void *hip_stream) {
-    if (!a || !d_vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
-        const int rc = ensure_device(a);
-        if (rc != RTK_OK) return rc;
-        // entry: nothing issued earlier on this accel, on whatever stream, may still read a buffer the update rewrites
-        RTK_HIP(hipDeviceSynchronize());
-        a->geom_pending = false;
-        return update_vertices_impl(a, d_vertices, static_cast<hipStream_t>(hip_stream));
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
-}
-
-int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
-    if (!a || !vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
-        int rc = ensure_device(a);
-        if (rc != RTK_OK) return rc;
-        const size_t n = size_t(a->scene.n_vertices) * 3;
-        for (size_t i = 0; i < n; ++i)
-            if (!std::isfinite(vertices[i])) return fail(RTK_ERR_INVALID, "vertices must be finite");
-        RTK_HIP(hipDeviceSynchronize());
-        a->geom_pending = false;
-        if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));   // (the vertex count never changes)
-        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
-        return update_vertices_impl(a, a->up_verts, nullptr);
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
-}
-
-// ---------------------------------------------------------------- batched intersect
-
-// workspace of the ray repacking: keys and indices (double-buffered for the sort), rocPRIM's temporary storage; grows, never shrinks
-static int ensure_repack_ws(rtk_accel *a, size_t n) {
-    if (!a->rp_bounds) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rp_bounds), kRepackBoundsAlloc * sizeof(uint32_t)));
-    if (a->rp_cap >= n) return RTK_OK;
-    (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
-    a->rp_keys = a->rp_idx = nullptr; a->rp_temp = nullptr; a->rp_cap = 0;
-    size_t tb = 0;
-    RTK_HIP(repack_temp_bytes(n, &tb));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rp_keys), 2 * n * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rp_idx), 2 * n * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(&a->rp_temp, tb > 0 ? tb : 16));
-    a->rp_temp_bytes = tb; a->rp_cap = n;
-    return RTK_OK;
-}
-
-static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, int cull, int mode, rtk_hit *d_out,
-                                 hipStream_t s, bool stats) {
-    if (!valid_batch_mode(mode)) return fail(RTK_ERR_INVALID, "unknown trace_mode");
-    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many rays for one launch");
-    if (n > 0 && (!d_rays || !d_out)) return fail(RTK_ERR_INVALID, "null ray or hit buffer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(RTK_ERR_INVALID, "hit buffer must be 16-byte aligned");
-    dev::IntersectArgs A;
-    A.tree = tree_view(a);
-    A.rays = d_rays; A.out = d_out; A.n = n; A.cull = cull ? 1 : 0; A.counters = a->d_counters; A.perm = nullptr; A.raster_w = 0u; A.verdict = nullptr;
-    A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;
-    // Ray repacking (repack.hip).  Large batches are probed first (every 16th wave; one stream synchronisation): waves that are
-    // coherent as they come are walked wave-cooperatively; a batch in no useful order is sorted by origin / direction cell and
-    // then walked wave-cooperatively when the sort makes tight waves (three varying dimensions: 10 bits each), with the per-lane
-    // fallback when it cannot (six: 5 bits each).  4 M rays on scene5: shuffled camera rays 4.5 -> 0.47 ms, uniform secondary
-    // rays 11.3 -> 4.1 ms, camera rays in pixel order 0.8 (RTK_TRACE_AUTO before) -> 0.3 ms.
-    const bool big = n >= (size_t(1) << 18) && n < (size_t(1) << 32);
-    const bool forced = mode == RTK_TRACE_REPACK;
-    if (forced) mode = RTK_TRACE_AUTO;
-    const bool sortable = !stats && n >= 2 && n < (size_t(1) << 32);
-    const bool probe = !stats && !forced && mode == RTK_TRACE_AUTO && a->knobs.repack && big;
-    if ((forced && sortable) || probe) {
-        int rc = ensure_repack_ws(a, n);
-        if (rc != RTK_OK) return rc;
-        // The workspace (bounds, keys, permutation) belongs to the accel: a batch on another stream may still be walking the
-        // permutation of the previous call.  Its k_intersect recorded rp_done; this stream waits for it before it rewrites anything.
-        if (a->rp_done == nullptr) RTK_HIP(hipEventCreateWithFlags(&a->rp_done, hipEventDisableTiming));
-        if (a->rp_in_use) RTK_HIP(hipStreamWaitEvent(s, a->rp_done, 0));
-        hipError_t eb = hipSuccess;
-        bool sort = forced;
-        unsigned sort_from_bit = 0u;
-        bool keys_made = false;
-        int sorted_mode = RTK_TRACE_AUTO;                                    // any order: wave-cooperative with the per-lane fallback
-        if (probe) {
-            // AUTO: the probe's verdict is needed on the host (one stream synchronisation; RTK_TRACE_REPACK and RTK_REPACK=0 never block)
-            // The verdict is made on the device (k_raster_probe) and needed on the host; while it travels, the launch a coherent
-            // batch needs is already under way -- it reads the same verdict and does nothing if the batch is to be sorted.
-            const uint32_t probe_stride = uint32_t(((n + 63) / 64 + 4095) / 4096 > 16 ? ((n + 63) / 64 + 4095) / 4096 : 16);   // ~4,096 waves looked at
-            unsigned fold = 0;
-            eb = launch_ray_bounds(d_rays, n, a->rp_bounds, probe_stride, true, s, &fold);
-            if (eb == hipSuccess) eb = launch_raster_probe(d_rays, n, a->rp_bounds, a->knobs.raster_tiles, s, fold);
-            if (eb != hipSuccess) return hip_fail(eb, "launch k_ray_bounds (probe)");
-            if (!a->rp_host) {
-                RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->rp_host), kRepackBoundsWords * sizeof(uint32_t), hipHostMallocDefault));
-                RTK_HIP(hipEventCreateWithFlags(&a->rp_probe_ev, hipEventDisableTiming));
-            }
-            uint32_t *h = a->rp_host;
-            RTK_HIP(hipMemcpyAsync(h, a->rp_bounds, kRepackBoundsWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            RTK_HIP(hipEventRecord(a->rp_probe_ev, s));
-            {
-                dev::IntersectArgs Spec = A;
-                Spec.verdict = a->rp_bounds;
-                const hipError_t es = launch_intersect(Spec, RTK_TRACE_WAVE, false, s);
-                if (es != hipSuccess) return hip_fail(es, "launch k_intersect");
-                a->rp_in_use = true;
-            }
-            // ... and so are the keys a batch to be sorted needs (k_ray_keys returns at once if it is not): the verdict's trip to the
-            // host and the launches that follow it no longer leave the stream idle
-            if (!a->knobs.repack_full_bounds) {
-                eb = launch_ray_keys(d_rays, n, a->rp_bounds, a->rp_keys, a->rp_idx, s, a->knobs.repack_dirs3, true);
-                if (eb != hipSuccess) return hip_fail(eb, "launch k_ray_keys");
-                keys_made = true;
-            }
-            RTK_HIP(hipEventRecord(a->rp_done, s));                         // (both read the workspace's verdict words)
-            RTK_HIP(hipEventSynchronize(a->rp_probe_ev));                   // the verdict, not the trace
-            sort = h[16] != 0u;
-            if (!sort) return RTK_OK;                                        // coherent as it comes: that launch was the batch
-            if (h[17] <= 3u) {
-                sorted_mode = RTK_TRACE_WAVE;                                // ten or fifteen bits per dimension: the sort makes tight waves
-                // ... also when the lowest ones stay unsorted: one or two radix passes less (two dimensions: 8 of the 15 bits each)
-                sort_from_bit = h[17] <= 2u ? uint32_t(a->knobs.repack_skip_bits2) : uint32_t(a->knobs.repack_skip_bits);
-            }
-        }
-        if (sort) {
-            // The cells of the sort keys lie in the bounds of a SAMPLE of the batch (the probe's, where there was one; ~4,096 waves
-            // otherwise): a ray outside them lands in a border cell -- an order a little worse for it, never another result -- and a
-            // pass over all rays (0.13 ms of a 2^24-ray batch's 1.8) is saved.
-            if (!probe) {
-                const size_t waves = (n + 63) / 64;
-                eb = launch_ray_bounds(d_rays, n, a->rp_bounds, a->knobs.repack_full_bounds ? 1u : uint32_t((waves + 4095) / 4096), false, s);
-            } else if (a->knobs.repack_full_bounds) eb = launch_ray_bounds(d_rays, n, a->rp_bounds, 1u, false, s);
-            if (eb == hipSuccess && !keys_made) eb = launch_ray_keys(d_rays, n, a->rp_bounds, a->rp_keys, a->rp_idx, s, a->knobs.repack_dirs3, false);
-            if (eb == hipSuccess) eb = launch_key_sort(n, a->rp_keys, a->rp_idx, a->rp_temp, a->rp_temp_bytes, s, sort_from_bit);
-            if (eb != hipSuccess) return hip_fail(eb, "ray repacking");
-            A.perm = a->rp_idx + n;
-            mode = a->knobs.repack_trace >= 0 ? a->knobs.repack_trace : sorted_mode;
-        }
-    }
-    const hipError_t e = launch_intersect(A, mode, stats, s);
-    if (e != hipSuccess) return hip_fail(e, "launch k_intersect");
-    if (A.perm != nullptr) {
-        RTK_HIP(hipEventRecord(a->rp_done, s));
-        a->rp_in_use = true;
-    }
-    return RTK_OK;
-}
-
-int rtk_accel_intersect_device(rtk_accel *a, const rtk_ray *d_rays, size_t n, int cull, int mode, rtk_hit *d_out, void *stream) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    std::lock_guard<std::mutex> lock(a->mu);
-    const int rc = ensure_device(a, static_cast<hipStream_t>(stream));
-    if (rc != RTK_OK) return rc;
-    return intersect_device_impl(a, d_rays, n, cull, mode, d_out, static_cast<hipStream_t>(stream), false);
-}
-
-int rtk_accel_intersect_stats(rtk_accel *a, const rtk_ray *d_rays, size_t n, int cull, int mode, rtk_hit *d_out,
-                              rtk_counters *counters) {
-    if (!a || !counters) return fail(RTK_ERR_INVALID, "null accel or counters");
-    std::lock_guard<std::mutex> lock(a->mu);
-    int rc = ensure_device(a);
-    if (rc != RTK_OK) return rc;
-    RTK_HIP(hipMemsetAsync(a->d_counters, 0, kCounterWords * sizeof(unsigned long long), nullptr));
-    rc = intersect_device_impl(a, d_rays, n, cull, mode, d_out, nullptr, true);
-    if (rc != RTK_OK) return rc;
-    unsigned long long h[8];
-    RTK_HIP(hipMemcpy(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-    counters->rays = h[0]; counters->primary = 0; counters->hits = h[2]; counters->nodes = h[3]; counters->boxpass = h[4];
-    counters->leaves = h[5]; counters->tris = h[6]; counters->packets16 = h[7];
-    return RTK_OK;
-}
-
-int rtk_accel_intersect(rtk_accel *a, const rtk_ray *rays, size_t n, int cull, int mode, rtk_hit *out) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    if (n > 0 && (!rays || !out)) return fail(RTK_ERR_INVALID, "null ray or hit buffer");
-    std::lock_guard<std::mutex> lock(a->mu);
-    int rc = ensure_device(a);
-    if (rc != RTK_OK) return rc;
-    if (n == 0) return RTK_OK;
-    rtk_ray *d_rays = nullptr;
-    rtk_hit *d_out = nullptr;
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d_rays), n * sizeof(rtk_ray)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_out), n * sizeof(rtk_hit));
-    if (e != hipSuccess) { (void)hipFree(d_rays); return hip_fail(e, "hipMalloc hits"); }
-    e = hipMemcpy(d_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = intersect_device_impl(a, d_rays, n, cull, mode, d_out, nullptr, false);
-        if (rc == RTK_OK) e = hipMemcpy(out, d_out, n * sizeof(rtk_hit), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_rays); (void)hipFree(d_out);
-    if (rc != RTK_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "intersect copy");
-    return RTK_OK;
-}
-
-// ---------------------------------------------------------------- batched occlusion
-
-// Word of the counter buffer the host variant counts its closest-hit queries in: the last of the four words behind the frame
-// counters (the first-frame prior's six 32-bit cursors fill the first three), so the counters of the most recent frame
-// (rtk_render_last_counters) stay as that frame left them.
-static constexpr int kOccludedCountWord = kCounterWords + 3;
-
-static int occluded_check(const rtk_accel *a, const void *rays, const void *max_t, size_t n, float shadow_bias, int mode, const void *out) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    if (!valid_mode(mode)) return fail(RTK_ERR_INVALID, "trace_mode of an occlusion batch must be RTK_TRACE_AUTO, RTK_TRACE_LANE or RTK_TRACE_WAVE");
-    if (!std::isfinite(shadow_bias)) return fail(RTK_ERR_INVALID, "shadow_bias must be finite");
-    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many queries for one launch");
-    if (n > 0 && (!rays || !max_t || !out)) return fail(RTK_ERR_INVALID, "null ray, max_t or answer buffer");
-    return RTK_OK;
-}
-
-static int occluded_launch(rtk_accel *a, const rtk_ray *d_rays, const float *d_max_t, size_t n, float shadow_bias, int mode,
-                           uint8_t *d_out, hipStream_t s, bool count) {
-    dev::OccludedArgs A;
-    A.tree = tree_view(a);
-    A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;
-    A.materials = a->d_materials;
-    A.rays = d_rays; A.max_t = d_max_t; A.out = d_out; A.n = n;
-    A.shadow_bias = shadow_bias;
-    A.has_refractive = a->has_refractive ? 1 : 0;
-    A.n_intersect = count ? a->d_counters + kOccludedCountWord : nullptr;
-    const hipError_t e = launch_occluded(A, mode, s);
-    if (e != hipSuccess) return hip_fail(e, "launch k_occluded");
-    return RTK_OK;
-}
-
-int rtk_accel_occluded_device(rtk_accel *a, const rtk_ray *d_rays, const float *d_max_t, size_t n, float shadow_bias, int mode,
-                              uint8_t *d_out, void *stream) {
-    int rc = occluded_check(a, d_rays, d_max_t, n, shadow_bias, mode, d_out);
-    if (rc != RTK_OK) return rc;
-    if (n == 0) return RTK_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    rc = ensure_device(a, static_cast<hipStream_t>(stream));
-    if (rc != RTK_OK) return rc;
-    return occluded_launch(a, d_rays, d_max_t, n, shadow_bias, mode, d_out, static_cast<hipStream_t>(stream), false);
-}
-
-int rtk_accel_occluded(rtk_accel *a, const rtk_ray *rays, const float *max_t, size_t n, float shadow_bias, int mode, uint8_t *out,
-                       uint64_t *n_intersections) {
-    int rc = occluded_check(a, rays, max_t, n, shadow_bias, mode, out);
-    if (rc != RTK_OK) return rc;
-    if (n == 0) {
-        if (n_intersections) *n_intersections = 0;
-        return RTK_OK;
-    }
-    std::lock_guard<std::mutex> lock(a->mu);
-    rc = ensure_device(a);
-    if (rc != RTK_OK) return rc;
-    if (a->oc_cap < n) {
-        (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
-        a->oc_rays = nullptr; a->oc_max_t = nullptr; a->oc_out = nullptr; a->oc_cap = 0;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_rays), n * sizeof(rtk_ray)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_max_t), n * sizeof(float)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->oc_out), n));
-        a->oc_cap = n;
-    }
-    RTK_HIP(hipMemcpy(a->oc_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-    RTK_HIP(hipMemcpy(a->oc_max_t, max_t, n * sizeof(float), hipMemcpyHostToDevice));
-    if (n_intersections) RTK_HIP(hipMemsetAsync(a->d_counters + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
-    rc = occluded_launch(a, a->oc_rays, a->oc_max_t, n, shadow_bias, mode, a->oc_out, nullptr, n_intersections != nullptr);
-    if (rc != RTK_OK) return rc;
-    RTK_HIP(hipMemcpy(out, a->oc_out, n, hipMemcpyDeviceToHost));
-    if (n_intersections) {
-        unsigned long long h = 0;
-        RTK_HIP(hipMemcpy(&h, a->d_counters + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
-        *n_intersections = h;
-    }
-    return RTK_OK;
-}
-
-// ---------------------------------------------------------------- frame
-
-int rtk_render_output_floats(const rtk_accel *a, const rtk_render_params *p, size_t *n_floats) {
-    if (!n_floats) return fail(RTK_ERR_INVALID, "null n_floats");
-    FrameGeom g;
-    const int rc = frame_geom(a, p, g);
-    if (rc != RTK_OK) return rc;
-    *n_floats = (g.world > 1) ? size_t(g.buckets_per_rank) * g.bucket * g.bucket * 3 : size_t(g.width) * g.height * 3;
-    return RTK_OK;
-}
-
-static int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d_out, hipStream_t s) {
-    FrameGeom g;
-    int rc = frame_geom(a, p, g);
-    if (rc != RTK_OK) return rc;
-    if (!d_out) return fail(RTK_ERR_INVALID, "null output buffer");
-    dev::RenderArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.tree = tree_view(a);
-    A.materials = a->d_materials; A.lights = a->d_lights;
-    A.textures = a->d_textures; A.tri_uv = a->d_tri_uv; A.tex_pixels = a->d_tex_pixels;
-    A.n_lights = int(a->scene.lights.size());
-    A.has_refractive = a->has_refractive ? 1 : 0;
-    std::memcpy(A.cam_pos, a->scene.cam_pos, sizeof(A.cam_pos));
-    std::memcpy(A.cam_mat, a->scene.cam_mat, sizeof(A.cam_mat));
-    std::memcpy(A.background, a->scene.background, sizeof(A.background));
-    A.width = g.width; A.height = g.height;
-    A.aspect = static_cast<float>(g.width) / static_cast<float>(g.height);                    // render.hpp:26
-    // render.hpp:55-57: `const F fov_radians = degrees_to_radians(fov_degrees)` is evaluated in double (fov_degrees is a
-    // double constant, utils/convert.hpp:4-6) and ROUNDED TO FLOAT by the declaration; `std::tan(fov_radians / F(2))` is
-    // then the float overload (tanf), and `screen_x *=` a float multiply (common.hip.hpp camera_ray).
-    const float fov_radians = static_cast<float>(p->fov_degrees * (3.14159265358979323846 / 180.0));
-    A.tan_half_fov = std::tan(fov_radians / 2.0f);
-    A.spp = p->spp; A.max_depth = p->max_ray_depth; A.diffuse_rays = p->diffuse_rays; A.seed = p->seed;
-    A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height);
-    A.spp_f = static_cast<float>(p->spp); A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
-    A.sample_begin = g.sample_begin; A.sample_end = g.sample_end;
-    A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
-    A.bucket = g.bucket; A.tiles_x = g.tiles_x; A.tiles_y = g.tiles_y; A.n_buckets = g.n_buckets;
-    A.blocks_per_bucket_side = g.blocks_side; A.buckets_per_rank = g.buckets_per_rank;
-    A.rank = g.rank; A.world = g.world; A.compact = g.world > 1 ? 1 : 0; A.skew_q = g.skew_q;
-    A.out = d_out; A.counters = a->d_counters;
-    A.slice_min_tris = a->knobs.slice_min_tris;
-    const bool forks = a->has_refractive || p->diffuse_rays > 0;
-    // the megakernel comes in two builds: the lean one (diffuse / reflective / constant materials only) and the general one
-    // (template FORKS: + refraction, diffuse GI, textures), so that the lean one does not carry the general one's registers
-    const bool general = forks || !a->scene.textures.empty();
-    // Occlusion queries (is_occluded) may stop at the first hit nearer than the light when no material is transmissive: the
-    // frame is bit-identical (trace.hip.hpp, `exit_t`), only the per-ray work counters shrink.  collect_stats == 1 counts the
-    // reference's work (every ray traced to the end), collect_stats == 2 the work of the production path.
-    A.shadow_exit = (a->knobs.shadow_exit && !a->has_refractive && p->collect_stats != 1) ? 1 : 0;
-    // Likewise an occlusion query whose light contribution is +-0 in every channel is counted in `rays` but not traced
-    // (common.hip.hpp, unlit_query): the same frame and ray count, less work under collect_stats 0 and 2.
-    A.skip_unlit = (a->knobs.skip_unlit_shadow && !a->has_refractive && p->collect_stats != 1) ? 1 : 0;
-    A.occl_on = (a->occl_on && p->collect_stats == 0) ? 1 : 0;
-    A.occl = A.tree;
-    if (A.occl_on) {
-        A.occl.nodes = a->d_occl_nodes; A.occl.leaves = a->d_occl_leaves; A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
-        A.occl.tris = a->d_occl_tris; A.occl.tri_ids = a->d_occl_ids;
-    }
-    RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
-    if (g.world > 1 && g.sample_begin == 0) {
-        // buckets past the end of the frame (padding so that every rank has equal length) stay zero
-        size_t nf = size_t(g.buckets_per_rank) * g.bucket * g.bucket * 3;
-        RTK_HIP(hipMemsetAsync(d_out, 0, nf * sizeof(float), s));
-    }
-    // fork-free scenes (no refraction, no GI) can be rendered by the streaming pipeline (stream.hip)
-    // RTK_TRACE_AUTO for frames: scenes whose ray trees fork (refraction, diffuse GI) go through the streaming pipeline
-    // (all rays of a depth level in parallel); fork-free scenes through the GROUP4 megakernel (fewer launches)
-    // Which of the two wins on a forking scene depends on how much of the frame forks (refractive dragon: pipeline 3x;
-    // a small glass object: megakernel 2x), so RTK_TRACE_AUTO times both on the first frames of a shape and keeps the
-    // faster: frame 1 pipeline, frames 2-3 megakernel (the second one with its cost-feedback order), then the verdict
-    // as soon as the events have completed (hipEventQuery, never a host wait).  Both engines produce the same frame.
-    bool stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
-    hipEvent_t trial_start = nullptr, trial_end = nullptr;
-    if (p->trace_mode == RTK_TRACE_AUTO && forks && !p->collect_stats) {
-        const bool trials = a->knobs.auto_trials;
-        const uint64_t tsig[3] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height), (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
-                                  (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays)};
-        if (std::memcmp(tsig, a->trial_sig, sizeof(tsig)) != 0) { std::memcpy(a->trial_sig, tsig, sizeof(tsig)); a->trial_state = 0; }
-        if (trials) {
-            if (!a->trial_ev[0]) for (auto &e : a->trial_ev) RTK_HIP(hipEventCreate(&e));
-            if (a->trial_state == 3) {                                      // both timed: is the verdict in?
-                float t_stream = 0.f, t_mega = 0.f;
-                if (hipEventQuery(a->trial_ev[1]) == hipSuccess && hipEventQuery(a->trial_ev[3]) == hipSuccess &&
-                    hipEventElapsedTime(&t_stream, a->trial_ev[0], a->trial_ev[1]) == hipSuccess &&
-                    hipEventElapsedTime(&t_mega, a->trial_ev[2], a->trial_ev[3]) == hipSuccess)
-                    a->trial_state = t_mega < t_stream ? 5 : 4;
-                else (void)hipGetLastError();                               // not ready yet: clear the sticky "not ready"
-            }
-            switch (a->trial_state) {
-                case 0: stream = true; trial_start = a->trial_ev[0]; trial_end = a->trial_ev[1]; a->trial_state = 1; break;
-                case 1: stream = false; a->trial_state = 2; break;          // first megakernel frame: records the block costs
-                case 2: stream = false; trial_start = a->trial_ev[2]; trial_end = a->trial_ev[3]; a->trial_state = 3; break;
-                case 5: stream = false; break;
-                default: stream = true; break;                              // 3 (waiting for the events), 4 (pipeline won)
-            }
-        }
-    }
-    // (the streaming pipeline's trial is started behind its workspace allocation, below: tens of GB of hipMalloc in front of the
-    // first frame once made the megakernel "win" config 5's shape at 1.2 s a frame against 0.1)
-    if (trial_start && !stream) RTK_HIP(hipEventRecord(trial_start, s));
-    const bool twopass = p->trace_mode == RTK_TRACE_TWOPASS;
-    if (twopass && p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
-    if (twopass) {
-        const size_t out_pixels = (g.world > 1) ? size_t(g.buckets_per_rank) * g.bucket * g.bucket : size_t(g.width) * g.height;
-        const size_t tiles = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
-        rc = ensure_twopass_ws(a, out_pixels, tiles);
-        if (rc != RTK_OK) return rc;
-        A.prim = a->tp_prim; A.bin_count = a->tp_bins; A.n_listed = a->tp_bins + kCostBins; A.bin_list = a->tp_bin_list;
-        A.tile_order = a->tp_order; A.tile_cap = uint32_t(a->tp_tiles);
-        const hipError_t et = launch_twopass(A, p->collect_stats != 0, general, s);
-        if (et != hipSuccess) return hip_fail(et, "launch two-pass frame");
-    } else if (stream) {
-        const size_t out_pixels = (g.world > 1) ? size_t(g.buckets_per_rank) * g.bucket * g.bucket : size_t(g.width) * g.height;
-        const size_t n_root = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side * 64;
-        // Ray-tree nodes per sample: the camera rays plus room for the secondary rays.  Refractive scenes fork (two
-        // children per interface), so they get more head room; an overflow is caught on the device and the frame
-        // redone by the megakernel.
-        const size_t factor = a->knobs.stream_node_factor > 0 ? size_t(a->knobs.stream_node_factor) : (forks ? 8 : 3);
-        const int n_pass = g.sample_end - g.sample_begin;
-        // Samples per launch (stream.hpp "batch") and batches in flight.  A batch's queues cost ~120 B per ray-tree node: the
-        // batch is as large as the pass, the knob and the memory budget allow (288 GB of HBM is what this design spends).
-        const size_t nodes_per_sample = n_root * factor + 4096;
-        const size_t bytes_per_node = sizeof(dev::RayRec) + sizeof(dev::NodeRes) + sizeof(uint32_t) +
-                                      (sizeof(dev::HitRec) + sizeof(uint32_t) + sizeof(float2) * (a->scene.lights.empty() ? 1 : a->scene.lights.size())) / 2 + 1;
-        // Measured (gpurun_out/r03d-f, hw15/scene2 and hw11/scene8 at the BASELINE sizes): four batches in flight, each a
-        // quarter of the pass, beat both more, smaller launches and fewer, larger ones (1920x1920, 16 samples, no helpers:
-        // 53.1 ms one sample per launch, 47.6 four, 61.6 eight in two lanes; 960x960, 8 samples: 14.4 -> 9.5 ms).
-        const int even = (n_pass + a->knobs.stream_lanes - 1) / a->knobs.stream_lanes;
-        const int want = a->knobs.stream_batch > 0 ? a->knobs.stream_batch : even;
-        int batch = n_pass < want ? n_pass : want;
-        const size_t budget = size_t(a->knobs.stream_mem_gb) << 30;
-        while (batch > 1 && (nodes_per_sample * size_t(batch) > 0xF0000000ull || nodes_per_sample * size_t(batch) * bytes_per_node > budget)) batch -= 1;
-        const int n_launch = (n_pass + batch - 1) / batch;
-        int lanes = n_launch < a->knobs.stream_lanes ? n_launch : a->knobs.stream_lanes;     // batches in flight at once (stream.hpp)
-        while (lanes > 1 && nodes_per_sample * size_t(batch) * bytes_per_node * size_t(lanes) > budget) lanes -= 1;
-        const size_t ws_nodes_before = a->ws_nodes;
-        const int ws_lanes_before = a->ws_lanes;
-        rc = ensure_stream_ws(a, out_pixels, nodes_per_sample * size_t(batch), a->scene.lights.size(), p->spp > 1, lanes);
-        if (rc != RTK_OK) return rc;
-        if (trial_start && (a->ws_nodes != ws_nodes_before || a->ws_lanes != ws_lanes_before)) {
-            // fresh queues: their first use is not what a frame costs -- time the pipeline on the next frame instead
-            trial_start = trial_end = nullptr;
-            a->trial_state = 0;
-        }
-        if (trial_start) RTK_HIP(hipEventRecord(trial_start, s));
-        dev::StreamArgs S;
-        S.r = A; S.r.tree.scalar_surv = a->knobs.stream_scalar_surv ? 1 : 0; S.ws = a->ws;
-        S.key_dirs = p->diffuse_rays > 0 ? 1u : 0u; S.level = 0; S.sample = 0; S.n_batch = 1; S.n_root = uint32_t(n_root); S.n_level0 = uint32_t(n_root); S.auto_min_lanes = a->knobs.auto_min_lanes;
-        S.n_lanes = uint32_t(lanes);
-        for (int j = 0; j < dev::kStreamLanes; ++j) S.lane_overflow[j] = a->ws_lane[j < lanes ? j : 0].ctrl + dev::kCtrlOverflow;
-        // measured on MI355X: the workgroup-cooperative wave walk beats the per-lane walk at every depth, even for the
-        // incoherent rays behind refractive surfaces, so no level switches strategy by default
-        const int deep_level = a->knobs.stream_deep_level, deep_mode = a->knobs.stream_deep_mode;
-        // fork-free trees stay coherent; sorting them would only add launches
-        const int sort_from = a->knobs.stream_sort_from >= 0 ? a->knobs.stream_sort_from : (forks ? 1 : 99);
-        {
-            const DevNode &root = a->tree.dev_nodes[0];
-            for (int k = 0; k < 3; ++k) {
-                const float ext = root.hi[k] - root.lo[k];
-                S.grid_lo[k] = root.lo[k];
-                S.grid_scale[k] = (ext > 0.f && ext < 3.0e38f) ? 16.0f / ext : 0.f;
-            }
-        }
-        S.nodes_sorted = S.hits_sorted = S.bin_children = S.bin_hits = 0;
-        S.user_rays = nullptr; S.user_ids = nullptr; S.user_n = S.user_id0 = S.user_sample = S.user_cull = 0u;
-        // (a radiance batch, possibly on another stream, may still be in these queues: rtk.h, rtk_accel_radiance)
-        if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
-        for (int j = 0; j < lanes; ++j) RTK_HIP(hipMemsetAsync(a->ws_lane[j].ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), s));
-        // fork: lane 0 is the caller's stream, the other lanes wait for everything enqueued on it so far
-        if (lanes > 1) {
-            RTK_HIP(hipEventRecord(a->lane_fork, s));
-            for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork, 0));
-        }
-        for (int i = 0; i < n_launch; ++i) {
-            const int j = i % lanes;
-            S.sample = g.sample_begin + i * batch;
-            S.n_batch = uint32_t(g.sample_end - S.sample < batch ? g.sample_end - S.sample : batch);
-            S.n_level0 = uint32_t(n_root) * S.n_batch;
-            S.ws = a->ws_lane[j];
-            const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
-            const hipEvent_t wait = (lanes > 1 && i > 0) ? a->lane_done[(i - 1) % lanes] : nullptr;
-            const hipEvent_t done = lanes > 1 ? a->lane_done[j] : nullptr;
-            const hipError_t es = launch_stream_sample(S, p->collect_stats != 0, deep_level, deep_mode, sort_from, ls, wait, done,
-                                                       // (side streams help while few rays are in flight: spp 1 16.7 -> 9.1 ms on config 3;
-                                                       // with four lanes the GPU is full already and they cost 20 %)
-                                                       (a->knobs.stream_side && lanes <= 2 && batch * lanes <= a->knobs.stream_side_below) ? &a->lane_side[j] : nullptr,
-                                                       a->knobs.stream_slices > 0 ? a->knobs.stream_slices : a->stream_slices_auto);
-            if (es != hipSuccess) return hip_fail(es, "launch streaming pipeline");
-        }
-        // join: the caller's stream continues behind the last sample of every lane
-        for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j], 0));
-        S.ws = a->ws;
-        // safety net: if any queue overflowed, the megakernel renders the frame again (a no-op otherwise)
-        hipError_t ef = launch_stream_overflow_reset(S, s);
-        if (ef != hipSuccess) return hip_fail(ef, "launch overflow reset");
-        dev::RenderArgs F = A;
-        F.only_if = a->ws.ctrl + dev::kCtrlOverflow;
-        ef = launch_render(F, RTK_TRACE_GROUP4, p->collect_stats != 0, general, s);
-        if (ef != hipSuccess) return hip_fail(ef, "launch fallback k_render");
-        if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
-        RTK_HIP(hipEventRecord(a->ws_done, s));
-        a->ws_in_use = true;
-        if (a->knobs.stream_debug) {
-            uint32_t h[dev::kCtrlWords];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h, a->ws.ctrl, sizeof(h), hipMemcpyDeviceToHost);
-            std::fprintf(stderr, "[rtk stream] node_cap %u hit_cap %u overflow %u; nodes per level:", a->ws.node_cap, a->ws.hit_cap, h[dev::kCtrlOverflow]);
-            for (int l = 0; l <= p->max_ray_depth + 1; ++l) std::fprintf(stderr, " %u", l == 0 ? unsigned(n_root) : h[dev::kCtrlNodeCount + l]);
-            std::fprintf(stderr, "; hits:");
-            for (int l = 0; l <= p->max_ray_depth; ++l) std::fprintf(stderr, " %u", h[dev::kCtrlHitCount + l]);
-            std::fprintf(stderr, "\n");
-        }
-    } else {
-        // Cost feedback: the frame time is set by the few pixel blocks whose rays graze the mesh (hundreds of microseconds
-        // each, against ~3 for a background block).  Started late they are the tail of the frame, so every block reports
-        // its cycle count and the next frame of the same shape starts them most-expensive-first.  Only the launch order
-        // changes: every block is rendered in full, every frame.  RTK_COST_FEEDBACK=0 turns it off.
-        const bool feedback = a->knobs.cost_feedback;
-        const size_t units = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
-        A.n_units = uint32_t(units);
-        // RTK_TRACE_AUTO for frames: workgroup-cooperative leaves.  Four waves per pixel block when there are enough blocks
-        // to fill the chip several times over (the frame is then bound by how many blocks run side by side); eight when
-        // there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block,
-        // and eight waves get through its big leaves faster).  Measured on config 2 (tools/rank_times.py): 32,400 blocks
-        // 0.44 ms (GROUP4) vs 0.87 (GROUP8); 4,050 blocks (one rank of eight) 0.43 vs 0.32.
-        const size_t group8_below = a->knobs.group8_below;
-        const int frame_mode = p->trace_mode != RTK_TRACE_AUTO ? p->trace_mode : (units < group8_below ? RTK_TRACE_GROUP8 : RTK_TRACE_GROUP4);
-        if (feedback && units > 0 && units <= 0x7FFFFFFFull) {
-            const uint64_t sig[4] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height),
-                                     (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
-                                     (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays),
-                                     (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode)};
-            if (a->fb_units < units) {
-                // (capacity, never shrunk; the first allocation also covers the scene's own frame size, so that a small frame
-                // rendered first -- a warm-up -- does not leave three hipMallocs, ~0.1 ms, in front of the first full-size frame)
-                size_t cap = units;
-                {
-                    const uint32_t bk = g.bucket, bs = g.blocks_side;
-                    const uint64_t tx = (uint64_t(a->scene.width > 0 ? a->scene.width : 0) + bk - 1) / bk, ty = (uint64_t(a->scene.height > 0 ? a->scene.height : 0) + bk - 1) / bk;
-                    const uint64_t native = tx * ty * bs * bs;
-                    if (a->fb_units == 0 && native > cap && native <= (1ull << 24)) cap = size_t(native);
-                }
-                (void)hipFree(a->fb_cost); (void)hipFree(a->fb_order); (void)hipFree(a->fb_bins);
-                a->fb_cost = a->fb_order = nullptr; a->fb_bins = nullptr; a->fb_units = 0; a->fb_valid = false; a->fb_order_valid = false;
-                RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_cost), cap * sizeof(uint32_t)));
-                RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_order), (2 * cap + 4 + 8) * sizeof(uint32_t)));   // order, header, workgroup list, prior's counters
-                RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_bins), cap));
-                a->fb_units = cap;
-            }
-            const bool same_shape = a->fb_valid && std::memcmp(sig, a->fb_sig, sizeof(sig)) == 0;
-            if (!same_shape) a->fb_order_valid = false;
-            // The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in for them
-            // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at).
-            // A one-shot render is exactly this frame (the reference CLI renders one, src/main.cpp:13-25).
-            const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0;
-            if (prior) {
-                const hipError_t ep = launch_block_prior(A, a->fb_bins, a->fb_order, a->fb_order + units + 4, a->fb_order + units,
-                                                         reinterpret_cast<uint32_t *>(a->d_counters + kCounterWords), 4u, s);
-                if (ep != hipSuccess) return hip_fail(ep, "launch k_block_prior");
-                A.order_in = a->fb_order; A.order_hdr = a->fb_order + units; A.wg_list = a->fb_order + units + 4;
-            }
-            if (same_shape) {
-                // The order is refreshed from the newest costs every few frames only: the sort is one small workgroup whose
-                // ~28 us sit in front of the frame, and an order that is a few frames old is as good (costs move slowly).
-                const unsigned every = a->knobs.resort_every;
-                if (!a->fb_order_valid || a->fb_age >= every) {
-                    // blocks that cost less than this many cycles (background, a handful of nodes) are packed four to a workgroup
-                    const uint32_t light_cycles = a->knobs.light_cycles;
-                    const bool group_mode = frame_mode == RTK_TRACE_GROUP4;                 // light packing: GROUP4 only
-                    const hipError_t eo = launch_order_by_cost(a->fb_cost, a->fb_bins, a->fb_order, a->fb_order + units + 4, a->fb_order + units,
-                                                               uint32_t(units), group_mode ? light_cycles >> 4 : 0u,
-                                                               a->knobs.order_floor_cycles >> 4, 4u, s);
-                    if (eo != hipSuccess) return hip_fail(eo, "launch k_order_by_cost");
-                    a->fb_order_valid = true;
-                    a->fb_age = 0;
-                    // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
-                    if (!a->fb_nwgs_host) {
-                        RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->fb_nwgs_host), sizeof(uint32_t), hipHostMallocDefault));
-                        RTK_HIP(hipEventCreateWithFlags(&a->fb_nwgs_ev, hipEventDisableTiming));
-                    }
-                    a->fb_nwgs_known = false;
-                    RTK_HIP(hipMemcpyAsync(a->fb_nwgs_host, a->fb_order + units, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    RTK_HIP(hipEventRecord(a->fb_nwgs_ev, s));
-                    a->fb_nwgs_pending = true;
-                }
-                a->fb_age += 1;
-                A.order_in = a->fb_order; A.order_hdr = a->fb_order + units; A.wg_list = a->fb_order + units + 4;
-            }
-            A.cost_out = a->fb_cost;
-            std::memcpy(a->fb_sig, sig, sizeof(sig));
-            a->fb_valid = true;
-        }
-        unsigned n_wgs = 0;
-        if (A.wg_list != nullptr && A.order_in == a->fb_order && a->fb_order_valid) {
-            if (a->fb_nwgs_pending && hipEventQuery(a->fb_nwgs_ev) == hipSuccess) { a->fb_nwgs_pending = false; a->fb_nwgs_known = true; }
-            else if (a->fb_nwgs_pending) (void)hipGetLastError();            // not ready: clear the sticky status
-            if (a->fb_nwgs_known && !a->fb_nwgs_pending) n_wgs = *a->fb_nwgs_host;
-        }
-        const hipError_t e = launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs);
-        if (e != hipSuccess) return hip_fail(e, "launch k_render");
-    }
-    if (trial_end) RTK_HIP(hipEventRecord(trial_end, s));
-    a->last_stream = s;
-    a->last_stats = p->collect_stats != 0;
-    // primary rays of this rank: pixels of its buckets x spp
-    uint64_t pixels = 0;
-    for (uint32_t j = 0; j < g.buckets_per_rank; ++j) {
-        const uint32_t b = dev::rank_bucket(uint32_t(g.rank), j, uint32_t(g.world), g.skew_q);
-        if (b >= g.n_buckets) continue;
-        const uint32_t bx = (b % g.tiles_x) * g.bucket, by = (b / g.tiles_x) * g.bucket;
-        const uint32_t w = (bx + g.bucket <= g.width) ? g.bucket : g.width - bx;
-        const uint32_t h = (by + g.bucket <= g.height) ? g.bucket : g.height - by;
-        pixels += uint64_t(w) * h;
-    }
-    a->last_primary = pixels * uint64_t(g.sample_end - g.sample_begin);
-    return RTK_OK;
-}
-
-int rtk_render_frame_device(rtk_accel *a, const rtk_render_params *p, float *d_out, void *stream) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    std::lock_guard<std::mutex> lock(a->mu);
-    const int rc = ensure_device(a, static_cast<hipStream_t>(stream));
-    if (rc != RTK_OK) return rc;
-    return render_device_impl(a, p, d_out, static_cast<hipStream_t>(stream));
-}
-
-int rtk_render_last_counters(rtk_accel *a, rtk_counters *c) {
-    if (!a || !c) return fail(RTK_ERR_INVALID, "null accel or counters");
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
-    RTK_HIP(hipSetDevice(a->device));
-    RTK_HIP(hipStreamSynchronize(a->last_stream));
-    unsigned long long h[kCounterWords];
-    RTK_HIP(hipMemcpy(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-    std::memset(c, 0, sizeof(*c));
-    for (int i = 0; i < kRayCounterShards; ++i) h[0] += h[8 + i];      // the frame kernel shards its ray counter
-    c->rays = h[0]; c->primary = a->last_primary;
-    if (a->last_stats) { c->hits = h[2]; c->nodes = h[3]; c->boxpass = h[4]; c->leaves = h[5]; c->tris = h[6]; c->packets16 = h[7]; }
-    return RTK_OK;
-}
-
-int rtk_render_last_critical_path(rtk_accel *a, double *ms) {
-    if (!a || !ms) return fail(RTK_ERR_INVALID, "null accel or ms");
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
-    RTK_HIP(hipSetDevice(a->device));
-    RTK_HIP(hipStreamSynchronize(a->last_stream));
-    unsigned long long shard[kRayCounterShards], ticks = 0;
-    RTK_HIP(hipMemcpy(shard, a->d_counters + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
-    for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
-    *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
-    return RTK_OK;
-}
-
-int rtk_render_frame(rtk_accel *a, const rtk_render_params *p, float *rgb, rtk_counters *counters) {
-    if (!a || !p || !rgb) return fail(RTK_ERR_INVALID, "null accel, params or rgb");
-    if (p->world_size > 1) return fail(RTK_ERR_INVALID, "rtk_render_frame renders whole frames; use rtk_render_frame_device for sharded output");
-    size_t nf = 0;
-    int rc = rtk_render_output_floats(a, p, &nf);
-    if (rc != RTK_OK) return rc;
-    {
-        std::lock_guard<std::mutex> lock(a->mu);
-        rc = ensure_device(a);
-        if (rc != RTK_OK) return rc;
-        float *d_out = nullptr;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d_out), nf * sizeof(float)));
-        hipError_t e = hipSuccess;
-        // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
-        if (p->sample_begin > 0) e = hipMemcpy(d_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_out); return hip_fail(e, "upload of the running sums"); }
-        rc = render_device_impl(a, p, d_out, nullptr);
-        if (rc == RTK_OK) e = hipMemcpy(rgb, d_out, nf * sizeof(float), hipMemcpyDeviceToHost);
-        (void)hipFree(d_out);
-        if (rc != RTK_OK) return rc;
-        if (e != hipSuccess) return hip_fail(e, "frame copy");
-    }
-    if (counters) return rtk_render_last_counters(a, counters);
-    return RTK_OK;
-}
-
-int rtk_tiles_assemble_device(const rtk_accel *a, const rtk_render_params *p, const float *d_gathered, float *d_rgb, void *stream) {
-    FrameGeom g;
-    const int rc = frame_geom(a, p, g);
-    if (rc != RTK_OK) return rc;
-    if (!d_gathered || !d_rgb) return fail(RTK_ERR_INVALID, "null buffer");
-    dev::AssembleArgs A;
-    A.gathered = d_gathered; A.rgb = d_rgb; A.width = g.width; A.height = g.height; A.bucket = g.bucket;
-    A.tiles_x = g.tiles_x; A.world = uint32_t(g.world); A.buckets_per_rank = g.buckets_per_rank; A.skew_q = g.skew_q;
-    const hipError_t e = launch_assemble(A, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "launch k_assemble");
-    return RTK_OK;
-}
-
-// ---------------------------------------------------------------- batched radiance
-
-// Rays of one chunk at most: a chunk's ray tree goes through one lane's queues (32-bit node ids, ~120 B per node).
-static constexpr size_t kRadianceChunkRays = size_t(1) << 22;
-
-static int radiance_check(const rtk_accel *a, const void *rays, const void *ids, size_t n, const rtk_radiance_params *p, const void *rgb) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    if (p->trace_mode != RTK_TRACE_AUTO && p->trace_mode != RTK_TRACE_STREAM)
-        return fail(RTK_ERR_INVALID, "trace_mode of a radiance batch must be RTK_TRACE_AUTO or RTK_TRACE_STREAM");
-    if (p->max_ray_depth < 0 || p->max_ray_depth > kMaxRayDepth) return fail(RTK_ERR_INVALID, "max_ray_depth must be in [0, 16]");
-    if (p->diffuse_rays < 0 || p->diffuse_rays > 32767) return fail(RTK_ERR_INVALID, "diffuse_rays must be in [0, 32767]");
-    if (p->sample < 0) return fail(RTK_ERR_INVALID, "sample must be >= 0");
-    if (!std::isfinite(p->shadow_bias) || !std::isfinite(p->reflection_bias) || !std::isfinite(p->refraction_bias))
-        return fail(RTK_ERR_INVALID, "shadow_bias, reflection_bias and refraction_bias must be finite");
-    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many rays for one call");
-    if (n > 0 && (!rays || !rgb)) return fail(RTK_ERR_INVALID, "null ray or colour buffer");
-    if (!ids && n > (size_t(1) << 32)) return fail(RTK_ERR_INVALID, "more than 2^32 rays need explicit ids");
-    return RTK_OK;
-}
-
-// The batch cut into chunks, every chunk one run of the streaming pipeline (level 0 = the chunk's rays) on one of the accel's
-// lanes, followed by its counter fold and its overflow fallback.  Nothing here waits on the host.
-static int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
-                                float *d_rgb, hipStream_t s, uint32_t *n_chunks_out) {
-    dev::RenderArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.tree = tree_view(a);
-    A.materials = a->d_materials; A.lights = a->d_lights;
-    A.textures = a->d_textures; A.tri_uv = a->d_tri_uv; A.tex_pixels = a->d_tex_pixels;
-    A.n_lights = int(a->scene.lights.size());
-    A.has_refractive = a->has_refractive ? 1 : 0;
-    std::memcpy(A.background, a->scene.background, sizeof(A.background));
-    // one colour per ray: "sample 0 of 1" for k_combine, whatever sample the RNG keys name
-    A.spp = 1; A.sample_begin = 0; A.sample_end = 1; A.spp_f = 1.0f;
-    A.max_depth = p->max_ray_depth; A.diffuse_rays = p->diffuse_rays; A.seed = p->seed;
-    A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
-    A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
-    A.world = 1;
-    A.slice_min_tris = a->knobs.slice_min_tris;
-    // as render_device_impl without collect_stats
-    A.shadow_exit = (a->knobs.shadow_exit && !a->has_refractive) ? 1 : 0;
-    A.skip_unlit = (a->knobs.skip_unlit_shadow && !a->has_refractive) ? 1 : 0;
-    A.occl_on = a->occl_on ? 1 : 0;
-    A.occl = A.tree;
-    if (A.occl_on) {
-        A.occl.nodes = a->d_occl_nodes; A.occl.leaves = a->d_occl_leaves; A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
-        A.occl.tris = a->d_occl_tris; A.occl.tri_ids = a->d_occl_ids;
-    }
-    const bool forks = a->has_refractive || p->diffuse_rays > 0;
-    // chunk size and lanes: the rule of STREAM frames (render_device_impl) with a chunk in the place of a sample
-    const size_t factor = a->knobs.stream_node_factor > 0 ? size_t(a->knobs.stream_node_factor) : (forks ? 8 : 3);
-    const size_t bytes_per_node = sizeof(dev::RayRec) + sizeof(dev::NodeRes) + sizeof(uint32_t) +
-                                  (sizeof(dev::HitRec) + sizeof(uint32_t) + sizeof(float2) * (a->scene.lights.empty() ? 1 : a->scene.lights.size())) / 2 + 1;
-    const size_t budget = size_t(a->knobs.stream_mem_gb) << 30;
-    const size_t n64 = (n + 63) / 64 * 64;
-    size_t chunk = n64 < kRadianceChunkRays ? n64 : kRadianceChunkRays;
-    auto fits = [&](size_t c, size_t l) { return c * factor + 4096 <= 0xF0000000ull && (c * factor + 4096) * bytes_per_node * l <= budget; };
-    // a batch that has to be cut for the budget is cut so that every lane gets queues: the chunks then overlap as a frame's samples do
-    if (!fits(chunk, 1)) while (chunk > 64 && !fits(chunk, size_t(a->knobs.stream_lanes))) chunk = (chunk / 2 + 63) / 64 * 64;
-    const size_t nodes = chunk * factor + 4096;
-    const size_t n_chunks = (n + chunk - 1) / chunk;
-    int lanes = n_chunks < size_t(a->knobs.stream_lanes) ? int(n_chunks) : a->knobs.stream_lanes;
-    while (lanes > 1 && !fits(chunk, size_t(lanes))) lanes -= 1;
-    if (n_chunks_out) *n_chunks_out = uint32_t(n_chunks);
-    int rc = ensure_stream_ws(a, 0, nodes, a->scene.lights.size(), false, lanes);
-    if (rc != RTK_OK) return rc;
-    unsigned long long *total = nullptr;
-    {
-        const size_t words = size_t(dev::kStreamLanes) * kCounterWords + 2;
-        if (!a->d_rad_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_rad_counters), words * sizeof(unsigned long long)));
-        total = a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords;
-    }
-    // the queues belong to the accel: whoever used them last (a STREAM frame, a batch on another stream) finishes first, on the device
-    if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
-    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
-    a->ws_in_use = true;
-    RTK_HIP(hipMemsetAsync(total, 0, 2 * sizeof(unsigned long long), s));
-
-    dev::StreamArgs S;
-    std::memset(&S, 0, sizeof(S));
-    S.r = A; S.r.tree.scalar_surv = a->knobs.stream_scalar_surv ? 1 : 0;
-    S.key_dirs = p->diffuse_rays > 0 ? 1u : 0u; S.sample = 0; S.n_batch = 1; S.auto_min_lanes = a->knobs.auto_min_lanes;
-    S.n_lanes = 1;                                       // a chunk is judged on its own overflow word (k_combine, depth 0)
-    S.user_sample = uint32_t(p->sample); S.user_cull = p->cull ? 1u : 0u;
-    const int deep_level = a->knobs.stream_deep_level, deep_mode = a->knobs.stream_deep_mode;
-    const int sort_from = a->knobs.stream_sort_from >= 0 ? a->knobs.stream_sort_from : (forks ? 1 : 99);
-    {
-        const DevNode &root = a->tree.dev_nodes[0];
-        for (int k = 0; k < 3; ++k) {
-            const float ext = root.hi[k] - root.lo[k];
-            S.grid_lo[k] = root.lo[k];
-            S.grid_scale[k] = (ext > 0.f && ext < 3.0e38f) ? 16.0f / ext : 0.f;
-        }
-    }
-    if (lanes > 1) {
-        RTK_HIP(hipEventRecord(a->lane_fork, s));
-        for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork, 0));
-    }
-    const bool side = a->knobs.stream_side && lanes <= 2 && lanes <= a->knobs.stream_side_below;
-    for (size_t i = 0; i < n_chunks; ++i) {
-        const int j = int(i % size_t(lanes));
-        const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
-        const size_t first = i * chunk, cn = n - first < chunk ? n - first : chunk;
-        S.ws = a->ws_lane[j];
-        for (int k = 0; k < dev::kStreamLanes; ++k) S.lane_overflow[k] = S.ws.ctrl + dev::kCtrlOverflow;
-        S.user_rays = d_rays + first; S.user_ids = d_ids ? d_ids + first : nullptr;
-        S.user_n = uint32_t(cn); S.user_id0 = uint32_t(first);
-        S.n_root = uint32_t((cn + 63) / 64 * 64); S.n_level0 = S.n_root;
-        S.r.out = d_rgb + first * 3;
-        S.r.counters = a->d_rad_counters + size_t(j) * kCounterWords;
-        RTK_HIP(hipMemsetAsync(S.ws.ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), ls));      // the overflow word included: it is the chunk's
-        RTK_HIP(hipMemsetAsync(S.r.counters, 0, kCounterWords * sizeof(unsigned long long), ls));
-        hipError_t e = launch_stream_sample(S, false, deep_level, deep_mode, sort_from, ls, nullptr, nullptr, side ? &a->lane_side[j] : nullptr,
-                                            a->knobs.stream_slices > 0 ? a->knobs.stream_slices : a->stream_slices_auto);
-        if (e == hipSuccess) e = launch_radiance_fold(S, total, ls);
-        if (e == hipSuccess) e = launch_radiance_fallback(S, total, ls);
-        if (e != hipSuccess) return hip_fail(e, "launch radiance chunk");
-        if (j != 0) RTK_HIP(hipEventRecord(a->lane_done[j], ls));
-    }
-    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j], 0));
-    RTK_HIP(hipEventRecord(a->ws_done, s));
-    return RTK_OK;
-}
-
-int rtk_accel_radiance_device(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
-                              float *d_rgb, void *stream) {
-    int rc = radiance_check(a, d_rays, d_ids, n, p, d_rgb);
-    if (rc != RTK_OK) return rc;
-    if (n == 0) return RTK_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    rc = ensure_device(a, static_cast<hipStream_t>(stream));
-    if (rc != RTK_OK) return rc;
-    return radiance_device_impl(a, d_rays, d_ids, n, p, d_rgb, static_cast<hipStream_t>(stream), nullptr);
-}
-
-int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, size_t n, const rtk_radiance_params *p, float *rgb,
-                       rtk_counters *counters) {
-    int rc = radiance_check(a, rays, ids, n, p, rgb);
-    if (rc != RTK_OK) return rc;
-    if (n == 0) {
-        if (counters) std::memset(counters, 0, sizeof(*counters));
-        return RTK_OK;
-    }
-    std::lock_guard<std::mutex> lock(a->mu);
-    rc = ensure_device(a);
-    if (rc != RTK_OK) return rc;
-    if (a->rad_cap < n) {
-        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb);
-        a->rad_rays = nullptr; a->rad_ids = nullptr; a->rad_rgb = nullptr; a->rad_cap = 0;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rays), n * sizeof(rtk_ray)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_ids), n * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rgb), n * 3 * sizeof(float)));
-        a->rad_cap = n;
-    }
-    RTK_HIP(hipMemcpy(a->rad_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-    if (ids) RTK_HIP(hipMemcpy(a->rad_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    uint32_t n_chunks = 0;
-    rc = radiance_device_impl(a, a->rad_rays, ids ? a->rad_ids : nullptr, n, p, a->rad_rgb, nullptr, &n_chunks);
-    if (rc != RTK_OK) return rc;
-    RTK_HIP(hipMemcpy(rgb, a->rad_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    unsigned long long h[2] = {0, 0};
-    RTK_HIP(hipMemcpy(h, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
-    if (counters) {
-        std::memset(counters, 0, sizeof(*counters));
-        counters->rays = h[0]; counters->primary = n;
-    }
-    if (a->knobs.stream_debug)
-        std::fprintf(stderr, "[rtk radiance] rays %zu chunks %u redone %llu node_cap %u\n", n, n_chunks, h[1], a->ws.node_cap);
-    return RTK_OK;
-}
-
-// ---------------------------------------------------------------- camera rays
-
-static int camera_args(rtk_accel *a, const rtk_render_params *p, int32_t sample, dev::RenderArgs &A) {
-    FrameGeom g;
-    const int rc = frame_geom(a, p, g);
-    if (rc != RTK_OK) return rc;
-    if (sample < 0 || sample >= p->spp) return fail(RTK_ERR_INVALID, "sample must be in [0, spp)");
-    std::memset(&A, 0, sizeof(A));
-    std::memcpy(A.cam_pos, a->scene.cam_pos, sizeof(A.cam_pos));
-    std::memcpy(A.cam_mat, a->scene.cam_mat, sizeof(A.cam_mat));
-    A.width = g.width; A.height = g.height;
-    A.aspect = static_cast<float>(g.width) / static_cast<float>(g.height);
-    A.tan_half_fov = std::tan(static_cast<float>(p->fov_degrees * (3.14159265358979323846 / 180.0)) / 2.0f);   // as render_device_impl
-    A.spp = p->spp; A.seed = p->seed;
-    A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height); A.spp_f = static_cast<float>(p->spp);
-    return RTK_OK;
-}
-
-int rtk_camera_rays_device(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *d_rays, void *stream) {
-    if (!a || !p || !d_rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
-    std::lock_guard<std::mutex> lock(a->mu);
-    int rc = ensure_device(a);
-    if (rc != RTK_OK) return rc;
-    dev::RenderArgs A;
-    if ((rc = camera_args(a, p, sample, A)) != RTK_OK) return rc;
-    const hipError_t e = launch_camera_rays(A, sample, d_rays, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "launch k_camera_rays");
-    return RTK_OK;
-}
-
-int rtk_camera_rays(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *rays) {
-    if (!a || !p || !rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
-    FrameGeom g;
-    int rc = frame_geom(a, p, g);
-    if (rc != RTK_OK) return rc;
-    const size_t n = size_t(g.width) * g.height;
-    rtk_ray *d = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(a->mu);
-        if ((rc = ensure_device(a)) != RTK_OK) return rc;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(rtk_ray)));
-    }
-    rc = rtk_camera_rays_device(a, p, sample, d, nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == RTK_OK) e = hipMemcpy(rays, d, n * sizeof(rtk_ray), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc != RTK_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "camera ray copy");
-    return RTK_OK;
-}
-
 // ---------------------------------------------------------------- image out
 
 int rtk_format_ppm(const float *rgb, int32_t width, int32_t height, char *buf, size_t cap, size_t *n) {
@@ -1909,8 +380,7 @@ int rtk_format_ppm(const float *rgb, int32_t width, int32_t height, char *buf, s
 int rtk_frame_to_rgb8_device(const float *d_rgb, size_t n, uint8_t *d_out, void *stream) {
     if (n > 0 && (!d_rgb || !d_out)) return fail(RTK_ERR_INVALID, "null buffer");
     if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many values for one launch");
-    const hipError_t e = launch_to_rgb8(d_rgb, n, d_out, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "launch k_to_rgb8");
+    RTK_HIP_AS(launch_to_rgb8(d_rgb, n, d_out, static_cast<hipStream_t>(stream)), "launch k_to_rgb8");
     return RTK_OK;
 }
 

@@ -1,0 +1,723 @@
+// C-ABI, everything that shades: frames, the radiance batch (the streaming pipeline's second client) and camera rays.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+
+#include "accel.hpp"
+#include "stream_plan.hpp"
+
+namespace rtk {
+
+int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    const int64_t w = p->width > 0 ? p->width : a->scene.width;
+    const int64_t h = p->height > 0 ? p->height : a->scene.height;
+    if (w <= 0 || h <= 0 || w > 65536 || h > 65536) return fail(RTK_ERR_INVALID, "image size must be in [1, 65536]");
+    if (p->spp < 1) return fail(RTK_ERR_INVALID, "spp must be >= 1");
+    if (p->max_ray_depth < 0 || p->max_ray_depth > kMaxRayDepth)
+        return fail(RTK_ERR_INVALID, "max_ray_depth must be in [0, 16]");
+    if (p->diffuse_rays < 0 || p->diffuse_rays > 32767) return fail(RTK_ERR_INVALID, "diffuse_rays must be in [0, 32767]");
+    if (!valid_frame_mode(p->trace_mode)) return fail(RTK_ERR_INVALID, "unknown trace_mode");
+    if (p->sample_begin < 0 || p->sample_count < 0 || p->sample_begin >= p->spp ||
+        int64_t(p->sample_begin) + p->sample_count > p->spp)
+        return fail(RTK_ERR_INVALID, "sample_begin / sample_count must select samples inside [0, spp)");
+    if (p->sample_count == 0 && p->sample_begin != 0) return fail(RTK_ERR_INVALID, "sample_count == 0 means all samples: sample_begin must be 0");
+    g.sample_begin = p->sample_begin;
+    g.sample_end = p->sample_count == 0 ? p->spp : p->sample_begin + p->sample_count;
+    g.world = p->world_size > 1 ? p->world_size : 1;
+    g.rank = p->world_size > 1 ? p->rank : 0;
+    if (g.rank < 0 || g.rank >= g.world) return fail(RTK_ERR_INVALID, "rank must be in [0, world_size)");
+    g.width = uint32_t(w); g.height = uint32_t(h);
+    g.bucket = uint32_t(a->scene.bucket_size > 0 ? a->scene.bucket_size : 64);
+    g.tiles_x = (g.width + g.bucket - 1) / g.bucket;
+    g.tiles_y = (g.height + g.bucket - 1) / g.bucket;
+    g.n_buckets = g.tiles_x * g.tiles_y;
+    g.blocks_side = (g.bucket + 7) / 8;
+    g.buckets_per_rank = (g.n_buckets + uint32_t(g.world) - 1) / uint32_t(g.world);
+    g.skew_q = (g.world > 1 && g.tiles_x % uint32_t(g.world) == 0u) ? g.tiles_x / uint32_t(g.world) : 0u;
+    return RTK_OK;
+}
+
+namespace {
+
+// The streams the streaming pipeline's lanes (and their k_shadow side kernels) run on belong to the PROCESS and are made once
+// per device, in the order the first accel needs them: made per accel, a second accel's lanes shared hardware queues.
+struct LaneStreams {
+    hipStream_t lane[rtk::dev::kStreamLanes] = {};
+    hipStream_t side[rtk::dev::kStreamLanes][2] = {};
+};
+std::mutex g_lane_mu;
+LaneStreams g_lane_streams[16];
+
+hipError_t lane_streams_for(int device, int lanes, LaneStreams **out) {
+    if (device < 0 || device >= 16) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lock(g_lane_mu);
+    LaneStreams &L = g_lane_streams[device];
+    for (int j = 0; j < lanes && j < rtk::dev::kStreamLanes; ++j) {
+        hipError_t e = hipSuccess;
+        if (j > 0 && !L.lane[j]) e = hipStreamCreateWithFlags(&L.lane[j], hipStreamNonBlocking);
+        for (int par = 0; par < 2 && e == hipSuccess; ++par)
+            if (!L.side[j][par]) e = hipStreamCreateWithFlags(&L.side[j][par], hipStreamNonBlocking);
+        if (e != hipSuccess) return e;
+    }
+    *out = &L;
+    return hipSuccess;
+}
+
+}  // namespace
+
+void free_stream_ws(rtk_accel *a) {
+    (void)hipFree(a->ws.sumbuf);
+    for (int j = 0; j < dev::kStreamLanes; ++j) {
+        dev::StreamWs &w = a->ws_lane[j];
+        (void)hipFree(w.rays); (void)hipFree(w.nodes); (void)hipFree(w.hits); (void)hipFree(w.contrib); (void)hipFree(w.ctrl);
+        (void)hipFree(w.node_bins); (void)hipFree(w.hit_bins); (void)hipFree(w.node_order); (void)hipFree(w.hit_order);
+        w = dev::StreamWs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};
+    }
+    a->ws = a->ws_lane[0];
+    a->ws_lanes = 0; a->ws_pixels = 0; a->ws_nodes = 0; a->ws_lights = 0; a->ws_sum = false;
+}
+
+// (Re)allocates the streaming workspace for `pixels` output pixels.  Allocation synchronises the device, so it only
+// happens when a larger frame (or more lights / multi-sample) is requested than ever before on this accel.
+int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes) {
+    if (lights == 0) lights = 1;
+    if (lanes < 1) lanes = 1;
+    if (pixels <= a->ws_pixels && nodes <= a->ws_nodes && lights <= a->ws_lights && (!need_sum || a->ws_sum) && lanes <= a->ws_lanes) return RTK_OK;
+    const size_t np = pixels > a->ws_pixels ? pixels : a->ws_pixels;
+    const size_t nn = nodes > a->ws_nodes ? nodes : a->ws_nodes;
+    const size_t nl = lights > a->ws_lights ? lights : a->ws_lights;
+    const int nlanes = lanes > a->ws_lanes ? lanes : a->ws_lanes;
+    const bool sum = need_sum || a->ws_sum;
+    if (nn > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "frame too large for the streaming pipeline's 32-bit node ids");
+    RTK_HIP(hipDeviceSynchronize());
+    free_stream_ws(a);
+    const size_t nh = nn / 2 + 64;                            // every shading point belongs to a distinct node
+    float *sumbuf = nullptr;
+    if (sum) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&sumbuf), np * 3 * sizeof(float)));
+    for (int j = 0; j < nlanes; ++j) {
+        dev::StreamWs &w = a->ws_lane[j];
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.rays), nn * sizeof(dev::RayRec)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.nodes), nn * sizeof(dev::NodeRes)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hits), nh * sizeof(dev::HitRec)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.contrib), nh * nl * sizeof(float2)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.ctrl), dev::kCtrlWords * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_bins), dev::kSortBins * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_bins), dev::kSortBins * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_order), nn * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_order), nh * sizeof(uint32_t)));
+        w.sumbuf = sumbuf;
+        w.node_cap = uint32_t(nn); w.hit_cap = uint32_t(nh);
+        if (!a->lane_done[j]) RTK_HIP(hipEventCreateWithFlags(&a->lane_done[j], hipEventDisableTiming));
+        for (int par = 0; par < 2; ++par) {
+            if (!a->lane_side[j].ready[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].ready[par], hipEventDisableTiming));
+            if (!a->lane_side[j].done[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].done[par], hipEventDisableTiming));
+        }
+    }
+    if (!a->lane_fork) RTK_HIP(hipEventCreateWithFlags(&a->lane_fork, hipEventDisableTiming));
+    LaneStreams *L = nullptr;                // the process's lane streams (see LaneStreams); the events that order them stay this accel's own
+    RTK_HIP(lane_streams_for(a->device, nlanes, &L));
+    for (int j = 0; j < nlanes; ++j) {
+        a->lane_stream[j] = L->lane[j];
+        a->lane_side[j].stream[0] = L->side[j][0]; a->lane_side[j].stream[1] = L->side[j][1];
+    }
+    a->ws = a->ws_lane[0];
+    a->ws_lanes = nlanes; a->ws_pixels = np; a->ws_nodes = nn; a->ws_lights = nl; a->ws_sum = sum;
+    return RTK_OK;
+}
+
+namespace {
+
+int ensure_twopass_ws(rtk_accel *a, size_t pixels, size_t tiles) {
+    if (pixels <= a->tp_pixels && tiles <= a->tp_tiles) return RTK_OK;
+    const size_t np = pixels > a->tp_pixels ? pixels : a->tp_pixels, nt = tiles > a->tp_tiles ? tiles : a->tp_tiles;
+    RTK_HIP(hipDeviceSynchronize());
+    (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
+    a->tp_prim = nullptr; a->tp_bins = nullptr; a->tp_bin_list = nullptr; a->tp_order = nullptr;
+    a->tp_pixels = 0; a->tp_tiles = 0;
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_prim), np * sizeof(float4)));
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bins), (kCostBins + 1) * sizeof(uint32_t)));
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bin_list), size_t(kCostBins) * nt * sizeof(uint32_t)));
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_order), nt * sizeof(uint32_t)));
+    a->tp_pixels = np; a->tp_tiles = nt;
+    return RTK_OK;
+}
+
+// output pixels of this rank: the whole frame, or its buckets (padded so that every rank has equal length) of a sharded one
+size_t out_pixels(const FrameGeom &g) {
+    return g.world > 1 ? size_t(g.buckets_per_rank) * g.bucket * g.bucket : size_t(g.width) * g.height;
+}
+
+// primary rays of this rank: pixels of its buckets x samples of this call
+uint64_t primary_rays_of_rank(const FrameGeom &g) {
+    uint64_t pixels = 0;
+    for (uint32_t j = 0; j < g.buckets_per_rank; ++j) {
+        const uint32_t b = dev::rank_bucket(uint32_t(g.rank), j, uint32_t(g.world), g.skew_q);
+        if (b >= g.n_buckets) continue;
+        const uint32_t bx = (b % g.tiles_x) * g.bucket, by = (b / g.tiles_x) * g.bucket;
+        const uint32_t w = (bx + g.bucket <= g.width) ? g.bucket : g.width - bx;
+        const uint32_t h = (by + g.bucket <= g.height) ? g.bucket : g.height - by;
+        pixels += uint64_t(w) * h;
+    }
+    return pixels * uint64_t(g.sample_end - g.sample_begin);
+}
+
+// What a frame and a radiance batch share: zeroed arguments with the scene as the device holds it and the way occlusion
+// queries are answered.  `stats_mode`: rtk_render_params.collect_stats; a radiance batch passes 0.
+dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
+    dev::RenderArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.tree = tree_view(a);
+    A.materials = a->d_materials; A.lights = a->d_lights;
+    A.textures = a->d_textures; A.tri_uv = a->d_tri_uv; A.tex_pixels = a->d_tex_pixels;
+    A.n_lights = int(a->scene.lights.size());
+    A.has_refractive = a->has_refractive ? 1 : 0;
+    std::memcpy(A.background, a->scene.background, sizeof(A.background));
+    A.slice_min_tris = a->knobs.slice_min_tris;
+    // Occlusion queries (is_occluded) may stop at the first hit nearer than the light when no material is transmissive: the
+    // frame is bit-identical (trace.hip.hpp, `exit_t`), only the per-ray work counters shrink.  collect_stats == 1 counts the
+    // reference's work (every ray traced to the end), collect_stats == 2 the work of the production path.
+    A.shadow_exit = (a->knobs.shadow_exit && !a->has_refractive && stats_mode != 1) ? 1 : 0;
+    // Likewise an occlusion query whose light contribution is +-0 in every channel is counted in `rays` but not traced
+    // (common.hip.hpp, unlit_query): the same frame and ray count, less work under collect_stats 0 and 2.
+    A.skip_unlit = (a->knobs.skip_unlit_shadow && !a->has_refractive && stats_mode != 1) ? 1 : 0;
+    A.occl_on = (a->occl_on && stats_mode == 0) ? 1 : 0;
+    A.occl = A.tree;
+    if (A.occl_on) {
+        A.occl.nodes = a->d_occl_nodes; A.occl.leaves = a->d_occl_leaves; A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
+        A.occl.tris = a->d_occl_tris; A.occl.tri_ids = a->d_occl_ids;
+    }
+    return A;
+}
+
+// the camera half: what k_camera_rays and the frame kernels make camera rays from
+void camera_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A) {
+    std::memcpy(A.cam_pos, a->scene.cam_pos, sizeof(A.cam_pos));
+    std::memcpy(A.cam_mat, a->scene.cam_mat, sizeof(A.cam_mat));
+    A.width = g.width; A.height = g.height;
+    A.aspect = static_cast<float>(g.width) / static_cast<float>(g.height);                    // render.hpp:26
+    // render.hpp:55-57: `const F fov_radians = degrees_to_radians(fov_degrees)` is evaluated in double (fov_degrees is a
+    // double constant, utils/convert.hpp:4-6) and ROUNDED TO FLOAT by the declaration; `std::tan(fov_radians / F(2))` is
+    // then the float overload (tanf), and `screen_x *=` a float multiply (common.hip.hpp camera_ray).
+    const float fov_radians = static_cast<float>(p->fov_degrees * (3.14159265358979323846 / 180.0));
+    A.tan_half_fov = std::tan(fov_radians / 2.0f);
+    A.spp = p->spp; A.seed = p->seed;
+    A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height); A.spp_f = static_cast<float>(p->spp);
+}
+
+// ---------------------------------------------------------------- the streaming pipeline's setup, for both of its clients
+
+struct StreamSetup {
+    dev::StreamArgs S;
+    int deep_level, deep_mode, sort_from, slices;      // launch_stream_sample's
+    size_t factor, node_bytes, budget;                 // stream_plan.hpp's
+};
+
+// Zeroed StreamArgs with what does not depend on the client: a frame and a radiance chunk then set only what is theirs.
+StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffuse_rays, bool forks) {
+    StreamSetup u = {};
+    u.S.r = A; u.S.r.tree.scalar_surv = a->knobs.stream_scalar_surv ? 1 : 0;
+    u.S.key_dirs = diffuse_rays > 0 ? 1u : 0u; u.S.n_batch = 1; u.S.auto_min_lanes = a->knobs.auto_min_lanes;
+    const DevNode &root = a->tree.dev_nodes[0];
+    for (int k = 0; k < 3; ++k) {
+        const float ext = root.hi[k] - root.lo[k];
+        u.S.grid_lo[k] = root.lo[k];
+        u.S.grid_scale[k] = (ext > 0.f && ext < 3.0e38f) ? 16.0f / ext : 0.f;
+    }
+    // measured on MI355X: the workgroup-cooperative wave walk beats the per-lane walk at every depth, even for the
+    // incoherent rays behind refractive surfaces, so no level switches strategy by default
+    u.deep_level = a->knobs.stream_deep_level; u.deep_mode = a->knobs.stream_deep_mode;
+    // fork-free trees stay coherent; sorting them would only add launches
+    u.sort_from = a->knobs.stream_sort_from >= 0 ? a->knobs.stream_sort_from : (forks ? 1 : 99);
+    u.slices = a->knobs.stream_slices > 0 ? a->knobs.stream_slices : a->stream_slices_auto;
+    // Ray-tree nodes per level-0 ray: the ray itself plus room for the secondary rays.  Refractive scenes fork (two children per
+    // interface), so they get more head room; an overflow is caught on the device and the frame (the chunk) redone by the fallback.
+    u.factor = a->knobs.stream_node_factor > 0 ? size_t(a->knobs.stream_node_factor) : (forks ? 8 : 3);
+    u.node_bytes = stream_bytes_per_node(sizeof(dev::RayRec), sizeof(dev::NodeRes), sizeof(dev::HitRec), sizeof(float2), a->scene.lights.size());
+    u.budget = size_t(a->knobs.stream_mem_gb) << 30;
+    return u;
+}
+
+// the queues belong to the accel: whoever used them last (a STREAM frame, a batch on another stream) finishes first, on the device
+int claim_stream_ws(rtk_accel *a, hipStream_t s) {
+    if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
+    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
+    a->ws_in_use = true;
+    return RTK_OK;
+}
+int release_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(hipEventRecord(a->ws_done, s)); return RTK_OK; }
+
+// fork: lane 0 is the caller's stream, the other lanes wait for everything enqueued on it so far
+int fork_lanes(rtk_accel *a, int lanes, hipStream_t s) {
+    if (lanes > 1) RTK_HIP(hipEventRecord(a->lane_fork, s));
+    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork, 0));
+    return RTK_OK;
+}
+// join: the caller's stream continues behind the last launch of every lane
+int join_lanes(rtk_accel *a, int lanes, hipStream_t s) {
+    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j], 0));
+    return RTK_OK;
+}
+
+// fresh queues: their first use is not what a frame costs -- time the pipeline on the next frame instead
+void trial_abandon(rtk_accel *a, hipEvent_t trial[2]) { trial[0] = trial[1] = nullptr; a->trial_state = 0; }
+
+// RTK_TRACE_AUTO for frames: fork-free scenes go through the GROUP4 megakernel; on scenes whose ray
+// trees fork (refraction, diffuse GI) which engine wins depends on how much of the frame forks, so both are timed on the first
+// frames of a shape: frame 1 pipeline, frames 2-3 megakernel (the second one with its cost-feedback order), then the verdict as
+// soon as the events have completed (hipEventQuery, never a host wait).  `trial`: {start, end} to record around the engine, or null.
+int choose_engine(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, bool forks, bool &stream, hipEvent_t trial[2]) {
+    stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
+    if (p->trace_mode == RTK_TRACE_AUTO && forks && !p->collect_stats) {
+        const uint64_t tsig[3] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height), (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
+                                  (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays)};
+        if (std::memcmp(tsig, a->trial_sig, sizeof(tsig)) != 0) { std::memcpy(a->trial_sig, tsig, sizeof(tsig)); a->trial_state = 0; }
+        if (a->knobs.auto_trials) {
+            if (!a->trial_ev[0]) for (auto &e : a->trial_ev) RTK_HIP(hipEventCreate(&e));
+            if (a->trial_state == 3) {                                      // both timed: is the verdict in?
+                float t_stream = 0.f, t_mega = 0.f;
+                if (hipEventQuery(a->trial_ev[1]) == hipSuccess && hipEventQuery(a->trial_ev[3]) == hipSuccess &&
+                    hipEventElapsedTime(&t_stream, a->trial_ev[0], a->trial_ev[1]) == hipSuccess &&
+                    hipEventElapsedTime(&t_mega, a->trial_ev[2], a->trial_ev[3]) == hipSuccess)
+                    a->trial_state = t_mega < t_stream ? 5 : 4;
+                else (void)hipGetLastError();                               // not ready yet: clear the sticky "not ready"
+            }
+            switch (a->trial_state) {
+                case 0: stream = true; trial[0] = a->trial_ev[0]; trial[1] = a->trial_ev[1]; a->trial_state = 1; break;
+                case 1: stream = false; a->trial_state = 2; break;          // first megakernel frame: records the block costs
+                case 2: stream = false; trial[0] = a->trial_ev[2]; trial[1] = a->trial_ev[3]; a->trial_state = 3; break;
+                case 5: stream = false; break;
+                default: stream = true; break;                              // 3 (waiting for the events), 4 (pipeline won)
+            }
+        }
+    }
+    return RTK_OK;
+}
+
+int render_twopass(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general, hipStream_t s) {
+    if (p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
+    const size_t tiles = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
+    RTK_TRY(ensure_twopass_ws(a, out_pixels(g), tiles));
+    A.prim = a->tp_prim; A.bin_count = a->tp_bins; A.n_listed = a->tp_bins + kCostBins; A.bin_list = a->tp_bin_list;
+    A.tile_order = a->tp_order; A.tile_cap = uint32_t(a->tp_tiles);
+    RTK_HIP_AS(launch_twopass(A, p->collect_stats != 0, general, s), "launch two-pass frame");
+    return RTK_OK;
+}
+
+// `trial[0]` is recorded here, behind the workspace allocation, which is not what a frame costs.
+int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const dev::RenderArgs &A, bool forks, bool general,
+                  hipEvent_t trial[2], hipStream_t s) {
+    StreamSetup u = stream_args(a, A, p->diffuse_rays, forks);
+    const size_t n_root = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side * 64;
+    const size_t nodes_per_sample = n_root * u.factor + 4096;
+    const FramePlan plan = plan_frame_batches(g.sample_end - g.sample_begin, nodes_per_sample, u.node_bytes, u.budget,
+                                              a->knobs.stream_lanes, a->knobs.stream_batch);
+    const int batch = plan.batch, lanes = plan.lanes;
+    const size_t ws_nodes_before = a->ws_nodes;
+    const int ws_lanes_before = a->ws_lanes;
+    RTK_TRY(ensure_stream_ws(a, out_pixels(g), nodes_per_sample * size_t(batch), a->scene.lights.size(), p->spp > 1, lanes));
+    if (trial[0] && (a->ws_nodes != ws_nodes_before || a->ws_lanes != ws_lanes_before)) trial_abandon(a, trial);
+    if (trial[0]) RTK_HIP(hipEventRecord(trial[0], s));
+    dev::StreamArgs &S = u.S;
+    S.ws = a->ws; S.n_root = uint32_t(n_root); S.n_level0 = uint32_t(n_root);
+    // overflow words: a frame is judged on those of all its lanes (unused slots point at lane 0's)
+    S.n_lanes = uint32_t(lanes);
+    for (int j = 0; j < dev::kStreamLanes; ++j) S.lane_overflow[j] = a->ws_lane[j < lanes ? j : 0].ctrl + dev::kCtrlOverflow;
+    RTK_TRY(claim_stream_ws(a, s));
+    // ctrl: a frame zeroes all its lanes' on the caller's stream, before the fork
+    for (int j = 0; j < lanes; ++j) RTK_HIP(hipMemsetAsync(a->ws_lane[j].ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), s));
+    RTK_TRY(fork_lanes(a, lanes, s));
+    // side streams: while few SAMPLES are in flight (a radiance batch counts chunks).  They help while few rays are in flight:
+    // spp 1 16.7 -> 9.1 ms on config 3; with four lanes the GPU is full already and they cost 20 %
+    const bool side = a->knobs.stream_side && lanes <= 2 && batch * lanes <= a->knobs.stream_side_below;
+    for (int i = 0; i < plan.n_launch; ++i) {
+        const int j = i % lanes;
+        S.sample = g.sample_begin + i * batch;
+        S.n_batch = uint32_t(g.sample_end - S.sample < batch ? g.sample_end - S.sample : batch);
+        S.n_level0 = uint32_t(n_root) * S.n_batch;
+        S.ws = a->ws_lane[j];
+        const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
+        // ordering events: the depth-0 k_combine of a batch waits for the previous batch's, so the pixel sums stay in sample order
+        const hipEvent_t wait = (lanes > 1 && i > 0) ? a->lane_done[(i - 1) % lanes] : nullptr;
+        const hipEvent_t done = lanes > 1 ? a->lane_done[j] : nullptr;
+        RTK_HIP_AS(launch_stream_sample(S, p->collect_stats != 0, u.deep_level, u.deep_mode, u.sort_from, ls, wait, done,
+                                        side ? &a->lane_side[j] : nullptr, u.slices), "launch streaming pipeline");
+    }
+    RTK_TRY(join_lanes(a, lanes, s));
+    S.ws = a->ws;
+    // tail: the safety net -- if any queue overflowed, the megakernel renders the frame again (a no-op otherwise)
+    RTK_HIP_AS(launch_stream_overflow_reset(S, s), "launch overflow reset");
+    dev::RenderArgs F = A;
+    F.only_if = a->ws.ctrl + dev::kCtrlOverflow;
+    RTK_HIP_AS(launch_render(F, RTK_TRACE_GROUP4, p->collect_stats != 0, general, s), "launch fallback k_render");
+    RTK_TRY(release_stream_ws(a, s));
+    if (a->knobs.stream_debug) {
+        uint32_t h[dev::kCtrlWords];
+        (void)hipStreamSynchronize(s);
+        (void)hipMemcpy(h, a->ws.ctrl, sizeof(h), hipMemcpyDeviceToHost);
+        std::fprintf(stderr, "[rtk stream] node_cap %u hit_cap %u overflow %u; nodes per level:", a->ws.node_cap, a->ws.hit_cap, h[dev::kCtrlOverflow]);
+        for (int l = 0; l <= p->max_ray_depth + 1; ++l) std::fprintf(stderr, " %u", l == 0 ? unsigned(n_root) : h[dev::kCtrlNodeCount + l]);
+        std::fprintf(stderr, "; hits:");
+        for (int l = 0; l <= p->max_ray_depth; ++l) std::fprintf(stderr, " %u", h[dev::kCtrlHitCount + l]);
+        std::fprintf(stderr, "\n");
+    }
+    return RTK_OK;
+}
+
+// (capacity, never shrunk)
+int ensure_feedback_ws(rtk_accel *a, const FrameGeom &g, size_t units) {
+    if (a->fb_units >= units) return RTK_OK;
+    // (the first allocation also covers the scene's own frame size, so that a small frame
+    // rendered first -- a warm-up -- does not leave three hipMallocs, ~0.1 ms, in front of the first full-size frame)
+    size_t cap = units;
+    const uint32_t bk = g.bucket, bs = g.blocks_side;
+    const uint64_t tx = (uint64_t(a->scene.width > 0 ? a->scene.width : 0) + bk - 1) / bk, ty = (uint64_t(a->scene.height > 0 ? a->scene.height : 0) + bk - 1) / bk;
+    const uint64_t native = tx * ty * bs * bs;
+    if (a->fb_units == 0 && native > cap && native <= (1ull << 24)) cap = size_t(native);
+    (void)hipFree(a->fb_cost); (void)hipFree(a->fb_order); (void)hipFree(a->fb_bins);
+    a->fb_cost = a->fb_order = nullptr; a->fb_bins = nullptr; a->fb_units = 0; a->fb_valid = false; a->fb_order_valid = false;
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_cost), cap * sizeof(uint32_t)));
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_order), (2 * cap + 4 + 8) * sizeof(uint32_t)));   // order, header, workgroup list, prior's counters
+    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->fb_bins), cap));
+    a->fb_units = cap;
+    return RTK_OK;
+}
+
+// The megakernel with cost feedback: the frame time is set by the few pixel blocks whose rays graze the mesh (hundreds of
+// microseconds each, against ~3 for a background block).  Started late they are the tail of the frame, so every block reports
+// its cycle count and the next frame of the same shape starts them most-expensive-first.  Only the launch order
+// changes: every block is rendered in full, every frame.  RTK_COST_FEEDBACK=0 turns it off.
+int render_megakernel(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general, hipStream_t s) {
+    const size_t units = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
+    A.n_units = uint32_t(units);
+    // RTK_TRACE_AUTO for frames: four waves per pixel block when there are enough blocks to fill the chip several times over,
+    // eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
+    // Measured on config 2 (tools/rank_times.py): 32,400 blocks 0.44 ms (GROUP4) vs 0.87 (GROUP8); 4,050 blocks 0.43 vs 0.32.
+    const int frame_mode = p->trace_mode != RTK_TRACE_AUTO ? p->trace_mode : (units < a->knobs.group8_below ? RTK_TRACE_GROUP8 : RTK_TRACE_GROUP4);
+    if (a->knobs.cost_feedback && units > 0 && units <= 0x7FFFFFFFull) {
+        const uint64_t sig[4] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height),
+                                 (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
+                                 (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays),
+                                 (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode)};
+        RTK_TRY(ensure_feedback_ws(a, g, units));
+        uint32_t *const order_hdr = a->fb_order + units, *const wg_list = a->fb_order + units + 4;
+        auto use_order = [&] { A.order_in = a->fb_order; A.order_hdr = order_hdr; A.wg_list = wg_list; };
+        const bool same_shape = a->fb_valid && std::memcmp(sig, a->fb_sig, sizeof(sig)) == 0;
+        if (!same_shape) a->fb_order_valid = false;
+        // The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in for them
+        // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at).
+        // A one-shot render is exactly this frame (the reference CLI renders one, src/main.cpp:13-25).
+        const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0;
+        if (prior) {
+            RTK_HIP_AS(launch_block_prior(A, a->fb_bins, a->fb_order, wg_list, order_hdr,
+                                          reinterpret_cast<uint32_t *>(a->d_counters + kCounterWords), 4u, s), "launch k_block_prior");
+            use_order();
+        }
+        if (same_shape) {
+            // The order is refreshed from the newest costs every few frames only: the sort is one small workgroup whose
+            // ~28 us sit in front of the frame, and an order that is a few frames old is as good (costs move slowly).
+            if (!a->fb_order_valid || a->fb_age >= a->knobs.resort_every) {
+                // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
+                RTK_HIP_AS(launch_order_by_cost(a->fb_cost, a->fb_bins, a->fb_order, wg_list, order_hdr, uint32_t(units),
+                                                frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
+                           "launch k_order_by_cost");
+                a->fb_order_valid = true;
+                a->fb_age = 0;
+                // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
+                if (!a->fb_nwgs_host) {
+                    RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->fb_nwgs_host), sizeof(uint32_t), hipHostMallocDefault));
+                    RTK_HIP(hipEventCreateWithFlags(&a->fb_nwgs_ev, hipEventDisableTiming));
+                }
+                a->fb_nwgs_known = false;
+                RTK_HIP(hipMemcpyAsync(a->fb_nwgs_host, order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                RTK_HIP(hipEventRecord(a->fb_nwgs_ev, s));
+                a->fb_nwgs_pending = true;
+            }
+            a->fb_age += 1;
+            use_order();
+        }
+        A.cost_out = a->fb_cost;
+        std::memcpy(a->fb_sig, sig, sizeof(sig));
+        a->fb_valid = true;
+    }
+    unsigned n_wgs = 0;
+    if (A.wg_list != nullptr && A.order_in == a->fb_order && a->fb_order_valid) {
+        if (a->fb_nwgs_pending && hipEventQuery(a->fb_nwgs_ev) == hipSuccess) { a->fb_nwgs_pending = false; a->fb_nwgs_known = true; }
+        else if (a->fb_nwgs_pending) (void)hipGetLastError();            // not ready: clear the sticky status
+        if (a->fb_nwgs_known && !a->fb_nwgs_pending) n_wgs = *a->fb_nwgs_host;
+    }
+    RTK_HIP_AS(launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs), "launch k_render");
+    return RTK_OK;
+}
+
+int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d_out, hipStream_t s) {
+    FrameGeom g;
+    RTK_TRY(frame_geom(a, p, g));
+    if (!d_out) return fail(RTK_ERR_INVALID, "null output buffer");
+    dev::RenderArgs A = scene_args(a, p->collect_stats);
+    camera_args(a, p, g, A);
+    A.max_depth = p->max_ray_depth; A.diffuse_rays = p->diffuse_rays;
+    A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
+    A.sample_begin = g.sample_begin; A.sample_end = g.sample_end;
+    A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
+    A.bucket = g.bucket; A.tiles_x = g.tiles_x; A.tiles_y = g.tiles_y; A.n_buckets = g.n_buckets;
+    A.blocks_per_bucket_side = g.blocks_side; A.buckets_per_rank = g.buckets_per_rank;
+    A.rank = g.rank; A.world = g.world; A.compact = g.world > 1 ? 1 : 0; A.skew_q = g.skew_q;
+    A.out = d_out; A.counters = a->d_counters;
+    const bool forks = a->has_refractive || p->diffuse_rays > 0;
+    // the megakernel comes in two builds: the lean one (diffuse / reflective / constant materials only) and the general one
+    // (template FORKS: + refraction, diffuse GI, textures), so that the lean one does not carry the general one's registers
+    const bool general = forks || !a->scene.textures.empty();
+    RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+    // buckets past the end of the frame (padding so that every rank has equal length) stay zero
+    if (g.world > 1 && g.sample_begin == 0) RTK_HIP(hipMemsetAsync(d_out, 0, out_pixels(g) * 3 * sizeof(float), s));
+    bool stream = false;
+    hipEvent_t trial[2] = {nullptr, nullptr};
+    RTK_TRY(choose_engine(a, p, g, forks, stream, trial));
+    // (the streaming pipeline starts its trial itself, behind its workspace allocation)
+    if (trial[0] && !stream) RTK_HIP(hipEventRecord(trial[0], s));
+    if (p->trace_mode == RTK_TRACE_TWOPASS) RTK_TRY(render_twopass(a, p, g, A, general, s));
+    else if (stream) RTK_TRY(render_stream(a, p, g, A, forks, general, trial, s));
+    else RTK_TRY(render_megakernel(a, p, g, A, general, s));
+    if (trial[1]) RTK_HIP(hipEventRecord(trial[1], s));
+    a->last_stream = s;
+    a->last_stats = p->collect_stats != 0;
+    a->last_primary = primary_rays_of_rank(g);
+    return RTK_OK;
+}
+
+int radiance_check(const rtk_accel *a, const void *rays, const void *ids, size_t n, const rtk_radiance_params *p, const void *rgb) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    if (p->trace_mode != RTK_TRACE_AUTO && p->trace_mode != RTK_TRACE_STREAM)
+        return fail(RTK_ERR_INVALID, "trace_mode of a radiance batch must be RTK_TRACE_AUTO or RTK_TRACE_STREAM");
+    if (p->max_ray_depth < 0 || p->max_ray_depth > kMaxRayDepth) return fail(RTK_ERR_INVALID, "max_ray_depth must be in [0, 16]");
+    if (p->diffuse_rays < 0 || p->diffuse_rays > 32767) return fail(RTK_ERR_INVALID, "diffuse_rays must be in [0, 32767]");
+    if (p->sample < 0) return fail(RTK_ERR_INVALID, "sample must be >= 0");
+    if (!std::isfinite(p->shadow_bias) || !std::isfinite(p->reflection_bias) || !std::isfinite(p->refraction_bias))
+        return fail(RTK_ERR_INVALID, "shadow_bias, reflection_bias and refraction_bias must be finite");
+    if (n > (size_t(1) << 38)) return fail(RTK_ERR_INVALID, "too many rays for one call");
+    if (n > 0 && (!rays || !rgb)) return fail(RTK_ERR_INVALID, "null ray or colour buffer");
+    if (!ids && n > (size_t(1) << 32)) return fail(RTK_ERR_INVALID, "more than 2^32 rays need explicit ids");
+    return RTK_OK;
+}
+
+// The batch cut into chunks, every chunk one run of the streaming pipeline (level 0 = the chunk's rays) on one of the accel's
+// lanes, followed by its counter fold and its overflow fallback.  Nothing here waits on the host.
+int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
+                         float *d_rgb, hipStream_t s, uint32_t *n_chunks_out) {
+    dev::RenderArgs A = scene_args(a, 0);
+    // one colour per ray: "sample 0 of 1" for k_combine, whatever sample the RNG keys name
+    A.spp = 1; A.sample_begin = 0; A.sample_end = 1; A.spp_f = 1.0f;
+    A.max_depth = p->max_ray_depth; A.diffuse_rays = p->diffuse_rays; A.seed = p->seed;
+    A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
+    A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
+    A.world = 1;
+    const bool forks = a->has_refractive || p->diffuse_rays > 0;
+    StreamSetup u = stream_args(a, A, p->diffuse_rays, forks);
+    const RadiancePlan plan = plan_radiance_chunks(n, u.factor, u.node_bytes, u.budget, a->knobs.stream_lanes);
+    const int lanes = plan.lanes;
+    if (n_chunks_out) *n_chunks_out = uint32_t(plan.n_chunks);
+    RTK_TRY(ensure_stream_ws(a, 0, plan.nodes, a->scene.lights.size(), false, lanes));
+    const size_t lane_words = size_t(dev::kStreamLanes) * kCounterWords;
+    if (!a->d_rad_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_rad_counters), (lane_words + 2) * sizeof(unsigned long long)));
+    unsigned long long *const total = a->d_rad_counters + lane_words;
+    RTK_TRY(claim_stream_ws(a, s));
+    RTK_HIP(hipMemsetAsync(total, 0, 2 * sizeof(unsigned long long), s));
+    dev::StreamArgs &S = u.S;
+    S.n_lanes = 1;                                       // overflow words: a chunk is judged on its own lane's alone (k_combine, depth 0)
+    S.user_sample = uint32_t(p->sample); S.user_cull = p->cull ? 1u : 0u;
+    RTK_TRY(fork_lanes(a, lanes, s));
+    const bool side = a->knobs.stream_side && lanes <= 2 && lanes <= a->knobs.stream_side_below;      // (a frame counts samples in flight, a batch chunks)
+    for (size_t i = 0; i < plan.n_chunks; ++i) {
+        const int j = int(i % size_t(lanes));
+        const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
+        const size_t first = i * plan.chunk, cn = n - first < plan.chunk ? n - first : plan.chunk;
+        S.ws = a->ws_lane[j];
+        for (int k = 0; k < dev::kStreamLanes; ++k) S.lane_overflow[k] = S.ws.ctrl + dev::kCtrlOverflow;
+        S.user_rays = d_rays + first; S.user_ids = d_ids ? d_ids + first : nullptr;
+        S.user_n = uint32_t(cn); S.user_id0 = uint32_t(first);
+        S.n_root = uint32_t((cn + 63) / 64 * 64); S.n_level0 = S.n_root;
+        S.r.out = d_rgb + first * 3;
+        S.r.counters = a->d_rad_counters + size_t(j) * kCounterWords;
+        // ctrl: a chunk zeroes its lane's and its counter block on the lane's stream (the overflow word included: it is the chunk's)
+        RTK_HIP(hipMemsetAsync(S.ws.ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), ls));
+        RTK_HIP(hipMemsetAsync(S.r.counters, 0, kCounterWords * sizeof(unsigned long long), ls));
+        // ordering events: none between chunks (each writes its own colours); lane_done is recorded here, for the join
+        hipError_t e = launch_stream_sample(S, false, u.deep_level, u.deep_mode, u.sort_from, ls, nullptr, nullptr, side ? &a->lane_side[j] : nullptr, u.slices);
+        // tail: the chunk's rays into the call's total, and the per-ray fallback if its queues overflowed
+        if (e == hipSuccess) e = launch_radiance_fold(S, total, ls);
+        if (e == hipSuccess) e = launch_radiance_fallback(S, total, ls);
+        if (e != hipSuccess) return hip_fail(e, "launch radiance chunk");
+        if (j != 0) RTK_HIP(hipEventRecord(a->lane_done[j], ls));
+    }
+    RTK_TRY(join_lanes(a, lanes, s));
+    return release_stream_ws(a, s);
+}
+
+}  // namespace
+}  // namespace rtk
+
+using namespace rtk;
+
+extern "C" {
+
+int rtk_render_output_floats(const rtk_accel *a, const rtk_render_params *p, size_t *n_floats) {
+    if (!n_floats) return fail(RTK_ERR_INVALID, "null n_floats");
+    FrameGeom g;
+    RTK_TRY(frame_geom(a, p, g));
+    *n_floats = out_pixels(g) * 3;
+    return RTK_OK;
+}
+
+int rtk_render_frame_device(rtk_accel *a, const rtk_render_params *p, float *d_out, void *stream) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    std::lock_guard<std::mutex> lock(a->mu);
+    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+    return render_device_impl(a, p, d_out, static_cast<hipStream_t>(stream));
+}
+
+int rtk_render_last_counters(rtk_accel *a, rtk_counters *c) {
+    if (!a || !c) return fail(RTK_ERR_INVALID, "null accel or counters");
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
+    RTK_HIP(hipSetDevice(a->device));
+    RTK_HIP(hipStreamSynchronize(a->last_stream));
+    unsigned long long h[kCounterWords];
+    RTK_HIP(hipMemcpy(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+    std::memset(c, 0, sizeof(*c));
+    for (int i = 0; i < kRayCounterShards; ++i) h[0] += h[8 + i];      // the frame kernel shards its ray counter
+    c->rays = h[0]; c->primary = a->last_primary;
+    if (a->last_stats) { c->hits = h[2]; c->nodes = h[3]; c->boxpass = h[4]; c->leaves = h[5]; c->tris = h[6]; c->packets16 = h[7]; }
+    return RTK_OK;
+}
+
+int rtk_render_last_critical_path(rtk_accel *a, double *ms) {
+    if (!a || !ms) return fail(RTK_ERR_INVALID, "null accel or ms");
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
+    RTK_HIP(hipSetDevice(a->device));
+    RTK_HIP(hipStreamSynchronize(a->last_stream));
+    unsigned long long shard[kRayCounterShards], ticks = 0;
+    RTK_HIP(hipMemcpy(shard, a->d_counters + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
+    for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
+    *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
+    return RTK_OK;
+}
+
+int rtk_render_frame(rtk_accel *a, const rtk_render_params *p, float *rgb, rtk_counters *counters) {
+    if (!a || !p || !rgb) return fail(RTK_ERR_INVALID, "null accel, params or rgb");
+    if (p->world_size > 1) return fail(RTK_ERR_INVALID, "rtk_render_frame renders whole frames; use rtk_render_frame_device for sharded output");
+    size_t nf = 0;
+    RTK_TRY(rtk_render_output_floats(a, p, &nf));
+    {
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        float *d_out = nullptr;
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d_out), nf * sizeof(float)));
+        hipError_t e = hipSuccess;
+        // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
+        if (p->sample_begin > 0) e = hipMemcpy(d_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d_out); return hip_fail(e, "upload of the running sums"); }
+        const int rc = render_device_impl(a, p, d_out, nullptr);
+        if (rc == RTK_OK) e = hipMemcpy(rgb, d_out, nf * sizeof(float), hipMemcpyDeviceToHost);
+        (void)hipFree(d_out);
+        if (rc != RTK_OK) return rc;
+        if (e != hipSuccess) return hip_fail(e, "frame copy");
+    }
+    if (counters) return rtk_render_last_counters(a, counters);
+    return RTK_OK;
+}
+
+int rtk_tiles_assemble_device(const rtk_accel *a, const rtk_render_params *p, const float *d_gathered, float *d_rgb, void *stream) {
+    FrameGeom g;
+    RTK_TRY(frame_geom(a, p, g));
+    if (!d_gathered || !d_rgb) return fail(RTK_ERR_INVALID, "null buffer");
+    dev::AssembleArgs A;
+    A.gathered = d_gathered; A.rgb = d_rgb; A.width = g.width; A.height = g.height; A.bucket = g.bucket;
+    A.tiles_x = g.tiles_x; A.world = uint32_t(g.world); A.buckets_per_rank = g.buckets_per_rank; A.skew_q = g.skew_q;
+    RTK_HIP_AS(launch_assemble(A, static_cast<hipStream_t>(stream)), "launch k_assemble");
+    return RTK_OK;
+}
+
+// ---------------------------------------------------------------- batched radiance
+
+int rtk_accel_radiance_device(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
+                              float *d_rgb, void *stream) {
+    RTK_TRY(radiance_check(a, d_rays, d_ids, n, p, d_rgb));
+    if (n == 0) return RTK_OK;
+    std::lock_guard<std::mutex> lock(a->mu);
+    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+    return radiance_device_impl(a, d_rays, d_ids, n, p, d_rgb, static_cast<hipStream_t>(stream), nullptr);
+}
+
+int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, size_t n, const rtk_radiance_params *p, float *rgb,
+                       rtk_counters *counters) {
+    RTK_TRY(radiance_check(a, rays, ids, n, p, rgb));
+    if (n == 0) {
+        if (counters) std::memset(counters, 0, sizeof(*counters));
+        return RTK_OK;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    RTK_TRY(ensure_device(a));
+    if (a->rad_cap < n) {
+        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb);
+        a->rad_rays = nullptr; a->rad_ids = nullptr; a->rad_rgb = nullptr; a->rad_cap = 0;
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rays), n * sizeof(rtk_ray)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_ids), n * sizeof(uint32_t)));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rgb), n * 3 * sizeof(float)));
+        a->rad_cap = n;
+    }
+    RTK_HIP(hipMemcpy(a->rad_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+    if (ids) RTK_HIP(hipMemcpy(a->rad_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    uint32_t n_chunks = 0;
+    RTK_TRY(radiance_device_impl(a, a->rad_rays, ids ? a->rad_ids : nullptr, n, p, a->rad_rgb, nullptr, &n_chunks));
+    RTK_HIP(hipMemcpy(rgb, a->rad_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    unsigned long long h[2] = {0, 0};
+    RTK_HIP(hipMemcpy(h, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
+    if (counters) {
+        std::memset(counters, 0, sizeof(*counters));
+        counters->rays = h[0]; counters->primary = n;
+    }
+    if (a->knobs.stream_debug)
+        std::fprintf(stderr, "[rtk radiance] rays %zu chunks %u redone %llu node_cap %u\n", n, n_chunks, h[1], a->ws.node_cap);
+    return RTK_OK;
+}
+
+// ---------------------------------------------------------------- camera rays
+
+int rtk_camera_rays_device(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *d_rays, void *stream) {
+    if (!a || !p || !d_rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
+    std::lock_guard<std::mutex> lock(a->mu);
+    RTK_TRY(ensure_device(a));
+    FrameGeom g;
+    RTK_TRY(frame_geom(a, p, g));
+    if (sample < 0 || sample >= p->spp) return fail(RTK_ERR_INVALID, "sample must be in [0, spp)");
+    dev::RenderArgs A;
+    std::memset(&A, 0, sizeof(A));
+    camera_args(a, p, g, A);
+    RTK_HIP_AS(launch_camera_rays(A, sample, d_rays, static_cast<hipStream_t>(stream)), "launch k_camera_rays");
+    return RTK_OK;
+}
+
+int rtk_camera_rays(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *rays) {
+    if (!a || !p || !rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
+    FrameGeom g;
+    RTK_TRY(frame_geom(a, p, g));
+    const size_t n = size_t(g.width) * g.height;
+    rtk_ray *d = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(rtk_ray)));
+    }
+    const int rc = rtk_camera_rays_device(a, p, sample, d, nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == RTK_OK) e = hipMemcpy(rays, d, n * sizeof(rtk_ray), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (rc != RTK_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "camera ray copy");
+    return RTK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,279 @@
+// C-ABI, dynamic geometry: rtk_accel_update_vertices rebuilds the kd-tree on the device (build.hip) and swaps it in.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "accel.hpp"
+
+using namespace rtk;
+
+namespace {
+
+// Grows a device buffer to at least `need` bytes (with head room; the old contents are not kept).  Freeing synchronises the
+// device: this is the "second block" of an update, taken only when a buffer has to grow.
+int grow_dev(void **p, size_t *cap, size_t need) {
+    if (need == 0) need = 1;
+    if (*p != nullptr && need <= *cap) return RTK_OK;
+    (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t n = need + need / 2 + 256;
+    RTK_HIP(hipMalloc(p, n));
+    *cap = n;
+    return RTK_OK;
+}
+
+int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
+    if (*p != nullptr && need <= *cap) return RTK_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t n = need + need / 2 + 256;
+    RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(p), n, hipHostMallocDefault));
+    *cap = n;
+    return RTK_OK;
+}
+
+// What an update needs of the topology, which never changes: vertex ids per triangle over the concatenated vertex array, the
+// vertex -> (triangle, corner) incidence lists and which triangles are opaque.  Made on the first update, kept.
+int ensure_update_static(rtk_accel *a) {
+    if (a->up_static) return RTK_OK;
+    const size_t nv = size_t(a->scene.n_vertices), nt = size_t(a->scene.n_triangles);
+    if (nt * 3 > 0xFFFFFFF0ull || nv > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "scene too large for the device build's 32-bit indices");
+    std::vector<uint32_t> index(nt * 3), off(nv + 1, 0u), inc(nt * 3);
+    std::vector<uint8_t> opaque(nt, uint8_t(1));
+    size_t voff = 0, t = 0;
+    for (const HostMesh &m : a->scene.meshes) {
+        const bool refr = size_t(m.material) < a->scene.materials.size() && a->scene.materials[size_t(m.material)].kind == RTK_MAT_REFRACTIVE;
+        for (size_t ti = 0; ti < m.indices.size() / 3; ++ti, ++t) {
+            for (size_t k = 0; k < 3; ++k) index[t * 3 + k] = uint32_t(voff + m.indices[ti * 3 + k]);
+            opaque[t] = refr ? 0 : 1;
+        }
+        voff += m.vertices.size();
+    }
+    if (voff != nv || t != nt) return fail(RTK_ERR_INVALID, "internal: the accel's scene copy lost its vertices");
+    // Incidence lists by counting sort over (triangle, corner) in ascending order: each vertex's list ascends by triangle and
+    // keeps duplicates, which is the order mesh.hpp:36-38 adds the face normals in (build.hip, k_build_normals).
+    for (uint32_t v : index) off[size_t(v) + 1] += 1u;
+    for (size_t v = 0; v < nv; ++v) off[v + 1] += off[v];
+    std::vector<uint32_t> cur(off.begin(), off.end() - 1);
+    for (size_t e = 0; e < nt * 3; ++e) inc[cur[index[e]]++] = uint32_t(e);
+    int rc;
+    // (a call that failed half way left what it had made: made once, never twice)
+    if (!a->up_index && (rc = upload(index, &a->up_index)) != RTK_OK) { (void)hipFree(a->up_index); a->up_index = nullptr; return rc; }
+    if (!a->up_inc_off && (rc = upload(off, &a->up_inc_off)) != RTK_OK) { (void)hipFree(a->up_inc_off); a->up_inc_off = nullptr; return rc; }
+    if (!a->up_inc && (rc = upload(inc, &a->up_inc)) != RTK_OK) { (void)hipFree(a->up_inc); a->up_inc = nullptr; return rc; }
+    if (!a->up_opaque && (rc = upload(opaque, &a->up_opaque)) != RTK_OK) { (void)hipFree(a->up_opaque); a->up_opaque = nullptr; return rc; }
+    if (!a->geom_ready) RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
+    const HostTree &T = a->tree;
+    auto bytes = [](size_t n, size_t each) { return (n == 0 ? 1 : n) * each; };
+    a->active_cap[G_NODES] = bytes(T.dev_nodes.size(), sizeof(DevNode));
+    a->active_cap[G_LEAVES] = bytes(T.dev_leaves.size(), sizeof(DevNode));
+    a->active_cap[G_FAST] = a->d_leaves_fast ? bytes(T.dev_leaves_fast.size(), sizeof(DevNode)) : 0;
+    a->active_cap[G_TRIS] = bytes(T.dev_tris.size(), sizeof(DevTri));
+    a->active_cap[G_IDS] = bytes(T.dev_tri_ids.size(), sizeof(uint32_t));
+    a->active_cap[G_SHADE] = bytes(T.dev_shade.size(), sizeof(DevShade));
+    // (the opaque-only copy was uploaded at its exact size, which is not kept: 0 makes the first update allocate its own)
+    a->up_static = true;
+    return RTK_OK;
+}
+
+int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
+    RTK_TRY(ensure_update_static(a));
+    const uint32_t nv = uint32_t(a->scene.n_vertices), nt = uint32_t(a->scene.n_triangles);
+    const bool occl = a->occl_on;
+    // per-triangle scratch (the triangle count never changes: allocated once) and the new shading records
+    if (!a->up_tris) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tris), std::max<size_t>(1, nt) * sizeof(DevTri)));
+    if (!a->up_tbox) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tbox), std::max<size_t>(1, nt) * 6 * sizeof(float)));
+    RTK_TRY(grow_dev(&a->spare[G_SHADE], &a->spare_cap[G_SHADE], size_t(nt) * sizeof(DevShade)));
+    // Capacities of the build: a tree of depth d has at most 2^(d+1) - 1 nodes; the lists of all levels lie one behind the
+    // other, a level's lists together are about as long as leaf_refs.  Both are checked on the device; a build that does not fit
+    // raises a flag, and is repeated with more room.
+    const size_t max_nodes = (size_t(1) << (a->params.max_depth + 1)) - 1;
+    size_t want_nodes = a->up_cap_nodes ? a->up_cap_nodes : std::max<size_t>(1024, 4 * a->tree.dev_nodes.size());
+    size_t want_refs = a->up_cap_refs ? a->up_cap_refs
+                                      : std::max<size_t>(4096, 2 * size_t(nt) * size_t(std::min(a->params.max_depth, 12) + 2));
+    dev::BuildHdr hdr;
+    for (int attempt = 0;; ++attempt) {
+        if (want_nodes > max_nodes) want_nodes = max_nodes;
+        if (attempt > 16 || want_refs > 0x7FFFFFF0ull) return fail(RTK_ERR_INVALID, "tree too large for 32-bit node/triangle indices");
+        if (want_refs < nt) want_refs = nt;
+        if (want_nodes != a->up_cap_nodes || !a->up_table) {
+            const size_t bytes = sizeof(dev::BuildHdr) + want_nodes * sizeof(dev::BuildNode);
+            (void)hipFree(a->up_table); a->up_table = nullptr; a->up_cap_nodes = 0;
+            if (a->up_table_host) (void)hipHostFree(a->up_table_host);
+            a->up_table_host = nullptr;
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_table), bytes));
+            RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->up_table_host), bytes, hipHostMallocDefault));
+            a->up_cap_nodes = want_nodes;
+        }
+        if (want_refs != a->up_cap_refs || !a->up_ref_id) {
+            (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);
+            a->up_ref_id = a->up_ref_node = nullptr; a->up_cap_refs = 0;
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_id), want_refs * sizeof(uint32_t)));
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_node), want_refs * sizeof(uint32_t)));
+            a->up_cap_refs = want_refs;
+        }
+        dev::BuildArgs B;
+        B.verts = d_verts; B.n_verts = nv; B.n_tris = nt;
+        B.index = a->up_index; B.inc_off = a->up_inc_off; B.inc = a->up_inc;
+        B.opaque = occl ? a->up_opaque : nullptr;
+        B.shade_old = a->d_shade; B.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
+        B.tris = a->up_tris; B.tbox = a->up_tbox;
+        B.ref_id = a->up_ref_id; B.ref_node = a->up_ref_node;
+        B.cap_refs = uint32_t(a->up_cap_refs); B.cap_nodes = uint32_t(a->up_cap_nodes);
+        B.max_depth = a->params.max_depth; B.max_leaf = a->params.max_leaf_size;
+        B.hdr = reinterpret_cast<dev::BuildHdr *>(a->up_table);
+        B.nodes = reinterpret_cast<dev::BuildNode *>(a->up_table + sizeof(dev::BuildHdr));
+        RTK_HIP_AS(launch_build(B, s), "launch device build");
+        // the one place an update blocks the host: flags, sizes and the node table
+        RTK_HIP(hipMemcpyAsync(a->up_table_host, a->up_table, sizeof(dev::BuildHdr) + a->up_cap_nodes * sizeof(dev::BuildNode), hipMemcpyDeviceToHost, s));
+        RTK_HIP(hipStreamSynchronize(s));
+        std::memcpy(&hdr, a->up_table_host, sizeof(hdr));
+        const uint32_t raised = ~hdr.ok;
+        if (raised & dev::kBuildNonFinite) return fail(RTK_ERR_INVALID, "vertices must be finite");
+        if ((raised & (dev::kBuildRefOverflow | dev::kBuildNodeOverflow)) == 0u) break;
+        if (raised & dev::kBuildNodeOverflow) want_nodes = std::max<size_t>(2 * a->up_cap_nodes, 2 * size_t(hdr.need_nodes));
+        if (raised & dev::kBuildRefOverflow) want_refs = std::max<size_t>(2 * a->up_cap_refs, 2 * size_t(hdr.need_refs));
+    }
+    // numbering on the host (kdtree.cpp): reference order, traversal order with skip links, leaf offsets in both, FAST orders
+    const dev::BuildNode *bn = reinterpret_cast<const dev::BuildNode *>(a->up_table_host + sizeof(dev::BuildHdr));
+    HostTree T;
+    std::vector<dev::GatherLeaf> gather;
+    tree_from_build_nodes(bn, T, gather);
+    if (T.nodes.size() != hdr.n_nodes) return fail(RTK_ERR_INVALID, "internal: the device build's node table is not a tree");
+    if (a->fast_traversal) build_fast_leaf_orders(T);
+    size_t n_refs = 0;
+    for (const dev::GatherLeaf &g : gather) n_refs += g.count;
+    if (n_refs > 0x7FFFFFFFull) return fail(RTK_ERR_INVALID, "tree too large for 32-bit node/triangle indices");
+    std::vector<DevNode> onodes, oleaves;
+    size_t n_opaque = 0;
+    if (occl) {                                                         // as ensure_device: the same nodes, their leaves without the transmissive triangles
+        onodes = T.dev_nodes;
+        size_t li = 0;
+        for (DevNode &n : onodes) {
+            if (n.b == DEV_INNER) continue;
+            dev::GatherLeaf &g = gather[li++];                          // (dev_leaves and gather are both the leaves in dev_nodes' order)
+            g.dst_occl = uint32_t(n_opaque);
+            n.a = uint32_t(n_opaque); n.b = g.pad[0];
+            n_opaque += g.pad[0];
+            if (n.b != 0u) oleaves.push_back(n);
+        }
+        if (oleaves.empty()) { DevNode n = onodes[0]; n.a = 0u; n.b = 0u; oleaves.push_back(n); }
+    }
+    for (dev::GatherLeaf &g : gather) g.pad[0] = 0u;
+    // room in the spare set
+    void **sp = a->spare;
+    size_t *sc = a->spare_cap;
+    RTK_TRY(grow_dev(&sp[G_NODES], &sc[G_NODES], T.dev_nodes.size() * sizeof(DevNode)));
+    RTK_TRY(grow_dev(&sp[G_LEAVES], &sc[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode)));
+    if (a->fast_traversal) RTK_TRY(grow_dev(&sp[G_FAST], &sc[G_FAST], T.dev_leaves_fast.size() * sizeof(DevNode)));
+    RTK_TRY(grow_dev(&sp[G_TRIS], &sc[G_TRIS], n_refs * sizeof(DevTri)));
+    RTK_TRY(grow_dev(&sp[G_IDS], &sc[G_IDS], n_refs * sizeof(uint32_t)));
+    RTK_TRY(grow_dev(&sp[G_LREFS], &sc[G_LREFS], n_refs * sizeof(int32_t)));
+    if (occl) {
+        RTK_TRY(grow_dev(&sp[G_ONODES], &sc[G_ONODES], onodes.size() * sizeof(DevNode)));
+        RTK_TRY(grow_dev(&sp[G_OLEAVES], &sc[G_OLEAVES], oleaves.size() * sizeof(DevNode)));
+        RTK_TRY(grow_dev(&sp[G_OTRIS], &sc[G_OTRIS], std::max<size_t>(1, n_opaque) * sizeof(DevTri)));
+        RTK_TRY(grow_dev(&sp[G_OIDS], &sc[G_OIDS], std::max<size_t>(1, n_opaque) * sizeof(uint32_t)));
+    }
+    size_t gcap = a->up_gather_cap * sizeof(dev::GatherLeaf);
+    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_gather), &gcap, gather.size() * sizeof(dev::GatherLeaf)));
+    a->up_gather_cap = gcap / sizeof(dev::GatherLeaf);
+    // the small tables go up through one pinned buffer (the copies are stream-ordered and the host does not wait for them)
+    struct Up { const void *src; void *dst; size_t bytes; };
+    const Up ups[] = {
+        {T.dev_nodes.data(), sp[G_NODES], T.dev_nodes.size() * sizeof(DevNode)},
+        {T.dev_leaves.data(), sp[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode)},
+        {T.dev_leaves_fast.data(), sp[G_FAST], a->fast_traversal ? T.dev_leaves_fast.size() * sizeof(DevNode) : 0},
+        {gather.data(), a->up_gather, gather.size() * sizeof(dev::GatherLeaf)},
+        {onodes.data(), sp[G_ONODES], onodes.size() * sizeof(DevNode)},
+        {oleaves.data(), sp[G_OLEAVES], oleaves.size() * sizeof(DevNode)},
+    };
+    size_t total = 0;
+    for (const Up &u : ups) total += (u.bytes + 63) & ~size_t(63);
+    RTK_TRY(grow_pinned(&a->up_stage, &a->up_stage_cap, total));
+    size_t at = 0;
+    for (const Up &u : ups) {
+        if (u.bytes == 0) continue;
+        std::memcpy(a->up_stage + at, u.src, u.bytes);
+        RTK_HIP(hipMemcpyAsync(u.dst, a->up_stage + at, u.bytes, hipMemcpyHostToDevice, s));
+        at += (u.bytes + 63) & ~size_t(63);
+    }
+    dev::GatherArgs G;
+    G.leaves = a->up_gather; G.n_leaves = uint32_t(gather.size());
+    G.ref_id = a->up_ref_id; G.tris_in = a->up_tris; G.opaque = occl ? a->up_opaque : nullptr;
+    G.tris = static_cast<DevTri *>(sp[G_TRIS]); G.tri_ids = static_cast<uint32_t *>(sp[G_IDS]); G.leaf_refs = static_cast<int32_t *>(sp[G_LREFS]);
+    G.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); G.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]);
+    RTK_HIP_AS(launch_gather(G, s), "launch k_build_gather");
+    if (occl && n_opaque == 0) {                                        // nothing opaque: keep the pointers valid, as ensure_device does
+        if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp[G_OTRIS], sp[G_TRIS], sizeof(DevTri), hipMemcpyDeviceToDevice, s));
+        else RTK_HIP(hipMemsetAsync(sp[G_OTRIS], 0, sizeof(DevTri), s));
+        RTK_HIP(hipMemsetAsync(sp[G_OIDS], 0, sizeof(uint32_t), s));
+    }
+    RTK_HIP(hipEventRecord(a->geom_ready, s));
+    // ---- nothing below fails: swap the sets and bring the host's picture of the accel up to date
+    void **act[kGeomBufs] = {reinterpret_cast<void **>(&a->d_nodes), reinterpret_cast<void **>(&a->d_leaves), reinterpret_cast<void **>(&a->d_leaves_fast),
+                             reinterpret_cast<void **>(&a->d_tris), reinterpret_cast<void **>(&a->d_tri_ids), reinterpret_cast<void **>(&a->d_shade),
+                             reinterpret_cast<void **>(&a->d_leaf_refs), reinterpret_cast<void **>(&a->d_occl_nodes), reinterpret_cast<void **>(&a->d_occl_leaves),
+                             reinterpret_cast<void **>(&a->d_occl_tris), reinterpret_cast<void **>(&a->d_occl_ids)};
+    for (int i = 0; i < kGeomBufs; ++i) {
+        if (i == G_FAST && !a->fast_traversal) continue;
+        if (i >= G_ONODES && !occl) continue;
+        std::swap(*act[i], a->spare[i]);
+        std::swap(a->active_cap[i], a->spare_cap[i]);
+    }
+    a->geom_pending = true;
+    a->occl_n_leaves = occl ? uint32_t(oleaves.size()) : 0u;
+    a->tree.nodes = std::move(T.nodes);
+    a->tree.dev_nodes = std::move(T.dev_nodes);
+    a->tree.dev_leaves = std::move(T.dev_leaves);
+    a->tree.dev_leaves_fast = std::move(T.dev_leaves_fast);
+    a->tree.depth = T.depth;
+    // what the host held per triangle, per reference and per vertex describes the old geometry: dropped, not left to lie
+    // (rtk_accel_tree_dump fetches leaf_refs from the device)
+    std::vector<HostTriangle>().swap(a->tree.triangles);
+    std::vector<int32_t>().swap(a->tree.leaf_refs);
+    std::vector<DevTri>().swap(a->tree.dev_tris);
+    std::vector<uint32_t>().swap(a->tree.dev_tri_ids);
+    std::vector<DevShade>().swap(a->tree.dev_shade);
+    for (HostMesh &m : a->scene.meshes) { std::vector<Vec3>().swap(m.vertices); std::vector<Vec3>().swap(m.vertex_normals); }
+    a->refs_on_device = true;
+    a->n_leaf_refs_dev = int32_t(n_refs);
+    a->coords_small = (~hdr.ok & dev::kBuildCoordsBig) == 0u;
+    a->stream_slices_auto = stream_slices_for(a->tree);
+    // the launch order learnt from the old silhouette and the engines' trial on it say nothing about the new geometry
+    a->fb_valid = false; a->fb_order_valid = false; a->fb_age = 0;
+    a->fb_nwgs_pending = false; a->fb_nwgs_known = false;
+    a->trial_state = 0;
+    return RTK_OK;
+}
+
+}  // namespace
+
+int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void *hip_stream) {
+    if (!a || !d_vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
+    std::lock_guard<std::mutex> lock(a->mu);
+    try {
+        RTK_TRY(ensure_device(a));
+        // entry: nothing issued earlier on this accel, on whatever stream, may still read a buffer the update rewrites
+        RTK_HIP(hipDeviceSynchronize());
+        a->geom_pending = false;
+        return update_vertices_impl(a, d_vertices, static_cast<hipStream_t>(hip_stream));
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+}
+
+int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
+    if (!a || !vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
+    std::lock_guard<std::mutex> lock(a->mu);
+    try {
+        RTK_TRY(ensure_device(a));
+        const size_t n = size_t(a->scene.n_vertices) * 3;
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(vertices[i])) return fail(RTK_ERR_INVALID, "vertices must be finite");
+        RTK_HIP(hipDeviceSynchronize());
+        a->geom_pending = false;
+        if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));   // (the vertex count never changes)
+        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
+        return update_vertices_impl(a, a->up_verts, nullptr);
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+}

@@ -128,7 +128,7 @@ __device__ __forceinline__ Ray camera_ray(const RenderArgs &A, const uint32_t px
     float sx = (2.0f * ndc_x) - 1.0f;
     float sy = 1.0f - (2.0f * ndc_y);
     sx *= A.aspect;
-    sx *= A.tan_half_fov;                                       // render.hpp:55-57: float *= tanf(float) (host, api.hip)
+    sx *= A.tan_half_fov;                                       // render.hpp:55-57: float *= tanf(float) (host, api_frame.hip camera_args)
     sy *= A.tan_half_fov;
     const float *M = A.cam_mat;                                 // transpose(camera.matrix) * dir
     V3 d = mk(M[0] * sx + M[3] * sy + M[6] * -1.0f, M[1] * sx + M[4] * sy + M[7] * -1.0f,

@@ -197,7 +197,7 @@ void flatten_jobs(HostTree &t, int32_t node, const dev::BuildNode *bn, const std
         t.dev_nodes[at].b = uint32_t(hn.leaf_count);
         dev::GatherLeaf g{};
         g.src = s.start; g.count = s.count; g.dst = n_refs; g.dst_ref = uint32_t(hn.leaf_start);
-        g.pad[0] = s.c0;                                                 // opaque triangles of the leaf (api.hip places dst_occl)
+        g.pad[0] = s.c0;                                                 // opaque triangles of the leaf (api_update.hip places dst_occl)
         gather.push_back(g);
         n_refs += s.count;
         t.dev_leaves.push_back(t.dev_nodes[at]);

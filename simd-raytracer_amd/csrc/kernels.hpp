@@ -1,4 +1,4 @@
-// Kernel argument blocks and launchers shared by kernels.hip and api.hip.
+// Kernel argument blocks and launchers shared by kernels.hip and the api*.hip files.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,7 +29,7 @@ namespace dev {
 // every row, and a rank's share is as uneven as the picture is from left to right (config 5's shape: 32.8 M ... 38.9 M rays per
 // rank).  Those frames are dealt diagonally instead: bucket (bx, by) -> rank (bx + by) % world; with q = tiles_x / world buckets
 // per rank and row it is that rank's (by * q + bx / world)-th.  skew_q = q selects it (0 = round robin).  Host mirrors:
-// api.hip frame_geom / rank_bucket, parallel.py BucketLayout.
+// api_frame.hip frame_geom / rank_bucket, parallel.py BucketLayout.
 __host__ __device__ inline uint32_t rank_bucket(uint32_t rank, uint32_t local, uint32_t world, uint32_t skew_q) {
     if (skew_q == 0u) return rank + local * world;
     const uint32_t by = local / skew_q, m = local % skew_q;
@@ -91,7 +91,7 @@ struct RenderArgs {
     uint32_t *n_listed;               // number of entries in tile_order
     uint32_t tile_cap;
     const uint32_t *only_if;          // non-null: the kernel does nothing unless this word is non-zero (overflow fallback)
-    // frame-to-frame scheduling feedback (api.hip "cost feedback"): every pixel block reports what it cost; the next
+    // frame-to-frame scheduling feedback (api_frame.hip render_megakernel): every pixel block reports what it cost; the next
     // frame of the same shape starts its blocks most-expensive-first (results do not depend on the order)
     uint32_t n_units;                 // pixel blocks (8x8) of this rank = buckets_per_rank * blocks_per_bucket_side^2
     uint32_t *cost_out;               // [n_units] or null

@@ -1,4 +1,4 @@
-// Batched occlusion query (rtk_accel_occluded*): argument block and launcher shared by occluded.hip and api.hip.
+// Batched occlusion query (rtk_accel_occluded*): argument block and launcher shared by occluded.hip and api_batch.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

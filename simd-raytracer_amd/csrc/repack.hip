@@ -279,7 +279,7 @@ __device__ __forceinline__ uint32_t spread_bits(uint32_t x, const uint32_t n, co
 // tile's loads in flight while this one's keys are made): 65,536 workgroups of one tile each spent their 3 us lives mostly waiting for
 // the bounds, their rays and a free slot -- 180 us for 0.54 GB.
 __global__ __launch_bounds__(256) void k_ray_keys(const rtk_ray *rays, size_t n, const uint32_t *bounds, uint32_t *keys, uint32_t *idx, uint32_t dirs3, uint32_t only_if_sort) {
-    if (only_if_sort != 0u && bounds[16] == 0u) return;      // launched ahead of the probe's verdict (api.hip): the batch is walked as it comes
+    if (only_if_sort != 0u && bounds[16] == 0u) return;      // launched ahead of the probe's verdict (api_batch.hip): the batch is walked as it comes
     __shared__ float4 tile[384];
     const bool aligned = (reinterpret_cast<uintptr_t>(rays) & 15u) == 0u;
     const size_t n_tiles = (n + 255u) / 256u;

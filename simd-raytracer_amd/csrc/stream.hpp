@@ -78,7 +78,7 @@ struct StreamWs {
 // in sample order.  Up to kStreamLanes batches are in flight at once, each on its own HIP stream with its own queues, so that
 // the tail of one batch's level overlaps the other batches' work; only the depth-0 k_combine of a batch is ordered behind the
 // previous batch's, by an event: the running pixel sums stay in sample order.  HBM is what pays: ~120 B per ray-tree node.
-constexpr int kStreamLanes = 8;          // upper bound; the default is 4 (api.hip rtk_knobs)
+constexpr int kStreamLanes = 8;          // upper bound; the default is 4 (accel.hpp rtk_knobs)
 
 struct StreamArgs {
     RenderArgs r;

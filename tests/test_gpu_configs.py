@@ -115,6 +115,23 @@ def test_progressive_passes_equal_one_launch(rtk, ora, mode):
     assert np.array_equal(_bits(whole), _bits(ref))
 
 
+def test_stream_ragged_batches_over_two_lanes(rtk, ora, monkeypatch):
+    """Frame batching off its defaults: five samples in batches of two (RTK_STREAM_BATCH) are three launches, the last of one
+    sample, dealt to two lanes (RTK_STREAM_LANES) whose depth-0 sums are ordered by events; then the same batches through one
+    lane.  The knobs are read when an accel is built.  Both frames are the oracle's, bit for bit, with its ray count."""
+    w, h, spp, depth = 64, 48, 5, 3
+    ref = ocn = None
+    for lanes in ("2", "1"):
+        monkeypatch.setenv("RTK_STREAM_LANES", lanes)
+        monkeypatch.setenv("RTK_STREAM_BATCH", "2")
+        acc, oacc = _pair(rtk, ora, SCENE5)
+        if ref is None:
+            ref, ocn = oacc.render(w, h, spp, depth, 0)
+        rgb, cn = acc.render_frame(rtk.RenderConfig(width=w, height=h, spp=spp, max_ray_depth=depth, trace_mode=STREAM))
+        assert cn["rays"] == ocn["rays"] and cn["primary"] == w * h * spp
+        assert np.array_equal(_bits(rgb), _bits(ref))
+
+
 def test_progressive_ragged_passes_and_bad_ranges(rtk, ora):
     import torch
 

@@ -363,7 +363,7 @@ def test_sharded_frames_assemble_to_the_unsharded_frame(rtk, ora, scene, w, h, w
 @pytest.mark.parametrize("mode", ["group4", "wave", "lane", "group16"])
 def test_cost_feedback_reorders_blocks_but_not_results(rtk, ora, mode):
     """From the second frame of a shape on, the megakernel starts its pixel blocks most-expensive-first, using the cycle
-    counts the previous frame reported (api.hip "cost feedback").  Frames 1, 2, 3 must all be the oracle's frame, also when
+    counts the previous frame reported (api_frame.hip render_megakernel).  Frames 1, 2, 3 must all be the oracle's frame, also when
     another shape is rendered in between, and for a rank of a sharded frame."""
     import torch
 
@@ -413,7 +413,7 @@ def test_early_exit_occlusion_queries_change_the_work_not_the_frame(rtk, ora, mo
 @pytest.mark.parametrize("scene,depth,gi", [("scene8", 10, 0), ("hw15_scene2", 5, 1)])
 def test_auto_engine_trials_on_forking_scenes_keep_the_frame(rtk, ora, scene, depth, gi):
     """RTK_TRACE_AUTO on a scene whose ray trees fork times the streaming pipeline and the megakernel on the first frames of
-    a shape and keeps the faster (api.hip).  Whichever engine a frame goes through, it is the oracle's frame."""
+    a shape and keeps the faster (api_frame.hip choose_engine).  Whichever engine a frame goes through, it is the oracle's frame."""
     acc, oacc = _scene_pair(rtk, ora, CONFIG_SCENES[scene])
     ref, ocn = oacc.render(240, 136, 2, depth, gi)
     cfg = rtk.RenderConfig(width=240, height=136, spp=2, max_ray_depth=depth, diffuse_rays=gi)

@@ -25,7 +25,7 @@ MISS = 0xFFFFFFFF
 
 
 def _first_caps(n_nodes, n_tris, max_depth):
-    """(cap_nodes, cap_refs) of an accel's FIRST update, from the tree it holds then: api.hip, update_vertices_impl, `max_nodes`,
+    """(cap_nodes, cap_refs) of an accel's FIRST update, from the tree it holds then: api_update.hip, update_vertices_impl, `max_nodes`,
     `want_nodes`, `want_refs` and their clamps at the head of the retry loop.  Later updates keep what the last one ended with."""
     max_nodes = (1 << (max_depth + 1)) - 1
     want_nodes = min(max(1024, 4 * n_nodes), max_nodes)
@@ -267,7 +267,7 @@ def _check_scaled_state(rtk, ora, acc, flat, unit, s, what):
 
 
 def test_an_update_across_the_bundle_limit_switches_bundle_culling(rtk, ora):
-    """coords_small (api.hip) is recomputed by every update from kBuildCoordsBig: above kBundleLimit the interval arithmetic of
+    """coords_small (api_update.hip) is recomputed by every update from kBuildCoordsBig: above kBundleLimit the interval arithmetic of
     bundle culling may overflow and must be off, below it is on again.  Up across the limit, down to just under it, down to
     the scene as loaded; and an accel BUILT above the limit comes down.  (What this pins are the results on both sides of the
     limit.  The flag alone is not observable here: a library with coords_small forced on passed this test)"""

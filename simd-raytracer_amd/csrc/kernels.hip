@@ -5,34 +5,10 @@
 
 #include "kernels.hpp"
 #include "trace.hip.hpp"
-#include "common.hip.hpp"
+#include "shade.hip.hpp"
 
 namespace rtk {
 namespace dev {
-
-// ------------------------------------------------------------------------------------------------
-// node staging: the whole traversal-ordered node array goes to LDS with coalesced 16-byte loads.
-__device__ __forceinline__ void stage_nodes(const DevNode *g_nodes, uint32_t n_nodes, DevNode *lds_nodes) {
-    const float4 *src = reinterpret_cast<const float4 *>(g_nodes);
-    float4 *dst = reinterpret_cast<float4 *>(lds_nodes);
-    for (uint32_t i = threadIdx.x; i < n_nodes * 2u; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-}
-
-__device__ __forceinline__ void flush_stats(const Stats &st, uint32_t rays, unsigned long long *counters) {
-    // counters: rays, primary, hits, nodes, boxpass, leaves, tris, packets16 (rtk_counters order)
-    const uint32_t r = wave_sum(rays), h = wave_sum(st.hits), nd = wave_sum(st.nodes), bp = wave_sum(st.boxpass),
-                   lv = wave_sum(st.leaves), tr = wave_sum(st.tris), pk = wave_sum(st.packets16);
-    if ((threadIdx.x & 63u) == 0u) {
-        atomicAdd(counters + 0, (unsigned long long)r);
-        atomicAdd(counters + 2, (unsigned long long)h);
-        atomicAdd(counters + 3, (unsigned long long)nd);
-        atomicAdd(counters + 4, (unsigned long long)bp);
-        atomicAdd(counters + 5, (unsigned long long)lv);
-        atomicAdd(counters + 6, (unsigned long long)tr);
-        atomicAdd(counters + 7, (unsigned long long)pk);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // accel.intersect<cull>(ray) for a batch (kd_tree_simd.hpp:187-264): lane i takes ray i.
@@ -149,16 +125,11 @@ struct ShadowBurstService {
             if (job >= n_jobs) break;
             const uint32_t k = first + (job >> plog);                        // this job's light (< n_lights: the owner counted the jobs)
             const uint32_t part = job & ((1u << plog) - 1u);
-            const float PI_F = 3.14159265358979323846f;
             const DevLight *L = A.lights + k;                                // wave-uniform
             const V3 lp = mk(L->pos[0], L->pos[1], L->pos[2]);
-            V3 ld = lp - P;                                                  // the light loop body of k_render's ST_LIGHT, verbatim
-            const float radius = length(ld);
-            const float area = 4.0f * PI_F * radius * radius;
-            ld = normalized(ld);
-            const float d0 = dot(ld, ncos);
-            const float cosine = (0.0f < d0) ? d0 : 0.0f;
-            const float contrib = (L->intensity / area) * cosine;
+            const LightTerm lt = light_term(L, P, ncos);
+            const V3 ld = lt.dir;
+            const float radius = lt.radius, contrib = lt.contrib;
             const bool mine = in_burst & (burst_part(ld, in_burst, plog) == part);
             const bool asked = mine & (0.0f < radius);                       // is_occluded's loop guard, render.hpp:114
             // counted, not traced, when it cannot light the lane (unlit_query(); b.z = the lane's albedo_reach).  A job none of
@@ -281,6 +252,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const unsigned long long cost_t0 = __builtin_readcyclecounter();
     const unsigned long long real_t0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz, for the frame's critical path (bench.py)
     constexpr bool writer = true;
+    // (block_map() / block_pixel() written out: through them the benchmark's kernel loses its register allocation)
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
     const uint32_t local_bucket = gwave / bpb, sub = gwave % bpb;
     const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
@@ -288,7 +260,6 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
     const uint32_t sub_x0 = (sub % A.blocks_per_bucket_side) * 8u, sub_y0 = (sub / A.blocks_per_bucket_side) * 8u;   // wave-uniform
     // this lane's pixel: recomputed where it is needed (see fresh_lane) instead of living in registers across the traversal
-    struct Pixel { uint32_t lx, ly, px, py; };
     const auto my_pixel = [&]() {
         const uint32_t l = fresh_lane();
         Pixel p;
@@ -306,7 +277,6 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
 #endif
     const V3 background = mk(A.background[0], A.background[1], A.background[2]);
     const V3 black = mk(0.f, 0.f, 0.f);
-    const float PI_F = 3.14159265358979323846f;
     const uint32_t seed_hash = pcg_hash(A.seed);
 
     // ---- per-lane path state
@@ -377,48 +347,30 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 if (kind == RTK_MAT_CONSTANT) {
                     ret = mk(mat->albedo[0], mat->albedo[1], mat->albedo[2]);                  // :302-303
                     state = ST_RETURN;
-                } else if (kind == RTK_MAT_REFLECTIVE) {                                        // :239-250
-                    const V3 rd = din - ((2.0f * dot(din, hn)) * hn);
-                    const V3 ro = P + (A.reflection_bias * rd);
+                } else if (kind == RTK_MAT_REFLECTIVE) {
+                    const RayOD refl = reflect_at(P, hn, din, A.reflection_bias);
                     // the reflected line leaves the mirror image of the incoming line's apex: as far behind P as that apex was
-                    mirror_apex = P - ((length(P - mirror_apex) / length(rd)) * rd);
-                    ray = spawn_ray(ro, rd);
+                    mirror_apex = P - ((length(P - mirror_apex) / length(refl.d)) * refl.d);
+                    ray = spawn_ray(refl.o, refl.d);
                     rkey = child_key(rkey, 0u);
                     cull = false; depth += 1; pend = PEND_CHILD_BG;
                     state = ST_TRACE;
-                } else if (FORKS && kind == RTK_MAT_REFRACTIVE) {                               // :252-301 (FORKS = the general kernel)
-                    V3 n = normalized(mat->smooth ? hn : fn);
-                    const V3 i = normalized(din);
-                    float eta_i = 1.0f, eta_r = mat->ior;
-                    if (0.0f < dot(i, n)) { const float tmp = eta_i; eta_i = eta_r; eta_r = tmp; n = neg(n); }
-                    const float cos_i_n = -dot(i, n);
-                    const float sin_i_n = __builtin_sqrtf(1.0f - cos_i_n * cos_i_n);
-                    const V3 rd = i - ((2.0f * dot(i, n)) * n);
-                    const V3 ro = P + (A.reflection_bias * rd);
-                    if (eta_r / eta_i < sin_i_n) {                                              // total internal reflection
-                        ray = spawn_ray(ro, rd);
-                        rkey = child_key(rkey, 0u);
-                        cull = false; depth += 1; pend = PEND_CHILD_BLACK;
-                        state = ST_TRACE;
+                } else if (FORKS && kind == RTK_MAT_REFRACTIVE) {                               // (FORKS = the general kernel)
+                    const Refraction rf = refract_at(A, mat, P, mat->smooth ? hn : fn, din);
+                    if (rf.tir) {
+                        ray = spawn_ray(rf.refl.o, rf.refl.d);
                     } else {
-                        const float sin_r = ((sin_i_n * eta_i) / eta_r);
-                        const float cos_r = __builtin_sqrtf(1.0f - sin_r * sin_r);
-                        const V3 r = (cos_r * neg(n)) + (sin_r * normalized(i + (cos_i_n * n)));
-                        const double x = (double)(1.0f + dot(i, n));                           // :300, x^5 in double
-                        const float fresnel = (float)(0.5 * (x * x * x * x * x));
-                        if (FORKS) {
-                            Frame &f = frames[fsp++];
-                            f.a[0] = ro.x; f.a[1] = ro.y; f.a[2] = ro.z;
-                            f.a[3] = rd.x; f.a[4] = rd.y; f.a[5] = rd.z;
-                            f.a[6] = fresnel;
-                            f.meta = FR_REFR_A | ((uint32_t)depth << 8);
-                            f.key = rkey;
-                        }
-                        ray = spawn_ray(P + (A.refraction_bias * r), r);
-                        rkey = child_key(rkey, 0u);
-                        cull = false; depth += 1; pend = PEND_CHILD_BLACK;
-                        state = ST_TRACE;
+                        Frame &f = frames[fsp++];                                               // the reflection ray waits for the refraction's subtree
+                        f.a[0] = rf.refl.o.x; f.a[1] = rf.refl.o.y; f.a[2] = rf.refl.o.z;
+                        f.a[3] = rf.refl.d.x; f.a[4] = rf.refl.d.y; f.a[5] = rf.refl.d.z;
+                        f.a[6] = rf.fresnel;
+                        f.meta = FR_REFR_A | ((uint32_t)depth << 8);
+                        f.key = rkey;
+                        ray = spawn_ray(rf.refr.o, rf.refr.d);
                     }
+                    rkey = child_key(rkey, 0u);
+                    cull = false; depth += 1; pend = PEND_CHILD_BLACK;
+                    state = ST_TRACE;
                 } else {                                                                        // diffuse :148-209, texture :211-238
                     lit_textured = FORKS && (kind == RTK_MAT_TEXTURE); // light loop only: no GI rays, no final division
                     if (!lit_textured) albedo = mk(mat->albedo[0], mat->albedo[1], mat->albedo[2]);
@@ -448,17 +400,11 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                     state = ST_RETURN;
                     continue;
                 }
-                const DevLight *L = A.lights + light_k;
-                V3 ld = mk(L->pos[0], L->pos[1], L->pos[2]) - P;
-                const float radius = length(ld);
-                const float area = 4.0f * PI_F * radius * radius;
-                ld = normalized(ld);
-                const float d0 = dot(ld, ncos);
-                const float cosine = (0.0f < d0) ? d0 : 0.0f;                // std::max(0, dot)
-                contrib = (L->intensity / area) * cosine;
-                if (0.0f < radius) {                                         // is_occluded's loop guard, :114
-                    ray = spawn_ray(P + (A.shadow_bias * ld), ld);
-                    shadow_max_t = radius;
+                const LightTerm lt = light_term(A.lights + light_k, P, ncos);
+                contrib = lt.contrib;
+                if (0.0f < lt.radius) {                                      // is_occluded's loop guard, :114
+                    ray = spawn_ray(P + (A.shadow_bias * lt.dir), lt.dir);
+                    shadow_max_t = lt.radius;
                     cull = false; pend = PEND_SHADOW;
                     state = ST_TRACE;
                 } else {
@@ -495,24 +441,8 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                     const V3 fhn = mk(f.a[6], f.a[7], f.a[8]);
                     if (it < A.diffuse_rays) {
                         f.meta = FR_DIFFUSE | ((uint32_t)fdepth << 8) | ((uint32_t)it << 16);
-                        const V3 fd = mk(f.a[3], f.a[4], f.a[5]);
-                        const V3 right = normalized(cross(fd, fhn));
-                        const V3 up = fhn;
-                        const V3 fwd = cross(right, up);
-                        const float a_xy = PI_F * urand_key(f.key, 2u + 2u * (uint32_t)it);
-                        float s1, c1;
-                        det_sincos(a_xy, s1, c1);
-                        V3 rv = mk(c1, s1, 0.0f);
-                        const float a_xz = PI_F * urand_key(f.key, 3u + 2u * (uint32_t)it) * 2.0f;
-                        float s2, c2;
-                        det_sincos(a_xz, s2, c2);
-                        rv = mk(c2 * rv.x + 0.0f * rv.y + (-s2) * rv.z, 0.0f * rv.x + 1.0f * rv.y + 0.0f * rv.z,
-                                s2 * rv.x + 0.0f * rv.y + c2 * rv.z);
-                        const V3 org = fP + (A.reflection_bias * fhn);
-                        const V3 dir = mk(right.x * rv.x + right.y * rv.y + right.z * rv.z,
-                                          up.x * rv.x + up.y * rv.y + up.z * rv.z,
-                                          fwd.x * rv.x + fwd.y * rv.y + fwd.z * rv.z);
-                        ray = spawn_ray(org, dir);
+                        const RayOD gi = gi_ray(fP, fhn, mk(f.a[3], f.a[4], f.a[5]), f.key, (uint32_t)it, A.reflection_bias);
+                        ray = spawn_ray(gi.o, gi.d);
                         rkey = child_key(f.key, (uint32_t)it);
                         cull = false; depth = fdepth + 1; pend = PEND_CHILD_BLACK;
                         state = ST_TRACE;
@@ -577,16 +507,8 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 if (burst && A.skip_unlit != 0) {
                     // no burst when no shadow lane is lit by any of its lights: nobody would trace anything
                     bool lit = sh_lane & !unlit;
-                    for (uint32_t s = 1u; s < burst_nl; ++s) {
-                        const DevLight *L = A.lights + burst_k + s;                          // wave-uniform
-                        V3 ld = mk(L->pos[0], L->pos[1], L->pos[2]) - P;                     // the light loop body of ST_LIGHT, verbatim
-                        const float radius = length(ld);
-                        const float area = 4.0f * PI_F * radius * radius;
-                        ld = normalized(ld);
-                        const float d0 = dot(ld, ncos);
-                        const float cosine = (0.0f < d0) ? d0 : 0.0f;
-                        lit |= sh_lane & !unlit_query((L->intensity / area) * cosine, reach);
-                    }
+                    for (uint32_t s = 1u; s < burst_nl; ++s)                                // (the light is wave-uniform)
+                        lit |= sh_lane & !unlit_query(light_term(A.lights + burst_k + s, P, ncos).contrib, reach);
                     burst = wave_any(lit);
                 }
                 if (burst) burst_my_part = burst_part(ray.d, sh_lane, burst_plog);   // (every shadow lane of a burst is at light burst_k)
@@ -692,6 +614,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
             more_rays = 1u;
             const bool hit = cand.k != kMiss;
             if (pend == PEND_SHADOW) {                                       // is_occluded, render.hpp:110-131
+                // (occlusion_step() written out: calling it here costs the benchmark's kernel its register allocation)
                 bool clear = !hit | (shadow_max_t < cand.t);
                 const bool in_burst = SLICES > 1 && burst_done && ((burst_lanes >> lane) & 1ull) != 0ull;
                 const uint32_t my_part = in_burst ? burst_part0 : 0u;
@@ -805,6 +728,7 @@ __global__ __launch_bounds__(64 * SLICES, 8) void k_primary(RenderArgs A) {
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gwave = blockIdx.x;
+    // (block_map() / block_pixel() written out, as in k_render)
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
     const uint32_t local_bucket = gwave / bpb, sub = gwave % bpb;
     const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
@@ -987,12 +911,9 @@ namespace dev {
 __global__ __launch_bounds__(256) void k_block_prior(RenderArgs A, uint8_t *cls, uint32_t *count /* [3], zeroed */) {
     const uint32_t unit = blockIdx.x * blockDim.x + threadIdx.x;
     const bool have = unit < A.n_units;
-    const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint32_t local_bucket = (have ? unit : 0u) / bpb, sub = (have ? unit : 0u) % bpb;
-    const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
-    const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
-    const uint32_t x0 = bx + (sub % A.blocks_per_bucket_side) * 8u, y0 = by + (sub / A.blocks_per_bucket_side) * 8u;
-    const bool in_frame = have && bucket < A.n_buckets && x0 < A.width && y0 < A.height;
+    const BlockMap blk = block_map(A, have ? unit : 0u);
+    const uint32_t x0 = blk.bx + blk.sub_x0, y0 = blk.by + blk.sub_y0;
+    const bool in_frame = have && blk.bucket < A.n_buckets && x0 < A.width && y0 < A.height;
     const uint32_t x1 = x0 + 7u < A.width ? x0 + 7u : A.width - 1u, y1 = y0 + 7u < A.height ? y0 + 7u : A.height - 1u;
     RenderArgs P = A;
     P.spp = 1;                                                                  // pixel centres: this is an estimate

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "occluded.hpp"
-#include "trace.hip.hpp"
+#include "shade.hip.hpp"
 
 namespace rtk {
 namespace dev {
@@ -16,12 +16,7 @@ template <int MODE, bool LDS_NODES>
 __global__ __launch_bounds__(256) void k_occluded(OccludedArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
-    if (LDS_NODES) {
-        const float4 *src = reinterpret_cast<const float4 *>(A.tree.nodes);
-        float4 *dst = reinterpret_cast<float4 *>(lds_nodes);
-        for (uint32_t i = threadIdx.x; i < A.tree.n_nodes * 2u; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
+    if (LDS_NODES) stage_nodes(A.tree.nodes, A.tree.n_nodes, lds_nodes);
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < A.n;
     Ray r;
@@ -46,22 +41,10 @@ __global__ __launch_bounds__(256) void k_occluded(OccludedArgs A) {
         const Cand c = trace<MODE, false, LDS_NODES>(A.tree, lds_nodes, r, false, pending, st, sx, kAutoMinLanes, exit_t);
         if (pending) {
             queries += 1u;
-            bool again = false;
-            if ((c.k == kMiss) | (max_t < c.t)) {                            // :117
-                answer = RTK_OCC_CLEAR;
-            } else {
-                answer = RTK_OCC_OCCLUDED;
-                if (A.has_refractive) {
-                    const uint32_t m = A.tree.shade[A.tree.tri_ids[c.k]].material;
-                    if (A.materials[m].kind == RTK_MAT_REFRACTIVE) {         // transmissive: step through, :126-127
-                        const V3 hp = r.o + (c.t * r.d);
-                        r.o = hp + (A.shadow_bias * r.d);
-                        max_t -= c.t;
-                        answer = RTK_OCC_CLEAR;                              // (what the guard says if it ends the loop now)
-                        again = 0.0f < max_t;
-                    }
-                }
-            }
+            const OccStep os = occlusion_step(A.tree, A.materials, A.shadow_bias, A.has_refractive, c, r.o, r.d, max_t);
+            r.o = os.o; max_t = os.max_t;
+            answer = os.answer == OCC_OCCLUDED ? RTK_OCC_OCCLUDED : RTK_OCC_CLEAR;
+            bool again = os.answer == OCC_AGAIN;
             if (again & (queries == (uint32_t)RTK_OCCLUDED_MAX_STEPS)) { answer = RTK_OCC_STEP_LIMIT; again = false; }
             pending = again;
         }

@@ -7,7 +7,7 @@
 // traces are the per-lane walk, and nothing but exactness is asked of it.
 #include <hip/hip_runtime.h>
 
-#include "common.hip.hpp"
+#include "shade.hip.hpp"
 #include "stream.hpp"
 
 namespace rtk {
@@ -46,17 +46,11 @@ __global__ __launch_bounds__(256) void k_radiance_fallback(StreamArgs S, unsigne
     const RenderArgs &A = S.r;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
-    if (LDS_NODES) {
-        const float4 *src = reinterpret_cast<const float4 *>(A.tree.nodes);
-        float4 *dst = reinterpret_cast<float4 *>(lds_nodes);
-        for (uint32_t i = threadIdx.x; i < A.tree.n_nodes * 2u; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
+    if (LDS_NODES) stage_nodes(A.tree.nodes, A.tree.n_nodes, lds_nodes);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool have = i < S.user_n;
     const V3 background = mk(A.background[0], A.background[1], A.background[2]);
     const V3 black = mk(0.f, 0.f, 0.f);
-    const float PI_F = 3.14159265358979323846f;
     const uint32_t n_lights = (uint32_t)A.n_lights;
 
     RadFrame stack[kMaxRayDepth + 1];
@@ -89,21 +83,12 @@ __global__ __launch_bounds__(256) void k_radiance_fallback(StreamArgs S, unsigne
         // what the trace means for this lane: a value to hand to the caller (`ret`), a new frame, or the next shadow step
         bool returning = false, advance = false;
         V3 ret = black;
-        if (state == ST_SHADOW) {                                            // is_occluded, render.hpp:110-131
+        if (state == ST_SHADOW) {
             RadFrame &f = stack[sp - 1u];
-            bool clr = (c.k == kMiss) | (max_t < c.t);                       // :117
-            bool again = false;
-            if (!clr && A.has_refractive) {
-                const uint32_t m = A.tree.shade[A.tree.tri_ids[c.k]].material;
-                if (A.materials[m].kind == RTK_MAT_REFRACTIVE) {             // transmissive: step through, :126-127
-                    const V3 hp = ray.o + (c.t * ray.d);
-                    ray = make_ray(hp + (A.shadow_bias * ray.d), ray.d);
-                    max_t -= c.t;
-                    if (0.0f < max_t) again = true; else clr = true;
-                }
-            }
-            if (!again) {
-                if (clr) f.acc = f.acc + (f.contrib * f.albedo);
+            const OccStep os = occlusion_step(A.tree, A.materials, A.shadow_bias, A.has_refractive, c, ray.o, ray.d, max_t);
+            ray.o = os.o; max_t = os.max_t;
+            if (os.answer != OCC_AGAIN) {
+                if (os.answer == OCC_CLEAR) f.acc = f.acc + (f.contrib * f.albedo);
                 f.light += 1u;
                 advance = true;
             }
@@ -122,32 +107,20 @@ __global__ __launch_bounds__(256) void k_radiance_fallback(StreamArgs S, unsigne
                 f.key = key; f.step = 0u; f.light = 0u; f.acc = black; f.P = P; f.hn = hn; f.d = ray.d;
                 f.contrib = 0.0f; f.fresnel = 0.0f; f.c1o = black; f.c1d = black; f.ncos = black; f.albedo = black;
                 if (mkind == RTK_MAT_CONSTANT) { ret = mk(m->albedo[0], m->albedo[1], m->albedo[2]); returning = true; }
-                else if (mkind == RTK_MAT_REFLECTIVE) {                                         // :239-250
-                    const V3 rd = ray.d - ((2.0f * dot(ray.d, hn)) * hn);
-                    const V3 ro = P + (A.reflection_bias * rd);
+                else if (mkind == RTK_MAT_REFLECTIVE) {
+                    const RayOD refl = reflect_at(P, hn, ray.d, A.reflection_bias);
                     f.kind = NODE_PASS; sp += 1u;
-                    ray = make_ray(ro, rd); key = child_key(f.key, 0u); miss_bg = true;
-                } else if (mkind == RTK_MAT_REFRACTIVE) {                                       // :252-301
-                    V3 n = normalized(m->smooth ? hn : s.face_normal);
-                    const V3 iv = normalized(ray.d);
-                    float eta_i = 1.0f, eta_r = m->ior;
-                    if (0.0f < dot(iv, n)) { const float tmp = eta_i; eta_i = eta_r; eta_r = tmp; n = neg(n); }
-                    const float cos_i_n = -dot(iv, n);
-                    const float sin_i_n = __builtin_sqrtf(1.0f - cos_i_n * cos_i_n);
-                    const V3 rd = iv - ((2.0f * dot(iv, n)) * n);
-                    const V3 ro = P + (A.reflection_bias * rd);
-                    if (eta_r / eta_i < sin_i_n) {                                              // total internal reflection
+                    ray = make_ray(refl.o, refl.d); key = child_key(f.key, 0u); miss_bg = true;
+                } else if (mkind == RTK_MAT_REFRACTIVE) {
+                    const Refraction rf = refract_at(A, m, P, m->smooth ? hn : s.face_normal, ray.d);
+                    if (rf.tir) {
                         f.kind = NODE_PASS; sp += 1u;
-                        ray = make_ray(ro, rd); key = child_key(f.key, 0u); miss_bg = false;
+                        ray = make_ray(rf.refl.o, rf.refl.d); key = child_key(f.key, 0u); miss_bg = false;
                     } else {
-                        const float sin_r = ((sin_i_n * eta_i) / eta_r);
-                        const float cos_r = __builtin_sqrtf(1.0f - sin_r * sin_r);
-                        const V3 r = (cos_r * neg(n)) + (sin_r * normalized(iv + (cos_i_n * n)));
-                        const double x = (double)(1.0f + dot(iv, n));                          // :300, x^5 in double
-                        f.fresnel = (float)(0.5 * (x * x * x * x * x));
-                        f.c1o = ro; f.c1d = rd;
+                        f.fresnel = rf.fresnel;
+                        f.c1o = rf.refl.o; f.c1d = rf.refl.d;
                         f.kind = NODE_REFR; sp += 1u;
-                        ray = make_ray(P + (A.refraction_bias * r), r); key = child_key(f.key, 0u); miss_bg = false;
+                        ray = make_ray(rf.refr.o, rf.refr.d); key = child_key(f.key, 0u); miss_bg = false;
                     }
                 } else if (mkind == RTK_MAT_TEXTURE) {                                          // :211-238
                     f.ncos = m->smooth ? hn : s.face_normal;
@@ -180,39 +153,22 @@ __global__ __launch_bounds__(256) void k_radiance_fallback(StreamArgs S, unsigne
             }
             advance = false;
             RadFrame &f = stack[sp - 1u];
-            if (f.kind == NODE_DIFF && f.step < (uint32_t)A.diffuse_rays) {                     // GI rays, :151-176
+            if (f.kind == NODE_DIFF && f.step < (uint32_t)A.diffuse_rays) {                     // GI rays
                 const uint32_t gi = f.step;
                 f.step += 1u;
-                const V3 right = normalized(cross(f.d, f.hn));
-                const V3 up = f.hn;
-                const V3 fwd = cross(right, up);
-                float s1, c1, s2, c2;
-                det_sincos(PI_F * urand_key(f.key, 2u + 2u * gi), s1, c1);
-                V3 rv = mk(c1, s1, 0.0f);
-                det_sincos(PI_F * urand_key(f.key, 3u + 2u * gi) * 2.0f, s2, c2);
-                rv = mk(c2 * rv.x + 0.0f * rv.y + (-s2) * rv.z, 0.0f * rv.x + 1.0f * rv.y + 0.0f * rv.z,
-                        s2 * rv.x + 0.0f * rv.y + c2 * rv.z);
-                const V3 org = f.P + (A.reflection_bias * f.hn);
-                const V3 dir = mk(right.x * rv.x + right.y * rv.y + right.z * rv.z, up.x * rv.x + up.y * rv.y + up.z * rv.z,
-                                  fwd.x * rv.x + fwd.y * rv.y + fwd.z * rv.z);
-                ray = make_ray(org, dir); key = child_key(f.key, gi); miss_bg = false; state = ST_TRACE;
+                const RayOD g = gi_ray(f.P, f.hn, f.d, f.key, gi, A.reflection_bias);
+                ray = make_ray(g.o, g.d); key = child_key(f.key, gi); miss_bg = false; state = ST_TRACE;
                 break;
             }
             bool shadow = false;
-            while (f.light < n_lights) {                                                        // light loop, :184-206
-                const DevLight *L = A.lights + f.light;
-                V3 ld = mk(L->pos[0], L->pos[1], L->pos[2]) - f.P;
-                const float radius = length(ld);
-                const float area = 4.0f * PI_F * radius * radius;
-                ld = normalized(ld);
-                const float d0 = dot(ld, f.ncos);
-                const float cosine = (0.0f < d0) ? d0 : 0.0f;                                   // std::max(0, dot)
-                const float contrib = (L->intensity / area) * cosine;
-                bool traced = 0.0f < radius;                                                    // is_occluded's loop guard, :114
+            while (f.light < n_lights) {                                                        // light loop
+                const LightTerm lt = light_term(A.lights + f.light, f.P, f.ncos);
+                const float contrib = lt.contrib;
+                bool traced = 0.0f < lt.radius;                                                   // is_occluded's loop guard, :114
                 if (traced && A.skip_unlit != 0 && unlit_query(contrib, albedo_reach(f.albedo))) { traced = false; nrays += 1u; }
                 if (traced) {
                     f.contrib = contrib;
-                    ray = make_ray(f.P + (A.shadow_bias * ld), ld); max_t = radius; state = ST_SHADOW; shadow = true;
+                    ray = make_ray(f.P + (A.shadow_bias * lt.dir), lt.dir); max_t = lt.radius; state = ST_SHADOW; shadow = true;
                     break;
                 }
                 f.acc = f.acc + (contrib * f.albedo);                                           // not occluded

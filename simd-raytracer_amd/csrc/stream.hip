@@ -22,7 +22,7 @@
 // redone by the megakernel — slower, never wrong.
 #include <hip/hip_runtime.h>
 
-#include "common.hip.hpp"
+#include "shade.hip.hpp"
 #include "stream.hpp"
 
 namespace rtk {
@@ -114,19 +114,20 @@ __device__ __forceinline__ void level_range(const uint32_t *count_words, const u
     count = (b + c <= cap) ? (uint32_t)c : cap - base;
 }
 
+// first hit id and hit count (shading points) of depth level `level`, clamped like the nodes'
+__device__ __forceinline__ void hit_range(const uint32_t *ctrl, const uint32_t level, const uint32_t cap, uint32_t &base, uint32_t &count) {
+    unsigned long long b = 0ull;
+    for (uint32_t j = 0; j < level; ++j) b += ctrl[kCtrlHitCount + j];
+    const unsigned long long c = ctrl[kCtrlHitCount + level];
+    base = b < cap ? (uint32_t)b : cap;
+    count = (b + c <= cap) ? (uint32_t)c : cap - base;
+}
+
 __device__ __forceinline__ void add_rays(const StreamArgs &S, const Stats &st, const uint32_t rays, const bool stats,
                                          const uint32_t shard) {
     const uint32_t total = wave_sum(rays);
     unsigned long long *c = S.r.counters;
-    if (stats) {
-        const uint32_t h = wave_sum(st.hits), nd = wave_sum(st.nodes), bp = wave_sum(st.boxpass), lv = wave_sum(st.leaves),
-                       tr = wave_sum(st.tris), pk = wave_sum(st.packets16);
-        if (__lane_id() == 0u) {
-            atomicAdd(c + 2, (unsigned long long)h); atomicAdd(c + 3, (unsigned long long)nd);
-            atomicAdd(c + 4, (unsigned long long)bp); atomicAdd(c + 5, (unsigned long long)lv);
-            atomicAdd(c + 6, (unsigned long long)tr); atomicAdd(c + 7, (unsigned long long)pk);
-        }
-    }
+    if (stats) flush_stats(st, 0u, c);
     if (__lane_id() == 0u && total != 0u) atomicAdd(c + 8 + (shard % (uint32_t)kRayCounterShards), (unsigned long long)total);
 }
 
@@ -181,12 +182,7 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
     constexpr bool kStage = (MODE != RTK_TRACE_WAVE);          // the per-lane walk reads the node array from LDS
-    if (kStage) {
-        const float4 *src = reinterpret_cast<const float4 *>(A.tree.nodes);
-        float4 *dst = reinterpret_cast<float4 *>(lds_nodes);
-        for (uint32_t i = threadIdx.x; i < A.tree.n_nodes * 2u; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
+    if (kStage) stage_nodes(A.tree.nodes, A.tree.n_nodes, lds_nodes);
     // SLICES > 1: the workgroup's wave 0 owns the rays, waves 1.. help with large leaves (trace.hip.hpp)
     __shared__ GroupStorage<(SLICES > 1 ? SLICES : 1)> group_st;
     GroupShared *const group_sh = group_st.get();
@@ -202,7 +198,6 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
     const uint32_t n_units_grid = SLICES > 1 ? gridDim.x : gridDim.x * (blockDim.x >> 6);
     const V3 background = mk(A.background[0], A.background[1], A.background[2]);
     const V3 black = mk(0.f, 0.f, 0.f);
-    const float PI_F = 3.14159265358979323846f;
     const uint32_t level = S.level;
     uint32_t *ctrl = S.ws.ctrl;
     if (ctrl[kCtrlOverflow] != 0u) {                                           // a queue overflowed: the megakernel redoes the frame
@@ -212,6 +207,8 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
     uint32_t base, count;
     level_range(ctrl + kCtrlNodeCount, S.n_level0, level, S.ws.node_cap, base, count);
     const uint32_t next_base = base + count;                                  // where depth level+1 starts
+    // the hits of the shallower levels.  (Not hit_range(): this level's count is what this kernel appends, and wave_append_1
+    // is what holds the sum below hit_cap.)
     uint32_t hit_base = 0u;
     for (uint32_t j = 0; j < level; ++j) hit_base += ctrl[kCtrlHitCount + j];
     const uint32_t n_items = (count + 63u) >> 6;
@@ -257,19 +254,14 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
             key = root_key(pcg_hash(A.seed), id, S.user_sample);
         } else if (SRC == PATH_CAMERA) {
             cull = true;
-            const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
             const uint32_t n_blocks = S.n_root >> 6;                           // items [b * n_blocks, (b + 1) * n_blocks): sample b of the batch
-            const uint32_t blk = item % n_blocks, in_batch = item / n_blocks;
-            const uint32_t local_bucket = blk / bpb, sub = blk % bpb;
-            const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
-            const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
-            const uint32_t lx = (sub % A.blocks_per_bucket_side) * 8u + (lane & 7u);
-            const uint32_t ly = (sub / A.blocks_per_bucket_side) * 8u + (lane >> 3);
-            const uint32_t px = bx + lx, py = by + ly;
-            valid = valid & (bucket < A.n_buckets) & (lx < A.bucket) & (ly < A.bucket) & (px < A.width) & (py < A.height);
-            if (valid) pix = (uint32_t)A.out_index(local_bucket, lx, ly, px, py);
-            key = root_key(pcg_hash(A.seed), py * A.width + px, (uint32_t)S.sample + in_batch);
-            ray = camera_ray(A, px, py, key);
+            const uint32_t in_batch = item / n_blocks;
+            const BlockMap blk = block_map(A, item % n_blocks);
+            const Pixel p = block_pixel(blk, lane);
+            valid = valid & pixel_valid(A, blk, p);
+            if (valid) pix = (uint32_t)A.out_index(blk.local_bucket, p.lx, p.ly, p.px, p.py);
+            key = root_key(pcg_hash(A.seed), p.py * A.width + p.px, (uint32_t)S.sample + in_batch);
+            ray = camera_ray(A, p.px, p.py, key);
         } else {
             const float4 *q = reinterpret_cast<const float4 *>(S.ws.rays + node);
             const float4 a = q[0], b = q[1], c = q[2];
@@ -286,7 +278,7 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
         // ---- color_hit's material switch (render.hpp:133-308): node kind + the rays it spawns
         uint32_t kind = NODE_LEAF, nchild = 0u, aux = 0u, mat = 0u;
         V3 value = black, P = black, hn = black, ncos = black;
-        V3 c0o = black, c0d = black, c1o = black, c1d = black;                  // explicit children (reflect / refract)
+        RayOD c0 = {black, black}, c1 = {black, black};                         // explicit children (reflect / refract)
         bool c0_bg = false, push_hit = false;
         if (valid) {
             if (c.k == kMiss) value = miss_bg ? background : black;
@@ -299,29 +291,16 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
                 const DevMaterial *m = A.materials + mat;
                 const int mkind = m->kind;
                 if (mkind == RTK_MAT_CONSTANT) value = mk(m->albedo[0], m->albedo[1], m->albedo[2]);
-                else if (mkind == RTK_MAT_REFLECTIVE) {                                         // :239-250
-                    c0d = ray.d - ((2.0f * dot(ray.d, hn)) * hn);
-                    c0o = P + (A.reflection_bias * c0d);
+                else if (mkind == RTK_MAT_REFLECTIVE) {
+                    c0 = reflect_at(P, hn, ray.d, A.reflection_bias);
                     c0_bg = true; kind = NODE_PASS; nchild = 1u;
-                } else if (mkind == RTK_MAT_REFRACTIVE) {                                       // :252-301
-                    V3 n = normalized(m->smooth ? hn : s.face_normal);
-                    const V3 i = normalized(ray.d);
-                    float eta_i = 1.0f, eta_r = m->ior;
-                    if (0.0f < dot(i, n)) { const float tmp = eta_i; eta_i = eta_r; eta_r = tmp; n = neg(n); }
-                    const float cos_i_n = -dot(i, n);
-                    const float sin_i_n = __builtin_sqrtf(1.0f - cos_i_n * cos_i_n);
-                    const V3 rd = i - ((2.0f * dot(i, n)) * n);
-                    const V3 ro = P + (A.reflection_bias * rd);
-                    if (eta_r / eta_i < sin_i_n) {                                              // total internal reflection
-                        c0o = ro; c0d = rd; kind = NODE_PASS; nchild = 1u;
+                } else if (mkind == RTK_MAT_REFRACTIVE) {
+                    const Refraction rf = refract_at(A, m, P, m->smooth ? hn : s.face_normal, ray.d);
+                    if (rf.tir) {
+                        c0 = rf.refl; kind = NODE_PASS; nchild = 1u;
                     } else {
-                        const float sin_r = ((sin_i_n * eta_i) / eta_r);
-                        const float cos_r = __builtin_sqrtf(1.0f - sin_r * sin_r);
-                        const V3 r = (cos_r * neg(n)) + (sin_r * normalized(i + (cos_i_n * n)));
-                        const double x = (double)(1.0f + dot(i, n));                           // :300, x^5 in double
-                        aux = __float_as_uint((float)(0.5 * (x * x * x * x * x)));
-                        c0o = P + (A.refraction_bias * r); c0d = r;                             // child 0: refraction
-                        c1o = ro; c1d = rd;                                                     // child 1: reflection
+                        aux = __float_as_uint(rf.fresnel);
+                        c0 = rf.refr; c1 = rf.refl;                                             // child 0: refraction, child 1: reflection
                         kind = NODE_REFR; nchild = 2u;
                     }
                 } else if (mkind == RTK_MAT_TEXTURE) {                                          // :211-238
@@ -341,12 +320,12 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
         const uint32_t first_child = next_base + child_slot;
         const bool spawn01 = kind == NODE_PASS || kind == NODE_REFR;
         if (spawn01) {
-            store_ray(S.ws.rays + first_child, c0o, c0d, node, pix, child_key(key, 0u), kRayValid | (c0_bg ? kRayMissBackground : 0u));
-            if (kind == NODE_REFR) store_ray(S.ws.rays + first_child + 1u, c1o, c1d, node, pix, child_key(key, 1u), kRayValid);
+            store_ray(S.ws.rays + first_child, c0.o, c0.d, node, pix, child_key(key, 0u), kRayValid | (c0_bg ? kRayMissBackground : 0u));
+            if (kind == NODE_REFR) store_ray(S.ws.rays + first_child + 1u, c1.o, c1.d, node, pix, child_key(key, 1u), kRayValid);
         }
         if (S.bin_children) {                                                                   // (wave-wide: bin_count)
-            bin_count(S.ws.node_bins, ray_sort_key(S, c0o, c0d), spawn01);
-            bin_count(S.ws.node_bins, ray_sort_key(S, c1o, c1d), kind == NODE_REFR);
+            bin_count(S.ws.node_bins, ray_sort_key(S, c0.o, c0.d), spawn01);
+            bin_count(S.ws.node_bins, ray_sort_key(S, c1.o, c1.d), kind == NODE_REFR);
         }
         const bool shade_point = kind == NODE_DIFF || kind == NODE_TEX;
         if (S.bin_hits) bin_count(S.ws.hit_bins, grid_cell(S, P), shade_point);
@@ -356,25 +335,14 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_path(StreamArgs S) {
             q[0] = make_float4(P.x, P.y, P.z, __uint_as_float(node));
             q[1] = make_float4(ncos.x, ncos.y, ncos.z, __uint_as_float(mat));
         }
-        // GI rays, :151-176.  The loop runs wave-wide (diffuse_rays is uniform; `mine` says whose ray it is) so that the
+        // GI rays.  The loop runs wave-wide (diffuse_rays is uniform; `mine` says whose ray it is) so that the
         // histogram of the spawned rays can be counted per wave (bin_count); a lane's arithmetic is what it was.
         if (wave_any(shade_point && nchild != 0u)) {
             for (uint32_t gi = 0; gi < (uint32_t)A.diffuse_rays; ++gi) {
                 const bool mine = shade_point && gi < nchild;
-                const V3 right = normalized(cross(ray.d, hn));
-                const V3 up = hn;
-                const V3 fwd = cross(right, up);
-                float s1, c1, s2, c2;
-                det_sincos(PI_F * urand_key(key, 2u + 2u * gi), s1, c1);
-                V3 rv = mk(c1, s1, 0.0f);
-                det_sincos(PI_F * urand_key(key, 3u + 2u * gi) * 2.0f, s2, c2);
-                rv = mk(c2 * rv.x + 0.0f * rv.y + (-s2) * rv.z, 0.0f * rv.x + 1.0f * rv.y + 0.0f * rv.z,
-                        s2 * rv.x + 0.0f * rv.y + c2 * rv.z);
-                const V3 org = P + (A.reflection_bias * hn);
-                const V3 dir = mk(right.x * rv.x + right.y * rv.y + right.z * rv.z, up.x * rv.x + up.y * rv.y + up.z * rv.z,
-                                  fwd.x * rv.x + fwd.y * rv.y + fwd.z * rv.z);
-                if (mine) store_ray(S.ws.rays + first_child + gi, org, dir, node, pix, child_key(key, gi), kRayValid);
-                if (S.bin_children) bin_count(S.ws.node_bins, ray_sort_key(S, org, dir), mine);
+                const RayOD g = gi_ray(P, hn, ray.d, key, gi, A.reflection_bias);
+                if (mine) store_ray(S.ws.rays + first_child + gi, g.o, g.d, node, pix, child_key(key, gi), kRayValid);
+                if (S.bin_children) bin_count(S.ws.node_bins, ray_sort_key(S, g.o, g.d), mine);
             }
         }
         if (in_range) {
@@ -396,12 +364,7 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_shadow(StreamArgs S) 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
     constexpr bool kStage = (MODE != RTK_TRACE_WAVE);
-    if (kStage) {
-        const float4 *src = reinterpret_cast<const float4 *>(A.occl_on ? A.occl.nodes : A.tree.nodes);
-        float4 *dst = reinterpret_cast<float4 *>(lds_nodes);
-        for (uint32_t i = threadIdx.x; i < A.tree.n_nodes * 2u; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
+    if (kStage) stage_nodes(A.occl_on ? A.occl.nodes : A.tree.nodes, A.tree.n_nodes, lds_nodes);
     __shared__ GroupStorage<(SLICES > 1 ? SLICES : 1)> group_st;
     GroupShared *const group_sh = group_st.get();
     // SLICES > 1: role 0 = owner; the owner role rotates with the workgroup index so that owners spread over the SIMDs
@@ -419,17 +382,10 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_shadow(StreamArgs S) 
         if (SLICES > 1) group_post_exit(group_sh);
         return;
     }
-    uint32_t hit_base = 0u, n_hits = 0u;
-    {
-        unsigned long long hb = 0ull;
-        for (uint32_t j = 0; j < S.level; ++j) hb += ctrl[kCtrlHitCount + j];
-        const unsigned long long hc = ctrl[kCtrlHitCount + S.level];
-        hit_base = hb < S.ws.hit_cap ? (uint32_t)hb : S.ws.hit_cap;
-        n_hits = (hb + hc <= S.ws.hit_cap) ? (uint32_t)hc : S.ws.hit_cap - hit_base;
-    }
+    uint32_t hit_base, n_hits;
+    hit_range(ctrl, S.level, S.ws.hit_cap, hit_base, n_hits);
     const uint32_t n_lights = (uint32_t)A.n_lights;
     const uint32_t n_items = ((n_hits + 63u) >> 6) * n_lights;
-    const float PI_F = 3.14159265358979323846f;
     Stats st = {0, 0, 0, 0, 0, 0};
     // bundles of the current trace (trace.hip.hpp "Bundle culling"): the group's shared block, or one area per wave when every wave owns rays
     __shared__ __attribute__((aligned(16))) float wave_bundles[SLICES > 1 ? 1 : 4][kMaxBundles * kBundleFloats];
@@ -453,16 +409,11 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_shadow(StreamArgs S) 
         const float4 a = q[0], b = q[1];
         const V3 P = mk(a.x, a.y, a.z), ncos = mk(b.x, b.y, b.z);
         const DevLight *L = A.lights + k;                                    // wave-uniform
-        V3 ld = mk(L->pos[0], L->pos[1], L->pos[2]) - P;
-        const float radius = length(ld);
-        const float area = 4.0f * PI_F * radius * radius;
-        ld = normalized(ld);
-        const float d0 = dot(ld, ncos);
-        const float cosine = (0.0f < d0) ? d0 : 0.0f;                        // std::max(0, dot)
-        const float contrib = (L->intensity / area) * cosine;
-        Ray ray = make_ray(P + (A.shadow_bias * ld), ld);
-        float max_t = radius;
-        bool pending = valid & (0.0f < radius);                              // is_occluded's loop guard, render.hpp:114
+        const LightTerm lt = light_term(L, P, ncos);
+        const float contrib = lt.contrib;
+        Ray ray = make_ray(P + (A.shadow_bias * lt.dir), lt.dir);
+        float max_t = lt.radius;
+        bool pending = valid & (0.0f < lt.radius);                             // is_occluded's loop guard, render.hpp:114
         bool clear = true;
         if (A.skip_unlit != 0 && pending) {
             // a query that adds +-0 whatever its answer is counted and left "clear", not traced (common.hip.hpp, unlit_query);
@@ -481,18 +432,10 @@ __global__ __launch_bounds__(256, RTK_STREAM_WAVES) void k_shadow(StreamArgs S) 
                                                               kClsHasApex | k, mk(L->pos[0], L->pos[1], L->pos[2]));
             if (pending) {
                 nrays += 1u;
-                bool clr = (c.k == kMiss) | (max_t < c.t);                   // :117
-                bool again = false;
-                if (!clr && A.has_refractive && !A.occl_on) {
-                    const uint32_t m = A.tree.shade[A.tree.tri_ids[c.k]].material;
-                    if (A.materials[m].kind == RTK_MAT_REFRACTIVE) {         // transmissive: step through, :126-127
-                        const V3 hp = ray.o + (c.t * ray.d);
-                        ray.o = hp + (A.shadow_bias * ray.d);
-                        max_t -= c.t;
-                        if (0.0f < max_t) again = true; else clr = true;
-                    }
-                }
-                if (!again) { clear = clr; pending = false; }
+                // (occl_on: the tree traced holds nothing transmissive, whatever the scene does)
+                const OccStep os = occlusion_step(A.tree, A.materials, A.shadow_bias, A.has_refractive && !A.occl_on, c, ray.o, ray.d, max_t);
+                ray.o = os.o; max_t = os.max_t;
+                if (os.answer != OCC_AGAIN) { clear = os.answer == OCC_CLEAR; pending = false; }
             }
         }
         if (valid) S.ws.contrib[(size_t)h * n_lights + k] = make_float2(contrib, clear ? 1.0f : 0.0f);
@@ -571,11 +514,8 @@ __global__ __launch_bounds__(256) void k_sort_scatter_nodes(StreamArgs S) {
 __global__ __launch_bounds__(256) void k_sort_scatter_hits(StreamArgs S) {
     const uint32_t *ctrl = S.ws.ctrl;
     if (ctrl[kCtrlOverflow] != 0u) return;
-    unsigned long long hb = 0ull;
-    for (uint32_t j = 0; j < S.level; ++j) hb += ctrl[kCtrlHitCount + j];
-    const unsigned long long hc = ctrl[kCtrlHitCount + S.level];
-    const uint32_t hit_base = hb < S.ws.hit_cap ? (uint32_t)hb : S.ws.hit_cap;
-    const uint32_t n_hits = (hb + hc <= S.ws.hit_cap) ? (uint32_t)hc : S.ws.hit_cap - hit_base;
+    uint32_t hit_base, n_hits;
+    hit_range(ctrl, S.level, S.ws.hit_cap, hit_base, n_hits);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < n_hits; i0 += stride) {
         const uint32_t i = i0 + threadIdx.x;

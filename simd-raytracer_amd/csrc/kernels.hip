@@ -185,10 +185,7 @@ template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRI
 __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : SLICES == 8 ? 2 : (SLICES == 4 && !STATS ? RTK_G4_WAVES : 4)) void k_render(RenderArgs A) {
     // PRIMED (second pass of a two-pass frame): pixel blocks come from tile_order (most expensive first) and the
     // camera ray's hit is read from A.prim instead of being traced again
-#ifdef RTK_DEBUG_PHASES
-    const unsigned long long ph_entry = __builtin_readcyclecounter();
-    const unsigned long long ph_rt0 = __builtin_amdgcn_s_memrealtime();     // 100 MHz, the same clock on every CU
-#endif
+    FrameProbe phases = FrameProbe::enter();                     // diagnostic build only (phases.hip.hpp); empty in the product
     if (PRIMED && blockIdx.x >= *A.n_listed) return;
     if (A.only_if != nullptr && *A.only_if == 0u) return;        // fallback launch behind the streaming pipeline: nothing overflowed
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -272,9 +269,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         valid = valid & (p.lx < A.bucket) & (p.ly < A.bucket) & (p.px < A.width) & (p.py < A.height);
     }
 
-#ifdef RTK_DEBUG_PHASES
-    const unsigned long long ph_begin = __builtin_readcyclecounter();
-#endif
+    phases.prologue_done();
     const V3 background = mk(A.background[0], A.background[1], A.background[2]);
     const V3 black = mk(0.f, 0.f, 0.f);
     const uint32_t seed_hash = pcg_hash(A.seed);
@@ -311,11 +306,6 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     unsigned long long burst_lanes = 0ull;
     uint32_t burst_plog_done = 0u, burst_part0 = 0u;   // log2(parts) of that burst; this lane's part for its first light
     uint32_t burst_nl_done = 0u;                       // lights of that burst
-#ifdef RTK_DEBUG_PHASES
-    unsigned long long ph_first_trace = 0, ph_after_first = 0, ph_wait = 0;
-    float ph_tr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ph_kind[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float ph_job[3][8] = {{0.f}}, ph_own[1] = {0.f};                 // the helpers' jobs of the last light burst
-#endif
 
     for (;;) {
         // ---------- resolve: run each lane forward until it needs a ray traced (or is done)
@@ -541,10 +531,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
             primed = false;
             burst_done = false;
         } else {
-#ifdef RTK_DEBUG_PHASES
-            const unsigned long long tr0 = __builtin_readcyclecounter();
-            if (ph_first_trace == 0) ph_first_trace = tr0;
-#endif
+            phases.trace_begins();
             // shadow rays of scenes without transmissive materials only ask "is the closest hit nearer than the light":
             // they may stop at the first hit that says yes (trace(), `exit_t`; A.shadow_exit is set by the host).
             const float exit_t = (A.shadow_exit && pend == PEND_SHADOW) ? shadow_max_t : -1.0f;
@@ -575,27 +562,14 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 sx.min_tris = 0xFFFFFFFFu;                                  // (they are busy: the owner's own leaves stay whole)
             }
             cand = trace<MODE, STATS, kStage, SLICES, kRootFirst>(A.tree, lds_nodes, ray, cull, in_root & !elsewhere, st, sx, kAutoMinLanes, exit_t, cls, apex);   // (in_root: no unlit lane)
-#ifdef RTK_DEBUG_PHASES
-            const unsigned long long ph_w0 = __builtin_readcyclecounter();
-#endif
+            phases.trace_returned();
             if (burst) {
                 __syncthreads();                                            // B2: their answers are in LDS
                 sx.min_tris = A.slice_min_tris;
             }
-#ifdef RTK_DEBUG_PHASES
-            ph_wait += __builtin_readcyclecounter() - ph_w0;
-            if (burst && SLICES > 1) ph_own[0] = (float)(ph_w0 - tr0);
-            for (int i = 0; i < 6; ++i) if (sx.n_trace == (uint32_t)i) {
-                ph_tr[i] = (float)(__builtin_readcyclecounter() - tr0);
-                ph_kind[i] = burst ? 100.f + (float)burst_plog : (float)__popcll(__builtin_amdgcn_ballot_w64(in_root));
-            }
-#endif
+            phases.trace_done(sx.probe(), burst, SLICES > 1, burst_plog, in_root);
             burst_done = burst; burst_lanes = burst_mask; burst_plog_done = burst_plog; burst_part0 = burst_my_part;
             burst_nl_done = burst_nl;
-#ifdef RTK_DEBUG_PHASES
-            sx.c_trace += __builtin_readcyclecounter() - tr0; sx.n_trace += 1u;
-            if (ph_after_first == 0) ph_after_first = __builtin_readcyclecounter();
-#endif
         }
 
         float *const unpark = &park_lds[park_slot][0][fresh_lane()];
@@ -672,29 +646,10 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     }
 
     const uint32_t lane = fresh_lane();
-#ifdef RTK_DEBUG_PHASES
-    const Pixel dbg_p = my_pixel();
-    const uint32_t lx = dbg_p.lx, ly = dbg_p.ly, px = dbg_p.px, py = dbg_p.py;
-    if (valid && writer) {
-        const unsigned long long ph_now = __builtin_readcyclecounter();
-        const unsigned long long ph_rt1 = __builtin_amdgcn_s_memrealtime();
-        const float vals[60] = {(float)(ph_now - ph_begin), (float)sx.c_trace, (float)sx.n_trace, (float)sx.n_steps,
-                                (float)sx.n_small, (float)sx.t_small, (float)sx.c_small, (float)sx.n_big, (float)sx.t_big, (float)sx.c_big,
-                                (float)(ph_begin - ph_entry), (float)(ph_first_trace - ph_begin), (float)(ph_after_first - ph_first_trace),
-                                (float)(ph_now - ph_after_first), (float)sx.tally.chunks, (float)sx.tally.surv, (float)sx.tally.tris,
-                                (float)(ph_rt0 & 0xFFFFFFull), (float)(ph_rt1 & 0xFFFFFFull), (float)blockIdx.x,
-                                (float)ph_wait, ph_tr[0], ph_tr[1], ph_tr[2], ph_tr[3], ph_tr[4], ph_tr[5],
-                                ph_kind[0], ph_kind[1], ph_kind[2], ph_kind[3], ph_kind[4], ph_kind[5], (float)sx.c_bund, (float)sx.c_list, ph_own[0],
-                                (float)sx.tally.stg.n, (float)sx.tally.stg.w1, (float)sx.tally.stg.l1, (float)sx.tally.stg.w2, (float)sx.tally.stg.l2,
-                                (float)sx.tally.stg.w3, (float)sx.tally.stg.l3, (float)sx.tally.stg.l4,
-                                ph_job[1][0], ph_job[1][1], ph_job[1][2], ph_job[1][3], ph_job[1][4], ph_job[1][5], ph_job[1][6], ph_job[1][7],
-                                ph_job[2][0], ph_job[2][1], ph_job[2][2], ph_job[2][3], ph_job[2][4], ph_job[2][5], ph_job[2][6], ph_job[2][7]};
-        float v = 0.f;
-        for (int i = 0; i < 60; ++i) v = (lane == (uint32_t)i) ? vals[i] : v;
-        float *o = A.out + A.out_index(local_bucket, lx, ly, px, py) * 3;
-        o[0] = v; o[1] = 0.f; o[2] = 0.f;
+    if (kPhases && valid && writer) {
+        const Pixel p = my_pixel();
+        phases.write(sx.probe(), lane, A.out + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3);
     }
-#endif
     if (A.cost_out != nullptr && lane == 0u && gwave < A.n_units) {        // what this block cost, for the next frame's order
         // (a block that ran alone on one wave of a packed workgroup took about twice as long as it would with helpers)
         const unsigned long long dt = (__builtin_readcyclecounter() - cost_t0) >> (light ? 5 : 4);

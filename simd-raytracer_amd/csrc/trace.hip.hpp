@@ -8,6 +8,7 @@
 
 #include <cstddef>
 
+#include "phases.hip.hpp"
 #include "rtk_internal.hpp"
 
 namespace rtk {
@@ -208,17 +209,9 @@ __device__ __forceinline__ TriS load_tri_uniform(cptr_f32 tp) {
 }
 
 // one triangle against the wave's rays (the arithmetic of test_triangle, wave-level early outs between the stages)
-#ifdef RTK_DEBUG_PHASES
-struct StageTally { uint32_t n, w1, l1, w2, l2, w3, l3, l4; };   // triangles; waves / lanes alive after det+u_est, after u, after v; lanes accepted
-#define RTK_STAGE_ARG , StageTally *stg = nullptr
-#define RTK_STAGE(x) if (stg) { x; }
-#else
-#define RTK_STAGE_ARG
-#define RTK_STAGE(x)
-#endif
 __device__ __forceinline__ void tri_step(const TriS &cur, const uint32_t k, const Ray &r, const bool cull, const float eps,
-                                         const unsigned long long pass_mask, const uint32_t lane, Cand &best RTK_STAGE_ARG) {
-    RTK_STAGE(stg->n += 1u)
+                                         const unsigned long long pass_mask, const uint32_t lane, Cand &best, const Probe probe) {
+    probe.tri();
     const float pvx = r.d.y * cur.e2z - r.d.z * cur.e2y;
     const float pvy = r.d.z * cur.e2x - r.d.x * cur.e2z;
     const float pvz = r.d.x * cur.e2y - r.d.y * cur.e2x;
@@ -235,23 +228,23 @@ __device__ __forceinline__ void tri_step(const TriS &cur, const uint32_t k, cons
     const float u_est = un * __builtin_amdgcn_rcpf(det);
     m &= ~(__builtin_amdgcn_ballot_w64(u_est < -1.0e-30f) | __builtin_amdgcn_ballot_w64(1.00001f < u_est));
     if (m == 0ull) return;
-    RTK_STAGE(stg->w1 += 1u; stg->l1 += (uint32_t)__popcll(m))
+    probe.alive(PH_STG_W1, m);
     const float inv_det = (1.0f / det);
     const float u = un * inv_det;
     m &= __builtin_amdgcn_ballot_w64(0.0f <= u) & __builtin_amdgcn_ballot_w64(u <= 1.0f);
     if (m == 0ull) return;
-    RTK_STAGE(stg->w2 += 1u; stg->l2 += (uint32_t)__popcll(m))
+    probe.alive(PH_STG_W2, m);
     const float qx = tvy * cur.e1z - tvz * cur.e1y;
     const float qy = tvz * cur.e1x - tvx * cur.e1z;
     const float qz = tvx * cur.e1y - tvy * cur.e1x;
     const float v = (r.d.x * qx + r.d.y * qy + r.d.z * qz) * inv_det;
     m &= __builtin_amdgcn_ballot_w64(0.0f <= v) & __builtin_amdgcn_ballot_w64(u + v <= 1.0f);
     if (m == 0ull) return;
-    RTK_STAGE(stg->w3 += 1u; stg->l3 += (uint32_t)__popcll(m))
+    probe.alive(PH_STG_W3, m);
     const float t = (cur.e2x * qx + cur.e2y * qy + cur.e2z * qz) * inv_det;
     m &= __builtin_amdgcn_ballot_w64(eps < t) & __builtin_amdgcn_ballot_w64(t < best.t);
     if (m == 0ull) return;
-    RTK_STAGE(stg->l4 += (uint32_t)__popcll(m))
+    probe.accepted(m);
     if ((m >> lane) & 1ull) { best.t = t; best.u = u; best.v = v; best.k = k; }
 }
 
@@ -273,10 +266,10 @@ __device__ __forceinline__ void leaf_range_wave(cptr_f32 tris, const uint32_t fi
     TriS A = load_tri_uniform(base + (size_t)k * 9);
     for (;;) {
         const TriS B = load_tri_uniform(base + (size_t)(k + 1u < hi ? k + 1u : last) * 9);
-        tri_step(A, first + k, r, cull, eps, pass_mask, lane, best);
+        tri_step(A, first + k, r, cull, eps, pass_mask, lane, best, Probe{});
         if (k + 1u >= hi) break;
         A = load_tri_uniform(base + (size_t)(k + 2u < hi ? k + 2u : last) * 9);
-        tri_step(B, first + k + 1u, r, cull, eps, pass_mask, lane, best);
+        tri_step(B, first + k + 1u, r, cull, eps, pass_mask, lane, best, Probe{});
         if (k + 2u >= hi) break;
         k += 2u;
     }
@@ -499,7 +492,8 @@ __device__ __forceinline__ uint32_t emit_bundle(const Ray &r, const bool cull, c
 // (The partition lives in `cidx` itself; any partition is a valid one, the bounds are made from whatever it is.)
 // Returns the number of bundles, 0 when culling is off for this trace.
 __device__ __forceinline__ uint32_t make_bundles(const Ray &r, const bool cull, const bool active, const uint32_t cls,
-                                                 const V3 apex, float *lds, uint32_t &cidx) {
+                                                 const V3 apex, float *lds, uint32_t &cidx, const Probe probe) {
+    const Stamp t0 = Stamp::now();                     // phase diagnostic: EVERY return below stops it (there are two)
     const uint32_t lane = __lane_id();
     unsigned long long rem = __builtin_amdgcn_ballot_w64(active);
     uint32_t n = 0u;
@@ -533,9 +527,10 @@ __device__ __forceinline__ uint32_t make_bundles(const Ray &r, const bool cull, 
             }
         }
         for (uint32_t b = 0u; b < cnt; ++b)
-            if (emit_bundle(r, cull, in & (cidx == n + b), hinted, cx, cy, cz, lds, n + b) == 0u) return 0u;
+            if (emit_bundle(r, cull, in & (cidx == n + b), hinted, cx, cy, cz, lds, n + b) == 0u) { probe.since(t0, PH_C_BUND); return 0u; }
         n += cnt;
     }
+    probe.since(t0, PH_C_BUND);
     return n;
 }
 
@@ -728,21 +723,13 @@ __device__ __forceinline__ bool pencil_misses(const PencilRegs &R, const float e
 // Leaf references [lo, hi) of the leaf starting at `first`, bundle-culled 64 at a time (one triangle per lane), the
 // survivors tested exactly in leaf order.  `cidx` = the bundle of this lane's ray.
 struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
-#ifdef RTK_DEBUG_PHASES
-struct CullTally { uint32_t chunks, surv, tris; unsigned long long c_cull, c_surv; StageTally stg; };
-#define RTK_TALLY_ARG , CullTally &tally
-#define RTK_TALLY_PASS , tally
-#else
-#define RTK_TALLY_ARG
-#define RTK_TALLY_PASS
-#endif
 // `exit_t` (trace()): lanes whose candidate already answers their occlusion query drop out of the pass mask at the start of
 // every 64-triangle pass after the first, and the rest of the range is skipped once none is left.  (Checked after every
 // survivor instead, the compare and branch wait on tri_step's result and config 2 was 8 % slower.)
 __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint32_t first, const uint32_t lo, const uint32_t hi,
                                                   const Ray &r, const bool cull, const float eps, const bool pass,
                                                   const uint32_t cidx, const BundleSet &BS, const bool scalar_surv, const float exit_t,
-                                                  Cand &best RTK_TALLY_ARG) {
+                                                  Cand &best, const Probe probe) {
     unsigned long long pass_mask = __builtin_amdgcn_ballot_w64(pass);
     const uint32_t lane = __lane_id();
     for (uint32_t base = lo; base < hi; base += 64u) {
@@ -750,9 +737,6 @@ __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint3
             pass_mask &= ~__builtin_amdgcn_ballot_w64(best.t <= exit_t);
             if (pass_mask == 0ull) return;
         }
-#ifdef RTK_DEBUG_PHASES
-        const unsigned long long pc0 = __builtin_readcyclecounter();
-#endif
         const uint32_t cnt = hi - base < 64u ? hi - base : 64u;
         const bool have = lane < cnt;
         const F3 *tp = reinterpret_cast<const F3 *>(tris + (size_t)(first + base + (have ? lane : 0u)) * 9);
@@ -769,13 +753,7 @@ __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint3
             }
         }
         unsigned long long surv = __builtin_amdgcn_ballot_w64(have & keep);
-#ifdef RTK_DEBUG_PHASES
-        tally.chunks += 1u; tally.surv += (uint32_t)__popcll(surv); tally.tris += cnt;
-#endif
-#ifdef RTK_DEBUG_PHASES
-        const unsigned long long ps0 = __builtin_readcyclecounter();
-        tally.c_cull += ps0 - pc0;
-#endif
+        probe.cull_pass(surv, cnt);
         // the survivors, in leaf order.  Their data is broadcast from the lane that holds it (nine v_readlane), or -- scalar_surv,
         // the streaming kernels -- comes back through the scalar cache (one 32-byte + one 4-byte s_load each, the next
         // survivor's issued before the current one is tested): the readlanes are VALU issue slots, which a lone wave runs out
@@ -789,11 +767,7 @@ __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint3
                 for (;;) {
                     const int jn = surv != 0ull ? __builtin_ctzll(surv) : j;
                     const TriS nxt = load_tri_uniform(tb + (size_t)jn * 9);
-#ifdef RTK_DEBUG_PHASES
-                    tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best, &tally.stg);
-#else
-                    tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best);
-#endif
+                    tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best, probe);
                     if (surv == 0ull) break;
                     surv &= surv - 1ull;
                     cur = nxt; j = jn;
@@ -813,27 +787,20 @@ __device__ __forceinline__ void leaf_range_bundle(const float *tris, const uint3
             cur.e2x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2.x), j));
             cur.e2y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2.y), j));
             cur.e2z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2.z), j));
-#ifdef RTK_DEBUG_PHASES
-            tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best, &tally.stg);
-#else
-            tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best);
-#endif
+            tri_step(cur, first + base + (uint32_t)j, r, cull, eps, pass_mask, lane, best, probe);
         }
         }
-#ifdef RTK_DEBUG_PHASES
-        tally.c_surv += __builtin_readcyclecounter() - ps0;
-#endif
     }
 }
 
 // leaf references [lo, hi): bundle-culled when the trace has bundles and the range is worth a 64-wide pass
 __device__ __forceinline__ void leaf_range(const TreeView &T, const uint32_t first, const uint32_t lo, const uint32_t hi,
                                            const Ray &r, const bool cull, const bool pass, const uint32_t cidx,
-                                           const BundleSet &BS, const float exit_t, Cand &best RTK_TALLY_ARG) {
+                                           const BundleSet &BS, const float exit_t, Cand &best, const Probe probe) {
     if (lo >= hi) return;
     if (BS.n != 0u && hi - lo >= kBundleMinTris)
         leaf_range_bundle(reinterpret_cast<const float *>(T.tris), first, lo, hi, r, cull, T.eps, pass, cidx, BS, T.scalar_surv != 0,
-                          exit_t, best RTK_TALLY_PASS);
+                          exit_t, best, probe);
     else
         leaf_range_wave((cptr_f32)(const void *)T.tris, first, lo, hi, r, cull, T.eps, pass, best);
 }
@@ -888,18 +855,8 @@ struct SliceCtx {
     bool rebundle = true;  // make new bundles when half of a trace's occlusion queries are answered (trace_list).  Pays where
                          // a trace is long (the megakernel's critical blocks: config 2 -5 %), not in the streaming pipeline's
                          // sorted queues (configs 3 / 4: +4 %)
-#ifdef RTK_DEBUG_PHASES
-    // diagnostic (tools/phase_times.py): cycles and counts of the owner's walk by phase
-    unsigned long long c_small = 0, c_big = 0, c_trace = 0, c_bund = 0, c_list = 0;
-    uint32_t n_steps = 0, n_small = 0, n_big = 0, t_small = 0, t_big = 0, n_trace = 0;
-    CullTally tally = {0u, 0u, 0u, 0ull, 0ull, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};   // owner's own chunks / survivors / triangles seen by the bundle culling
-#endif
+    RTK_PHASE_TALLIES_OF_SLICECTX   // probe(): the handle to this wave's phase tallies (phases.hip.hpp; no data member in the product)
 };
-#ifdef RTK_DEBUG_PHASES
-#define RTK_SX_TALLY , sx.tally
-#else
-#define RTK_SX_TALLY
-#endif
 
 // Slice `slice` of a leaf of `count` triangles: contiguous (the merge relies on it).  A leaf with at least one full
 // 64-triangle pass per wave is cut at multiples of 64, so that the bundle culling, which reads 64 triangles at a time, does
@@ -929,9 +886,6 @@ __device__ __forceinline__ void group_helper_loop(const TreeView &T, GroupShared
     r.o = mk(0.f, 0.f, 0.f); r.d = mk(0.f, 0.f, 0.f); r.inv = mk(0.f, 0.f, 0.f);
     uint32_t cidx = 0u;
     BundleSet BS = {sh->bundles, 0u};
-#ifdef RTK_DEBUG_PHASES
-    CullTally tally = {0u, 0u, 0u, 0ull, 0ull, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
-#endif
     for (;;) {
         __syncthreads();                                                   // B1: a command is posted
         const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh->kind);
@@ -958,7 +912,7 @@ __device__ __forceinline__ void group_helper_loop(const TreeView &T, GroupShared
         uint32_t lo, hi;
         slice_range<SLICES>(count, slice, lo, hi);
         leaf_range(T, first, lo, hi, r, ((cm >> lane) & 1ull) != 0ull, ((pm >> lane) & 1ull) != 0ull, cidx, BS, sh->ray_d[lane].w,
-                   mine RTK_TALLY_PASS);
+                   mine, Probe{});
         sh->result[slice][lane] = make_float4(mine.t, mine.u, mine.v, __uint_as_float(mine.k));
         __syncthreads();                                                   // B2: results are in LDS
     }
@@ -975,6 +929,7 @@ template <int SLICES>
 __device__ __forceinline__ void process_leaf(const TreeView &T, const uint32_t a, const uint32_t b, const Ray &r, const bool cull,
                                              const bool pass, const uint32_t cidx, const BundleSet &BS, Cand &best, SliceCtx &sx,
                                              const float exit_t) {
+    const Stamp leaf_t0 = Stamp::now();
     if (SLICES > 1 && b >= sx.min_tris) {
         GroupShared *sh = sx.sh;
         const uint32_t lane = __lane_id();
@@ -994,15 +949,17 @@ __device__ __forceinline__ void process_leaf(const TreeView &T, const uint32_t a
         __syncthreads();                                       // B1: helpers start on their slices
         uint32_t lo0, hi0;
         slice_range<SLICES>(b, 0u, lo0, hi0);
-        leaf_range(T, a, lo0, hi0, r, cull, pass, cidx, BS, exit_t, best RTK_SX_TALLY);
+        leaf_range(T, a, lo0, hi0, r, cull, pass, cidx, BS, exit_t, best, sx.probe());
         __syncthreads();                                       // B2: helper results are in LDS
 #pragma unroll
         for (int s = 1; s < SLICES; ++s) {
             const float4 c = sh->result[s][lane];
             if (c.x < best.t) { best.t = c.x; best.u = c.y; best.v = c.z; best.k = __float_as_uint(c.w); }
         }
+        sx.probe().leaf(true, b, leaf_t0);
     } else {
-        leaf_range(T, a, 0u, b, r, cull, pass, cidx, BS, exit_t, best RTK_SX_TALLY);
+        leaf_range(T, a, 0u, b, r, cull, pass, cidx, BS, exit_t, best, sx.probe());
+        sx.probe().leaf(false, b, leaf_t0);
     }
 }
 
@@ -1072,9 +1029,7 @@ __device__ __forceinline__ void trace_list(const TreeView &T, const Ray &r, cons
     }
     uint32_t bundled = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(active));   // live lanes when the bundles were last made
     for (uint32_t base = 0; base < T.n_leaves; base += 64u) {
-#ifdef RTK_DEBUG_PHASES
-        const unsigned long long pl0 = __builtin_readcyclecounter();
-#endif
+        const Stamp pass_t0 = Stamp::now();
         const bool have = base + lane < T.n_leaves;
         const float4 *lp = reinterpret_cast<const float4 *>(leaf_list + (have ? base + lane : 0u));
         const float4 q0 = lp[0], q1 = lp[1];
@@ -1087,10 +1042,7 @@ __device__ __forceinline__ void trace_list(const TreeView &T, const Ray &r, cons
             }
         }
         unsigned long long cm = __builtin_amdgcn_ballot_w64(have & cand);
-#ifdef RTK_DEBUG_PHASES
-        sx.n_steps += (uint32_t)__popcll(cm);
-        sx.c_list += __builtin_readcyclecounter() - pl0;
-#endif
+        sx.probe().list_pass(cm, pass_t0);
         while (cm != 0ull) {
             const int j = __builtin_ctzll(cm);
             cm &= cm - 1ull;
@@ -1107,17 +1059,7 @@ __device__ __forceinline__ void trace_list(const TreeView &T, const Ray &r, cons
             const uint32_t a = (uint32_t)__builtin_amdgcn_readlane(__float_as_int(q1.z), j);
             const uint32_t b = (uint32_t)__builtin_amdgcn_readlane(__float_as_int(q1.w), j);
             sx.work += b + 2u;
-#ifdef RTK_DEBUG_PHASES
-            const unsigned long long ph0 = __builtin_readcyclecounter();
-#endif
             process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx, exit_t);
-#ifdef RTK_DEBUG_PHASES
-            {
-                const unsigned long long ph1 = __builtin_readcyclecounter();
-                if (SLICES > 1 && b >= sx.min_tris) { sx.c_big += ph1 - ph0; sx.n_big += 1u; sx.t_big += b; }
-                else { sx.c_small += ph1 - ph0; sx.n_small += 1u; sx.t_small += b; }
-            }
-#endif
             // occlusion queries: a lane whose hit already answers the query stops; when nobody is left the walk ends
             if (best.t <= exit_t) live = false;
             const uint32_t n_live = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(live));
@@ -1125,13 +1067,7 @@ __device__ __forceinline__ void trace_list(const TreeView &T, const Ray &r, cons
             // occlusion queries thin out as they are answered: once half of the rays the bundles were made for are gone, bundles
             // of the remaining ones are tighter (the candidate leaves found with the old bundles stay a valid superset)
             if (sx.rebundle && n_live * 2u <= bundled && (uint32_t)__popcll(cm) >= kRebundleMinLeaves) {
-#ifdef RTK_DEBUG_PHASES
-                const unsigned long long pb0 = __builtin_readcyclecounter();
-#endif
-                BS.n = make_bundles(r, cull, live, cls, apex, sx.bundle_lds, cidx);
-#ifdef RTK_DEBUG_PHASES
-                sx.c_bund += __builtin_readcyclecounter() - pb0;
-#endif
+                BS.n = make_bundles(r, cull, live, cls, apex, sx.bundle_lds, cidx, sx.probe());
                 bundled = n_live;
                 sx.rays_dirty = true;                                       // helpers re-read the bundles and the lanes' bundle indices
             }
@@ -1173,9 +1109,7 @@ __device__ __forceinline__ uint32_t trace_wave(const TreeView &T, const Ray &r, 
         if (STATS) { st.nodes += part ? 1u : 0u; st.boxpass += pass ? 1u : 0u; }
         const bool any_pass = wave_any(pass);
         sx.work += (any_pass && b != DEV_INNER) ? b + 2u : 2u;
-#ifdef RTK_DEBUG_PHASES
-        sx.n_steps += 1u;
-#endif
+        sx.probe().node_step();
         if (b == DEV_INNER) {
             if (part) next = pass ? n + 1 : a;
             n = any_pass ? n + 1 : a;
@@ -1183,17 +1117,7 @@ __device__ __forceinline__ uint32_t trace_wave(const TreeView &T, const Ray &r, 
             if (part) next = n + 1;
             if (any_pass) {
                 if (STATS && pass) { st.leaves += 1; st.tris += b; st.packets16 += (b + 15u) >> 4; }
-#ifdef RTK_DEBUG_PHASES
-                const unsigned long long ph0 = __builtin_readcyclecounter();
-#endif
                 process_leaf<SLICES>(T, a, b, r, cull, pass, cidx, BS, best, sx, exit_t);
-#ifdef RTK_DEBUG_PHASES
-                {
-                    const unsigned long long ph1 = __builtin_readcyclecounter();
-                    if (SLICES > 1 && b >= sx.min_tris) { sx.c_big += ph1 - ph0; sx.n_big += 1u; sx.t_big += b; }
-                    else { sx.c_small += ph1 - ph0; sx.n_small += 1u; sx.t_small += b; }
-                }
-#endif
                 // occlusion queries: a lane whose hit already answers the query stops; when nobody is left the walk ends
                 if (best.t <= exit_t) next = end;
                 if (__builtin_amdgcn_ballot_w64(next < end) == 0ull) break;
@@ -1246,13 +1170,7 @@ __device__ __forceinline__ Cand trace(const TreeView &T, const DevNode *lds_node
             if (wave_any(in)) {
                 BundleSet BS = {sx.bundle_lds, 0u};
                 uint32_t cidx = 0u;
-#ifdef RTK_DEBUG_PHASES
-                const unsigned long long pb0 = __builtin_readcyclecounter();
-#endif
-                if (T.bundle_cull != 0 && sx.bundle_lds != nullptr) BS.n = make_bundles(r, cull, in, cls, apex, sx.bundle_lds, cidx);
-#ifdef RTK_DEBUG_PHASES
-                sx.c_bund += __builtin_readcyclecounter() - pb0;
-#endif
+                if (T.bundle_cull != 0 && sx.bundle_lds != nullptr) BS.n = make_bundles(r, cull, in, cls, apex, sx.bundle_lds, cidx, sx.probe());
                 if (!STATS && BS.n != 0u && T.n_leaves <= kListMaxLeaves) trace_list<SLICES>(T, r, cull, in, best, sx, exit_t, cidx, BS, cls, apex);
                 else (void)trace_wave<STATS, SLICES>(T, r, cull, in, best, st, 1u, sx, exit_t, cidx, BS);
             }

@@ -364,6 +364,41 @@ int rtk_accel_radiance_device(rtk_accel *accel, const rtk_ray *d_rays, const uin
 int rtk_accel_update_vertices(rtk_accel *accel, const float *vertices /* host [n_vertices][3] */);
 int rtk_accel_update_vertices_device(rtk_accel *accel, const float *d_vertices /* device [n_vertices][3] */, void *hip_stream);
 
+/* ---- dynamic geometry, new triangle lists: the accel after scene<F>'s meshes got other triangles as well (an isosurface
+ *      extracted again, another level of detail, a tear) ----
+ * `vertices` as above.  `indices` has the layout of rtk_scene_desc.indices: the meshes' triangle lists one behind the other,
+ * three indices per triangle, each LOCAL to its mesh's vertices; `mesh_ntris` says how many triangles each mesh has now and
+ * is read on the host in both variants.  `indices` may be NULL when every count is 0.
+ * After RTK_OK everything observable through the accel is, bit for bit, what rtk_accel_build gives for a scene that differs from
+ * the accel's only in `vertices`, `indices` and `mesh_ntris` (same params, same environment knobs): rtk_accel_tree_info (with
+ * n_triangles) / _tree_dump, every rtk_accel_intersect*, rtk_accel_occluded* and rtk_accel_radiance* result, every frame through
+ * every RTK_TRACE_* engine and its counters' `rays`.  RTK_TRAVERSAL_FAST accels included, with their leaf orders and the
+ * opaque-only occlusion tree.  rtk_hit.tri is the global index in the new concatenated order.  A later
+ * rtk_accel_update_vertices moves the vertices of the new topology.
+ * Fixed by the call: the number of meshes, every mesh's vertex count, every mesh's material, the per-vertex uvs, materials,
+ * textures, lights, camera and rtk_accel_params.  Every mesh's triangle count is free: 0, smaller, or larger than anything
+ * before.  Vertices no triangle uses are legal and cost a few bytes each: a caller whose vertex count varies builds the scene
+ * with a POOL of vertices per mesh, as large as it will ever need, and indexes into what it uses of it.
+ * The topology tables -- vertex ids, the vertex -> (triangle, corner) lists the smooth normals are summed in, mesh / material and
+ * uvs per triangle, which triangles are opaque -- are made on the device from `indices` (csrc/topology.hip); from there the
+ * call is rtk_accel_update_vertices: one code path, the same tree build, the same host numbering.
+ * Ordering and memory are those of rtk_accel_update_vertices: the device is synchronised at entry, the work goes to `hip_stream`
+ * (the host variant: the null stream), the host blocks once for the node table and the flags, later work on any stream waits
+ * for the update's event; NOT stream-capturable.  Buffers grow with head room when a count outgrows them and never shrink.  The
+ * node / reference retry is the same.  The cost-feedback launch order and RTK_TRACE_AUTO's engine trial start over.
+ * Errors, in this order: a NULL accel, vertices or mesh_ntris, or NULL indices with a positive count -> RTK_ERR_INVALID; no usable
+ * device -> RTK_ERR_NO_DEVICE; then RTK_ERR_INVALID for a negative count, triangles on a mesh without vertices, more than
+ * 0xFFFFFFF0 / 3 triangles, a non-finite coordinate, an index that is not below its OWN mesh's vertex count.  The host variant
+ * finds the last two before it touches the device; the device variant learns them from flags in the header it reads back anyway.
+ * A bad index never becomes a bad address: the kernel that validates puts an index that is in range in its place before anything
+ * dereferences it, and nothing else reads the vertex array through the caller's indices.  After any error the accel is exactly
+ * as before the call and stays usable: topology and geometry are built into buffers of their own and swapped in at the end. */
+int rtk_accel_update_geometry(rtk_accel *accel, const float *vertices /* host [n_vertices][3] */,
+                              const uint32_t *indices /* host, concatenated [sum mesh_ntris][3], mesh-local */,
+                              const int32_t *mesh_ntris /* host [n_meshes] */);
+int rtk_accel_update_geometry_device(rtk_accel *accel, const float *d_vertices, const uint32_t *d_indices,
+                                     const int32_t *mesh_ntris /* HOST [n_meshes] */, void *hip_stream);
+
 /* ---- frame: replaces render_frame<A,F> (render/render.hpp:18-108) with color_hit/is_occluded device-side ---- */
 /* number of floats the (rank-local) output of rtk_render_frame_device holds */
 int rtk_render_output_floats(const rtk_accel *accel, const rtk_render_params *p, size_t *n_floats);

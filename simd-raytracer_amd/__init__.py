@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "rtk_accel_occluded", "rtk_accel_occluded_device",
     "rtk_accel_radiance", "rtk_accel_radiance_device",
     "rtk_accel_update_vertices", "rtk_accel_update_vertices_device",
+    "rtk_accel_update_geometry", "rtk_accel_update_geometry_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
@@ -160,6 +161,8 @@ _L.rtk_accel_radiance.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceP
 _L.rtk_accel_radiance_device.argtypes = [_vp, _vp, _vp, C.c_size_t, C.POINTER(RadianceParams), _vp, _vp]
 _L.rtk_accel_update_vertices.argtypes = [_vp, _vp]
 _L.rtk_accel_update_vertices_device.argtypes = [_vp, _vp, _vp]
+_L.rtk_accel_update_geometry.argtypes = [_vp, _vp, _vp, _vp]
+_L.rtk_accel_update_geometry_device.argtypes = [_vp, _vp, _vp, _vp, _vp]
 _L.rtk_render_output_floats.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]
 _L.rtk_render_frame.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.POINTER(Counters)]
 _L.rtk_render_frame_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp]
@@ -462,6 +465,37 @@ class KdTreeSimdAccel:
     def update_vertices_device(self, d_vertices_ptr: int, stream: int = 0) -> None:
         """d_vertices_ptr: device float32 [n_vertices, 3]; stream-ordered on `stream`, blocks the host once; not capturable (rtk.h)."""
         _check(_L.rtk_accel_update_vertices_device(self._h, d_vertices_ptr or None, stream))
+
+    # ---- dynamic geometry: the same meshes with other triangle lists as well (rtk.h, csrc/topology.hip)
+    def _mesh_ntris(self, mesh_ntris) -> np.ndarray:
+        mesh_ntris = np.asarray(mesh_ntris)
+        if mesh_ntris.dtype.kind not in "iu" or mesh_ntris.shape != (self.scene.info.n_meshes,):
+            raise ValueError(f"mesh_ntris must be {self.scene.info.n_meshes} integers, one per mesh")
+        return np.ascontiguousarray(mesh_ntris, np.int32)
+
+    def update_geometry(self, vertices: np.ndarray, indices: np.ndarray, mesh_ntris) -> None:
+        """vertices: [n_vertices, 3] float32; indices: [sum(mesh_ntris), 3] uint32, mesh-local, the meshes' lists concatenated;
+        mesh_ntris: one count per mesh.  All in host memory.  Afterwards the accel is bit for bit the one a new build of the scene
+        with these three arrays would give (self.scene goes on describing what the accel was BUILT from; tree_info() has the new
+        triangle count).  What the counts and indices hold is judged by the library (RtkError)."""
+        vertices, indices = np.asarray(vertices), np.asarray(indices)
+        n = self.scene.info.n_vertices
+        if vertices.dtype != np.float32 or vertices.shape != (n, 3):
+            raise ValueError(f"vertices must be float32 of shape ({n}, 3)")
+        mesh_ntris = self._mesh_ntris(mesh_ntris)
+        if indices.dtype != np.uint32 or indices.ndim != 2 or indices.shape[1] != 3:
+            raise ValueError("indices must be uint32 of shape (n, 3)")
+        if (mesh_ntris >= 0).all() and indices.shape[0] != int(mesh_ntris.sum(dtype=np.int64)):
+            raise ValueError("indices must have one row per triangle of mesh_ntris")
+        vertices, indices = np.ascontiguousarray(vertices), np.ascontiguousarray(indices)
+        _check(_L.rtk_accel_update_geometry(self._h, vertices.ctypes.data, indices.ctypes.data if indices.size else None,
+                                            mesh_ntris.ctypes.data))
+
+    def update_geometry_device(self, d_vertices_ptr: int, d_indices_ptr: int, mesh_ntris, stream: int = 0) -> None:
+        """d_vertices_ptr: device float32 [n_vertices, 3]; d_indices_ptr: device uint32 [sum(mesh_ntris), 3] (0 when there are no
+        triangles); mesh_ntris: HOST integers.  Stream-ordered on `stream`, blocks the host once; not capturable (rtk.h)."""
+        mesh_ntris = self._mesh_ntris(mesh_ntris)
+        _check(_L.rtk_accel_update_geometry_device(self._h, d_vertices_ptr or None, d_indices_ptr or None, mesh_ntris.ctypes.data, stream))
 
     # ---- frames
     def output_floats(self, cfg: RenderConfig) -> int:

@@ -93,6 +93,8 @@ struct rtk_knobs {
 
 namespace rtk {
 enum { G_NODES, G_LEAVES, G_FAST, G_TRIS, G_IDS, G_SHADE, G_LREFS, G_ONODES, G_OLEAVES, G_OTRIS, G_OIDS, kGeomBufs };
+// the topology tables of an update (up_index, up_inc_off, up_inc, up_opaque, d_tri_uv), which rtk_accel_update_geometry replaces
+enum { T_INDEX, T_INC_OFF, T_INC, T_OPAQUE, T_TRI_UV, kTopoBufs };
 }
 
 struct rtk_accel {
@@ -193,12 +195,26 @@ struct rtk_accel {
     int32_t *d_leaf_refs = nullptr;            // leaf_refs in reference order, written by the device build
     bool refs_on_device = false;               // tree.leaf_refs (and every per-triangle host array) lives on the device only
     int32_t n_leaf_refs_dev = 0;
-    bool up_static = false;                    // the tables of the constant topology below are made
+    bool up_static = false;                    // the tables of the current topology below are made
     uint32_t *up_index = nullptr, *up_inc_off = nullptr, *up_inc = nullptr;
     uint8_t *up_opaque = nullptr;
     float *up_verts = nullptr;                 // staging of the host variant
-    rtk::DevTri *up_tris = nullptr;            // per triangle
+    rtk::DevTri *up_tris = nullptr;            // per triangle: scratch of a build, grows with the triangle count
     float *up_tbox = nullptr;
+    size_t up_tris_cap = 0, up_tbox_cap = 0;   // bytes
+    // ---- topo_*: rtk_accel_update_geometry (api_update.hip, topology.hip).  The topology tables exist twice like the geometry:
+    // the new ones are made on the device into the spare set (with d_tri_uv, and mesh / material in the spare shading records)
+    // and swapped in with it.  The counts per mesh are numbers: the host arrays they came from are dropped by the updates.
+    std::vector<int32_t> mesh_nverts, mesh_ntris;
+    void *topo_spare[rtk::kTopoBufs] = {};
+    size_t topo_spare_cap[rtk::kTopoBufs] = {}, topo_active_cap[rtk::kTopoBufs] = {};
+    rtk::dev::TopoMesh *topo_meshes = nullptr; // [n_meshes + 1] the small per-mesh table of the call in flight
+    float *topo_vert_uv = nullptr;             // [n_vertices][2], zero for meshes without uvs; made once, with textures only
+    uint32_t *topo_keys = nullptr;             // the sorted vertex ids of the incidence sort
+    void *topo_temp = nullptr;                 // rocPRIM's
+    size_t topo_keys_cap = 0, topo_temp_cap = 0;
+    uint32_t *up_idx_stage = nullptr;          // staging of the host variant's indices
+    size_t up_idx_stage_cap = 0;
     uint32_t *up_ref_id = nullptr, *up_ref_node = nullptr;
     size_t up_cap_refs = 0, up_cap_nodes = 0;
     uint8_t *up_table = nullptr, *up_table_host = nullptr;     // BuildHdr + BuildNode[up_cap_nodes]; the host copy is pinned

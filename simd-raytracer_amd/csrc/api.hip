@@ -268,6 +268,7 @@ int rtk_accel_build(const rtk_scene *scene, const rtk_accel_params *params, rtk_
             delete a; return fail(RTK_ERR_INVALID, "eps must be in [FLT_MIN, 1)");
         }
         for (const DevMaterial &m : a->scene.materials) if (m.kind == RTK_MAT_REFRACTIVE) a->has_refractive = true;
+        for (const HostMesh &m : a->scene.meshes) { a->mesh_nverts.push_back(int32_t(m.vertices.size())); a->mesh_ntris.push_back(int32_t(m.indices.size() / 3)); }
         a->knobs = rtk_knobs::from_env();
         a->stream_slices_auto = stream_slices_for(a->tree);
         a->fast_traversal = a->params.traversal == RTK_TRAVERSAL_FAST || a->knobs.traversal_fast;
@@ -291,7 +292,8 @@ int rtk_accel_tree_info(const rtk_accel *a, rtk_tree_info *info) {
         if (n.leaf_start >= 0) { info->n_leaves += 1; if (n.leaf_count > info->max_leaf_refs) info->max_leaf_refs = n.leaf_count; }
         else info->n_inner += 1;
     }
-    // (after rtk_accel_update_vertices the per-triangle and per-reference arrays live on the device only)
+    // (after rtk_accel_update_vertices / _update_geometry the per-triangle and per-reference arrays live on the device only, and
+    // scene.n_triangles is the count of the last triangle lists)
     info->n_leaf_refs = a->refs_on_device ? a->n_leaf_refs_dev : int32_t(a->tree.leaf_refs.size());
     info->n_triangles = a->refs_on_device ? a->scene.n_triangles : int32_t(a->tree.triangles.size());
     info->tree_depth = a->tree.depth;
@@ -337,6 +339,8 @@ void rtk_accel_destroy(rtk_accel *a) {
         (void)hipFree(a->up_index); (void)hipFree(a->up_inc_off); (void)hipFree(a->up_inc); (void)hipFree(a->up_opaque); (void)hipFree(a->up_verts);
         (void)hipFree(a->up_tris); (void)hipFree(a->up_tbox); (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);
         (void)hipFree(a->up_table); (void)hipFree(a->up_gather);
+        for (void *p : a->topo_spare) (void)hipFree(p);
+        (void)hipFree(a->topo_meshes); (void)hipFree(a->topo_vert_uv); (void)hipFree(a->topo_keys); (void)hipFree(a->topo_temp); (void)hipFree(a->up_idx_stage);
         if (a->up_table_host) (void)hipHostFree(a->up_table_host);
         if (a->up_stage) (void)hipHostFree(a->up_stage);
         if (a->geom_ready) (void)hipEventDestroy(a->geom_ready);

@@ -1,4 +1,5 @@
-// C-ABI, dynamic geometry: rtk_accel_update_vertices rebuilds the kd-tree on the device (build.hip) and swaps it in.
+// C-ABI, dynamic geometry: rtk_accel_update_vertices and rtk_accel_update_geometry rebuild the kd-tree on the device (build.hip,
+// for new triangle lists topology.hip first) and swap it in.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -33,24 +34,44 @@ int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
     return RTK_OK;
 }
 
-// What an update needs of the topology, which never changes: vertex ids per triangle over the concatenated vertex array, the
-// vertex -> (triangle, corner) incidence lists and which triangles are opaque.  Made on the first update, kept.
+// What every update needs once: the event later work waits for, and how large the buffers are that ensure_device uploaded.
+int ensure_update_common(rtk_accel *a) {
+    if (a->geom_ready) return RTK_OK;
+    RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
+    const HostTree &T = a->tree;
+    auto bytes = [](size_t n, size_t each) { return (n == 0 ? 1 : n) * each; };
+    a->active_cap[G_NODES] = bytes(T.dev_nodes.size(), sizeof(DevNode));
+    a->active_cap[G_LEAVES] = bytes(T.dev_leaves.size(), sizeof(DevNode));
+    a->active_cap[G_FAST] = a->d_leaves_fast ? bytes(T.dev_leaves_fast.size(), sizeof(DevNode)) : 0;
+    a->active_cap[G_TRIS] = bytes(T.dev_tris.size(), sizeof(DevTri));
+    a->active_cap[G_IDS] = bytes(T.dev_tri_ids.size(), sizeof(uint32_t));
+    a->active_cap[G_SHADE] = bytes(T.dev_shade.size(), sizeof(DevShade));
+    // (the opaque-only copy was uploaded at its exact size, which is not kept: 0 makes the first update allocate its own)
+    a->topo_active_cap[T_TRI_UV] = a->d_tri_uv ? bytes(T.dev_tri_uv.size(), sizeof(DevTriUv)) : 0;
+    return RTK_OK;
+}
+
+// What an update of the vertices needs of the topology: vertex ids per triangle over the concatenated vertex array, the
+// vertex -> (triangle, corner) incidence lists and which triangles are opaque.  Made here, on the host, from the scene the accel
+// was built from, on its first update; rtk_accel_update_geometry replaces them by what topology.hip makes of its triangle lists.
 int ensure_update_static(rtk_accel *a) {
+    RTK_TRY(ensure_update_common(a));
     if (a->up_static) return RTK_OK;
     const size_t nv = size_t(a->scene.n_vertices), nt = size_t(a->scene.n_triangles);
     if (nt * 3 > 0xFFFFFFF0ull || nv > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "scene too large for the device build's 32-bit indices");
     std::vector<uint32_t> index(nt * 3), off(nv + 1, 0u), inc(nt * 3);
     std::vector<uint8_t> opaque(nt, uint8_t(1));
     size_t voff = 0, t = 0;
-    for (const HostMesh &m : a->scene.meshes) {
+    for (size_t mi = 0; mi < a->scene.meshes.size(); ++mi) {
+        const HostMesh &m = a->scene.meshes[mi];
         const bool refr = size_t(m.material) < a->scene.materials.size() && a->scene.materials[size_t(m.material)].kind == RTK_MAT_REFRACTIVE;
         for (size_t ti = 0; ti < m.indices.size() / 3; ++ti, ++t) {
             for (size_t k = 0; k < 3; ++k) index[t * 3 + k] = uint32_t(voff + m.indices[ti * 3 + k]);
             opaque[t] = refr ? 0 : 1;
         }
-        voff += m.vertices.size();
+        voff += size_t(a->mesh_nverts[mi]);                                  // (a number: an update empties m.vertices)
     }
-    if (voff != nv || t != nt) return fail(RTK_ERR_INVALID, "internal: the accel's scene copy lost its vertices");
+    if (voff != nv || t != nt) return fail(RTK_ERR_INVALID, "internal: the accel's scene copy lost its topology");
     // Incidence lists by counting sort over (triangle, corner) in ascending order: each vertex's list ascends by triangle and
     // keeps duplicates, which is the order mesh.hpp:36-38 adds the face normals in (build.hip, k_build_normals).
     for (uint32_t v : index) off[size_t(v) + 1] += 1u;
@@ -63,35 +84,101 @@ int ensure_update_static(rtk_accel *a) {
     if (!a->up_inc_off && (rc = upload(off, &a->up_inc_off)) != RTK_OK) { (void)hipFree(a->up_inc_off); a->up_inc_off = nullptr; return rc; }
     if (!a->up_inc && (rc = upload(inc, &a->up_inc)) != RTK_OK) { (void)hipFree(a->up_inc); a->up_inc = nullptr; return rc; }
     if (!a->up_opaque && (rc = upload(opaque, &a->up_opaque)) != RTK_OK) { (void)hipFree(a->up_opaque); a->up_opaque = nullptr; return rc; }
-    if (!a->geom_ready) RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
-    const HostTree &T = a->tree;
-    auto bytes = [](size_t n, size_t each) { return (n == 0 ? 1 : n) * each; };
-    a->active_cap[G_NODES] = bytes(T.dev_nodes.size(), sizeof(DevNode));
-    a->active_cap[G_LEAVES] = bytes(T.dev_leaves.size(), sizeof(DevNode));
-    a->active_cap[G_FAST] = a->d_leaves_fast ? bytes(T.dev_leaves_fast.size(), sizeof(DevNode)) : 0;
-    a->active_cap[G_TRIS] = bytes(T.dev_tris.size(), sizeof(DevTri));
-    a->active_cap[G_IDS] = bytes(T.dev_tri_ids.size(), sizeof(uint32_t));
-    a->active_cap[G_SHADE] = bytes(T.dev_shade.size(), sizeof(DevShade));
-    // (the opaque-only copy was uploaded at its exact size, which is not kept: 0 makes the first update allocate its own)
+    a->topo_active_cap[T_INDEX] = a->topo_active_cap[T_INC] = std::max<size_t>(1, nt * 3) * sizeof(uint32_t);
+    a->topo_active_cap[T_INC_OFF] = (nv + 1) * sizeof(uint32_t);
+    a->topo_active_cap[T_OPAQUE] = std::max<size_t>(1, nt);
     a->up_static = true;
     return RTK_OK;
 }
 
-int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
-    RTK_TRY(ensure_update_static(a));
-    const uint32_t nv = uint32_t(a->scene.n_vertices), nt = uint32_t(a->scene.n_triangles);
+// New triangle lists for an update (null: the vertices alone moved).
+struct NewTopology {
+    const uint32_t *d_indices;      // device, mesh-local, not validated
+    const int32_t *mesh_ntris;      // host, validated by check_counts
+    uint32_t n_tris;
+};
+
+// Everything topology.hip needs beside the caller's arrays: room for its tables in the spare set, its scratch, the per-vertex uvs
+// (once) and the per-mesh rows of this call, sent off on `s` through the pinned stage.
+int prepare_topology(rtk_accel *a, const NewTopology &N, hipStream_t s, dev::TopoArgs &T) {
+    const size_t nv = size_t(a->scene.n_vertices), nt = N.n_tris, nm = a->mesh_nverts.size();
+    const bool textured = !a->scene.textures.empty();
+    void **sp = a->topo_spare;
+    size_t *sc = a->topo_spare_cap;
+    RTK_TRY(grow_dev(&sp[T_INDEX], &sc[T_INDEX], nt * 3 * sizeof(uint32_t)));
+    RTK_TRY(grow_dev(&sp[T_INC_OFF], &sc[T_INC_OFF], (nv + 1) * sizeof(uint32_t)));
+    RTK_TRY(grow_dev(&sp[T_INC], &sc[T_INC], nt * 3 * sizeof(uint32_t)));
+    RTK_TRY(grow_dev(&sp[T_OPAQUE], &sc[T_OPAQUE], nt));
+    if (textured) RTK_TRY(grow_dev(&sp[T_TRI_UV], &sc[T_TRI_UV], nt * sizeof(DevTriUv)));
+    size_t kcap = a->topo_keys_cap, temp_bytes = 0;
+    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->topo_keys), &kcap, nt * 3 * sizeof(uint32_t)));
+    a->topo_keys_cap = kcap;
+    RTK_HIP_AS(topology_temp_bytes(uint32_t(nt), uint32_t(nv), &temp_bytes), "size the incidence sort");
+    RTK_TRY(grow_dev(&a->topo_temp, &a->topo_temp_cap, temp_bytes));
+    if (!a->topo_meshes) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->topo_meshes), (nm + 1) * sizeof(dev::TopoMesh)));
+    if (textured && !a->topo_vert_uv) {                                     // kdtree.cpp:283-: a mesh without uvs has zeros
+        std::vector<float> uv(std::max<size_t>(1, nv) * 2, 0.0f);
+        size_t voff = 0;
+        for (size_t mi = 0; mi < nm; ++mi) {
+            const std::vector<float> &mu = a->scene.meshes[mi].uvs;
+            const size_t n = std::min(mu.size(), size_t(a->mesh_nverts[mi]) * 2);
+            if (n > 0) std::memcpy(uv.data() + voff * 2, mu.data(), n * sizeof(float));
+            voff += size_t(a->mesh_nverts[mi]);
+        }
+        int rc;
+        if ((rc = upload(uv, &a->topo_vert_uv)) != RTK_OK) { (void)hipFree(a->topo_vert_uv); a->topo_vert_uv = nullptr; return rc; }
+    }
+    RTK_TRY(grow_pinned(&a->up_stage, &a->up_stage_cap, (nm + 1) * sizeof(dev::TopoMesh)));
+    dev::TopoMesh *rows = reinterpret_cast<dev::TopoMesh *>(a->up_stage);
+    uint32_t tri = 0u, vert = 0u;
+    for (size_t mi = 0; mi <= nm; ++mi) {
+        dev::TopoMesh r{};
+        r.tri_begin = tri; r.vert_begin = vert;
+        if (mi < nm) {
+            const int32_t mat = a->scene.meshes[mi].material;
+            r.n_verts = uint32_t(a->mesh_nverts[mi]);
+            r.material = uint32_t(mat);
+            r.opaque = (size_t(mat) < a->scene.materials.size() && a->scene.materials[size_t(mat)].kind == RTK_MAT_REFRACTIVE) ? 0u : 1u;
+            tri += uint32_t(N.mesh_ntris[mi]); vert += r.n_verts;
+        }
+        rows[mi] = r;
+    }
+    RTK_HIP(hipMemcpyAsync(a->topo_meshes, rows, (nm + 1) * sizeof(dev::TopoMesh), hipMemcpyHostToDevice, s));
+    T.indices = N.d_indices; T.meshes = a->topo_meshes;
+    T.n_meshes = uint32_t(nm); T.n_tris = uint32_t(nt); T.n_verts = uint32_t(nv);
+    T.vert_uv = textured ? a->topo_vert_uv : nullptr;
+    T.index = static_cast<uint32_t *>(sp[T_INDEX]); T.inc_off = static_cast<uint32_t *>(sp[T_INC_OFF]); T.inc = static_cast<uint32_t *>(sp[T_INC]);
+    T.opaque = static_cast<uint8_t *>(sp[T_OPAQUE]);
+    T.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
+    T.tri_uv = textured ? static_cast<DevTriUv *>(sp[T_TRI_UV]) : nullptr;
+    T.keys = a->topo_keys; T.temp = a->topo_temp; T.temp_bytes = temp_bytes;
+    T.hdr = nullptr;                                                        // (the caller's: the table may still be allocated)
+    return RTK_OK;
+}
+
+// The one path of both updates.  `topo` null: the vertices moved and the active topology tables describe the triangles.  Else the
+// tables are made first, into the spare set, and become the active ones where the geometry does: at the very end.
+int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hipStream_t s) {
+    if (topo) RTK_TRY(ensure_update_common(a));
+    else RTK_TRY(ensure_update_static(a));
+    const uint32_t nv = uint32_t(a->scene.n_vertices), nt = topo ? topo->n_tris : uint32_t(a->scene.n_triangles);
     const bool occl = a->occl_on;
-    // per-triangle scratch (the triangle count never changes: allocated once) and the new shading records
-    if (!a->up_tris) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tris), std::max<size_t>(1, nt) * sizeof(DevTri)));
-    if (!a->up_tbox) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_tbox), std::max<size_t>(1, nt) * 6 * sizeof(float)));
+    // per-triangle scratch and the new shading records
+    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_tris), &a->up_tris_cap, size_t(nt) * sizeof(DevTri)));
+    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_tbox), &a->up_tbox_cap, size_t(nt) * 6 * sizeof(float)));
     RTK_TRY(grow_dev(&a->spare[G_SHADE], &a->spare_cap[G_SHADE], size_t(nt) * sizeof(DevShade)));
+    dev::TopoArgs TA{};
+    if (topo) RTK_TRY(prepare_topology(a, *topo, s, TA));
+    const uint32_t *t_index = topo ? TA.index : a->up_index, *t_inc_off = topo ? TA.inc_off : a->up_inc_off, *t_inc = topo ? TA.inc : a->up_inc;
+    const uint8_t *t_opaque = topo ? TA.opaque : a->up_opaque;
     // Capacities of the build: a tree of depth d has at most 2^(d+1) - 1 nodes; the lists of all levels lie one behind the
     // other, a level's lists together are about as long as leaf_refs.  Both are checked on the device; a build that does not fit
     // raises a flag, and is repeated with more room.
     const size_t max_nodes = (size_t(1) << (a->params.max_depth + 1)) - 1;
     size_t want_nodes = a->up_cap_nodes ? a->up_cap_nodes : std::max<size_t>(1024, 4 * a->tree.dev_nodes.size());
-    size_t want_refs = a->up_cap_refs ? a->up_cap_refs
-                                      : std::max<size_t>(4096, 2 * size_t(nt) * size_t(std::min(a->params.max_depth, 12) + 2));
+    const size_t first_refs = std::max<size_t>(4096, 2 * size_t(nt) * size_t(std::min(a->params.max_depth, 12) + 2));
+    size_t want_refs = a->up_cap_refs ? a->up_cap_refs : first_refs;
+    if (topo && want_refs < first_refs) want_refs = first_refs;             // more triangles than the capacity was learnt on: no point in trying it
     dev::BuildHdr hdr;
     for (int attempt = 0;; ++attempt) {
         if (want_nodes > max_nodes) want_nodes = max_nodes;
@@ -115,22 +202,26 @@ int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
         }
         dev::BuildArgs B;
         B.verts = d_verts; B.n_verts = nv; B.n_tris = nt;
-        B.index = a->up_index; B.inc_off = a->up_inc_off; B.inc = a->up_inc;
-        B.opaque = occl ? a->up_opaque : nullptr;
-        B.shade_old = a->d_shade; B.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
+        B.index = t_index; B.inc_off = t_inc_off; B.inc = t_inc;
+        B.opaque = occl ? t_opaque : nullptr;
+        B.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
+        B.shade_old = topo ? B.shade : a->d_shade;                          // (topology.hip wrote mesh / material into the new records)
         B.tris = a->up_tris; B.tbox = a->up_tbox;
         B.ref_id = a->up_ref_id; B.ref_node = a->up_ref_node;
         B.cap_refs = uint32_t(a->up_cap_refs); B.cap_nodes = uint32_t(a->up_cap_nodes);
         B.max_depth = a->params.max_depth; B.max_leaf = a->params.max_leaf_size;
         B.hdr = reinterpret_cast<dev::BuildHdr *>(a->up_table);
         B.nodes = reinterpret_cast<dev::BuildNode *>(a->up_table + sizeof(dev::BuildHdr));
-        RTK_HIP_AS(launch_build(B, s), "launch device build");
+        TA.hdr = B.hdr;
+        // (the topology tables do not depend on the capacities: a repeat keeps them.  Their flag is read after the first attempt.)
+        RTK_HIP_AS(launch_build(B, topo && attempt == 0 ? &TA : nullptr, s), "launch device build");
         // the one place an update blocks the host: flags, sizes and the node table
         RTK_HIP(hipMemcpyAsync(a->up_table_host, a->up_table, sizeof(dev::BuildHdr) + a->up_cap_nodes * sizeof(dev::BuildNode), hipMemcpyDeviceToHost, s));
         RTK_HIP(hipStreamSynchronize(s));
         std::memcpy(&hdr, a->up_table_host, sizeof(hdr));
         const uint32_t raised = ~hdr.ok;
         if (raised & dev::kBuildNonFinite) return fail(RTK_ERR_INVALID, "vertices must be finite");
+        if (raised & dev::kBuildBadIndex) return fail(RTK_ERR_INVALID, "an index is not a vertex of its mesh");
         if ((raised & (dev::kBuildRefOverflow | dev::kBuildNodeOverflow)) == 0u) break;
         if (raised & dev::kBuildNodeOverflow) want_nodes = std::max<size_t>(2 * a->up_cap_nodes, 2 * size_t(hdr.need_nodes));
         if (raised & dev::kBuildRefOverflow) want_refs = std::max<size_t>(2 * a->up_cap_refs, 2 * size_t(hdr.need_refs));
@@ -201,7 +292,7 @@ int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
     }
     dev::GatherArgs G;
     G.leaves = a->up_gather; G.n_leaves = uint32_t(gather.size());
-    G.ref_id = a->up_ref_id; G.tris_in = a->up_tris; G.opaque = occl ? a->up_opaque : nullptr;
+    G.ref_id = a->up_ref_id; G.tris_in = a->up_tris; G.opaque = occl ? t_opaque : nullptr;
     G.tris = static_cast<DevTri *>(sp[G_TRIS]); G.tri_ids = static_cast<uint32_t *>(sp[G_IDS]); G.leaf_refs = static_cast<int32_t *>(sp[G_LREFS]);
     G.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); G.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]);
     RTK_HIP_AS(launch_gather(G, s), "launch k_build_gather");
@@ -221,6 +312,21 @@ int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
         if (i >= G_ONODES && !occl) continue;
         std::swap(*act[i], a->spare[i]);
         std::swap(a->active_cap[i], a->spare_cap[i]);
+    }
+    if (topo) {
+        void **tact[kTopoBufs] = {reinterpret_cast<void **>(&a->up_index), reinterpret_cast<void **>(&a->up_inc_off), reinterpret_cast<void **>(&a->up_inc),
+                                  reinterpret_cast<void **>(&a->up_opaque), reinterpret_cast<void **>(&a->d_tri_uv)};
+        for (int i = 0; i < kTopoBufs; ++i) {
+            if (i == T_TRI_UV && TA.tri_uv == nullptr) continue;
+            std::swap(*tact[i], a->topo_spare[i]);
+            std::swap(a->topo_active_cap[i], a->topo_spare_cap[i]);
+        }
+        a->up_static = true;
+        a->scene.n_triangles = int32_t(nt);
+        a->mesh_ntris.assign(topo->mesh_ntris, topo->mesh_ntris + a->mesh_ntris.size());
+        // the host's copy of the old lists, and what was derived from them: dropped, as the vertices are below
+        for (HostMesh &m : a->scene.meshes) std::vector<uint32_t>().swap(m.indices);
+        std::vector<DevTriUv>().swap(a->tree.dev_tri_uv);
     }
     a->geom_pending = true;
     a->occl_n_leaves = occl ? uint32_t(oleaves.size()) : 0u;
@@ -248,6 +354,24 @@ int update_vertices_impl(rtk_accel *a, const float *d_verts, hipStream_t s) {
     return RTK_OK;
 }
 
+bool any_triangles(const rtk_accel *a, const int32_t *mesh_ntris) {
+    for (size_t mi = 0; mi < a->mesh_nverts.size(); ++mi) if (mesh_ntris[mi] > 0) return true;
+    return false;
+}
+
+// The counts of an update_geometry call, before anything is sized by them.
+int check_counts(const rtk_accel *a, const int32_t *mesh_ntris, uint32_t &total) {
+    uint64_t sum = 0;
+    for (size_t mi = 0; mi < a->mesh_nverts.size(); ++mi) {
+        if (mesh_ntris[mi] < 0) return fail(RTK_ERR_INVALID, "a negative triangle count");
+        if (mesh_ntris[mi] > 0 && a->mesh_nverts[mi] <= 0) return fail(RTK_ERR_INVALID, "triangles on a mesh without vertices");
+        sum += uint64_t(mesh_ntris[mi]);
+    }
+    if (sum * 3 > 0xFFFFFFF0ull || sum > 0x7FFFFFFFull) return fail(RTK_ERR_INVALID, "too many triangles for the device build's 32-bit indices");
+    total = uint32_t(sum);
+    return RTK_OK;
+}
+
 }  // namespace
 
 int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void *hip_stream) {
@@ -258,7 +382,7 @@ int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void
         // entry: nothing issued earlier on this accel, on whatever stream, may still read a buffer the update rewrites
         RTK_HIP(hipDeviceSynchronize());
         a->geom_pending = false;
-        return update_vertices_impl(a, d_vertices, static_cast<hipStream_t>(hip_stream));
+        return update_impl(a, d_vertices, nullptr, static_cast<hipStream_t>(hip_stream));
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }
 
@@ -274,6 +398,50 @@ int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
         a->geom_pending = false;
         if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));   // (the vertex count never changes)
         if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
-        return update_vertices_impl(a, a->up_verts, nullptr);
+        return update_impl(a, a->up_verts, nullptr, nullptr);
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+}
+
+int rtk_accel_update_geometry_device(rtk_accel *a, const float *d_vertices, const uint32_t *d_indices, const int32_t *mesh_ntris, void *hip_stream) {
+    if (!a || !d_vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
+    std::lock_guard<std::mutex> lock(a->mu);
+    try {
+        if (!d_indices && any_triangles(a, mesh_ntris)) return fail(RTK_ERR_INVALID, "null indices");
+        RTK_TRY(ensure_device(a));
+        NewTopology N{d_indices, mesh_ntris, 0u};
+        RTK_TRY(check_counts(a, mesh_ntris, N.n_tris));
+        RTK_HIP(hipDeviceSynchronize());
+        a->geom_pending = false;
+        return update_impl(a, d_vertices, &N, static_cast<hipStream_t>(hip_stream));
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+}
+
+// validate + stage + the device path
+int rtk_accel_update_geometry(rtk_accel *a, const float *vertices, const uint32_t *indices, const int32_t *mesh_ntris) {
+    if (!a || !vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
+    std::lock_guard<std::mutex> lock(a->mu);
+    try {
+        if (!indices && any_triangles(a, mesh_ntris)) return fail(RTK_ERR_INVALID, "null indices");
+        RTK_TRY(ensure_device(a));
+        NewTopology N{nullptr, mesh_ntris, 0u};
+        RTK_TRY(check_counts(a, mesh_ntris, N.n_tris));
+        const size_t n = size_t(a->scene.n_vertices) * 3;
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(vertices[i])) return fail(RTK_ERR_INVALID, "vertices must be finite");
+        size_t t = 0;
+        for (size_t mi = 0; mi < a->mesh_nverts.size(); ++mi) {
+            const uint32_t limit = uint32_t(a->mesh_nverts[mi]);
+            for (size_t e = t * 3, end = (t + size_t(mesh_ntris[mi])) * 3; e < end; ++e)
+                if (indices[e] >= limit) return fail(RTK_ERR_INVALID, "an index is not a vertex of its mesh");
+            t += size_t(mesh_ntris[mi]);
+        }
+        RTK_HIP(hipDeviceSynchronize());
+        a->geom_pending = false;
+        if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));
+        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
+        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_idx_stage), &a->up_idx_stage_cap, size_t(N.n_tris) * 3 * sizeof(uint32_t)));
+        if (N.n_tris > 0u) RTK_HIP(hipMemcpy(a->up_idx_stage, indices, size_t(N.n_tris) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        N.d_indices = a->up_idx_stage;
+        return update_impl(a, a->up_verts, &N, nullptr);
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }

@@ -1,4 +1,5 @@
-// rtk_accel_update_vertices: the accel of a scene whose vertices moved, rebuilt on the device.
+// rtk_accel_update_vertices / rtk_accel_update_geometry: the accel of a scene whose vertices moved, rebuilt on the device.
+// (A new triangle list first becomes the tables of BuildArgs in topology.hip; from there on the two calls are one.)
 //
 // Everything per vertex, per triangle and per (node, triangle) reference happens here; the host sees one table of nodes
 // (build.hpp) and numbers them (kdtree.cpp).  The result is defined bit for bit by the host build (scene.cpp, kdtree.cpp, i.e.
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void k_build_tris(const BuildArgs B) {
         // unit(cross(v1 - v0, v2 - v0)), vec3.hpp:104-108 / 124-131
         const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
         const float inv_length = 1.0f / sqrtf(cx * cx + cy * cy + cz * cz);
-        DevShade sh = B.shade_old[i];                                   // mesh, material: topology
+        DevShade sh = B.shade_old[i];                                   // mesh, material: topology (may be B.shade[i] itself)
         sh.fn[0] = cx * inv_length; sh.fn[1] = cy * inv_length; sh.fn[2] = cz * inv_length;
         B.shade[i] = sh;                                                // (n0..n2: k_build_normals)
         DevTri t;
@@ -348,9 +349,10 @@ __global__ __launch_bounds__(64) void k_build_gather(const GatherArgs G) {
 }  // namespace
 }  // namespace dev
 
-hipError_t launch_build(const dev::BuildArgs &B, hipStream_t s) {
+hipError_t launch_build(const dev::BuildArgs &B, const dev::TopoArgs *topo, hipStream_t s) {
     hipError_t e = hipMemsetAsync(B.hdr, 0xFF, sizeof(dev::BuildHdr), s);
     if (e != hipSuccess) return e;
+    if (topo != nullptr && (e = launch_topology(*topo, s)) != hipSuccess) return e;
     const uint32_t n = B.n_verts > B.n_tris ? B.n_verts : B.n_tris;
     if (n > 0u) {
         hipLaunchKernelGGL(dev::k_build_tris, dim3((n + 255u) / 256u), dim3(256), 0, s, B);

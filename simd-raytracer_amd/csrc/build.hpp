@@ -1,4 +1,4 @@
-// Device kd-tree build for rtk_accel_update_vertices (build.hip): what the kernels and the host share.
+// Device kd-tree build for rtk_accel_update_vertices / _update_geometry (build.hip, topology.hip): what the kernels and the host share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@ struct BuildHdr {
 };
 static_assert(sizeof(BuildHdr) == 128, "BuildHdr must be 128 bytes");
 constexpr uint32_t kBuildNonFinite = 1u, kBuildCoordsBig = 2u, kBuildRefOverflow = 4u, kBuildNodeOverflow = 8u;
+constexpr uint32_t kBuildBadIndex = 16u;     // topology.hip: an index that is not a vertex of its own mesh
 
 struct BuildArgs {
     const float *verts;             // [n_verts][3], the new positions
@@ -30,7 +31,7 @@ struct BuildArgs {
     const uint32_t *inc_off;        // [n_verts + 1] vertex -> incidences
     const uint32_t *inc;            // triangle * 3 + corner, ascending per vertex, duplicates kept
     const uint8_t *opaque;          // [n_tris] 1 = material not refractive; null when no opaque-only tree is kept
-    const DevShade *shade_old;      // mesh / material of every triangle (constant topology)
+    const DevShade *shade_old;      // mesh / material of every triangle: the active records, or `shade` itself after topology.hip filled them in
     DevShade *shade;                // out
     DevTri *tris;                   // out, per triangle
     float *tbox;                    // out, [n_tris][6]
@@ -39,6 +40,33 @@ struct BuildArgs {
     int32_t max_depth, max_leaf;
     BuildHdr *hdr;
     BuildNode *nodes;               // [cap_nodes]
+};
+
+// rtk_accel_update_geometry: one row per mesh and a last one that holds the totals, from the host.
+struct TopoMesh {
+    uint32_t tri_begin, vert_begin;     // prefix sums over the meshes
+    uint32_t n_verts;
+    uint32_t material;
+    uint32_t opaque;                    // 0: the material is refractive
+    uint32_t pad[3];
+};
+static_assert(sizeof(TopoMesh) == 32, "TopoMesh must be 32 bytes");
+
+// What topology.hip makes of a caller's triangle lists: every table the build takes from the topology.
+struct TopoArgs {
+    const uint32_t *indices;        // the caller's: [n_tris][3], mesh-local, NOT validated
+    const TopoMesh *meshes;         // [n_meshes + 1]
+    uint32_t n_meshes, n_tris, n_verts;
+    const float *vert_uv;           // [n_verts][2]; null when the scene has no textures
+    uint32_t *index;                // out: BuildArgs::index, validated
+    uint32_t *inc_off, *inc;        // out: BuildArgs::inc_off / inc
+    uint8_t *opaque;                // out: [n_tris]
+    DevShade *shade;                // out: mesh, material and zero padding of [n_tris] records
+    DevTriUv *tri_uv;               // out: [n_tris]; null when the scene has no textures
+    uint32_t *keys;                 // scratch: [3 n_tris] the vertex ids sorted
+    void *temp;                     // scratch of the sort, topology_temp_bytes() long
+    size_t temp_bytes;
+    BuildHdr *hdr;                  // kBuildBadIndex is raised here
 };
 
 struct GatherArgs {
@@ -56,7 +84,10 @@ struct GatherArgs {
 
 }  // namespace dev
 
-hipError_t launch_build(const dev::BuildArgs &B, hipStream_t s);       // header memset + triangles + vertex normals + tree
+// header memset + (with `topo`: the topology tables, topology.hip) + triangles + vertex normals + tree
+hipError_t launch_build(const dev::BuildArgs &B, const dev::TopoArgs *topo, hipStream_t s);
+hipError_t launch_topology(const dev::TopoArgs &T, hipStream_t s);
+hipError_t topology_temp_bytes(uint32_t n_tris, uint32_t n_verts, size_t *bytes);
 hipError_t launch_gather(const dev::GatherArgs &G, hipStream_t s);
 
 }  // namespace rtk

@@ -237,6 +237,35 @@ struct hip_accel {
         scene_ptr = std::move(moved);
     }
 
+    // The accel after the scene's meshes got other TRIANGLES as well (rtk_accel_update_geometry): `changed` has the same meshes with
+    // the same number of vertices each (positions may differ) and any triangle lists over them -- fewer, more, none.  Materials,
+    // uvs, lights and camera are taken to be the old ones.  scene_ptr then points to it, so hits carry its triangles.
+    void update_geometry(std::shared_ptr<const scene<F>> changed) {
+        if (!changed || changed->meshes.size() != scene_ptr->meshes.size()) throw std::invalid_argument("hip_accel::update_geometry: other meshes");
+        std::vector<float> vertices;
+        std::vector<uint32_t> indices;
+        std::vector<int32_t> mesh_ntris;
+        std::vector<std::size_t> first;
+        std::size_t total = 0;
+        for (std::size_t m = 0; m < changed->meshes.size(); ++m) {
+            const auto &mesh = changed->meshes[m];
+            if (mesh.vertices.size() != scene_ptr->meshes[m].vertices.size())
+                throw std::invalid_argument("hip_accel::update_geometry: a mesh keeps its number of vertices");
+            for (const auto &v : mesh.vertices) { vertices.push_back(v.x); vertices.push_back(v.y); vertices.push_back(v.z); }
+            for (const auto &t : mesh.triangles)
+                for (int k = 0; k < 3; ++k) indices.push_back(static_cast<uint32_t>(t.vertex_indices[k]));
+            mesh_ntris.push_back(static_cast<int32_t>(mesh.triangles.size()));
+            first.push_back(total);
+            total += mesh.triangles.size();
+        }
+        if (vertices.empty()) vertices.push_back(0.f);    // (an empty scene still hands over a pointer)
+        if (mesh_ntris.empty()) mesh_ntris.push_back(0);
+        check(rtk_accel_update_geometry(accel_.get(), vertices.data(), indices.empty() ? nullptr : indices.data(), mesh_ntris.data()));
+        first_triangle_ = std::move(first);
+        n_triangles_ = total;
+        scene_ptr = std::move(changed);
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running

@@ -423,6 +423,51 @@ int rtk_tiles_assemble_device(const rtk_accel *accel, const rtk_render_params *p
 int rtk_camera_rays(rtk_accel *accel, const rtk_render_params *p, int32_t sample, rtk_ray *rays /* host [h*w] */);
 int rtk_camera_rays_device(rtk_accel *accel, const rtk_render_params *p, int32_t sample, rtk_ray *d_rays, void *hip_stream);
 
+/* ---- the camera of a live accel, and many cameras in one call ----
+ * camera<F> (scene/camera.hpp:9-11): position and matrix, row-major -- the layout of rtk_scene_desc.cam_pos / cam_mat; 48 bytes.
+ * The reference keeps the camera a plain mutable member and reads it when a frame starts (render/render.hpp:25); so does the
+ * accel: it is 12 floats of every launch's arguments.  The camera moves of camera.hpp:13-70 are not mirrored: callers compute poses. */
+typedef struct { float position[3]; float matrix[9]; } rtk_view;
+
+int rtk_accel_get_camera(const rtk_accel *accel, rtk_view *out);
+/* After RTK_OK everything that reads the camera -- rtk_render_frame* in every RTK_TRACE_* engine, sharded frames,
+ * rtk_camera_rays*, the counters -- is, bit for bit, what a fresh rtk_accel_build gives for a scene that differs only in cam_pos /
+ * cam_mat.  The tree, the batched intersect / occluded / radiance results and rtk_accel_tree_dump do not depend on it.
+ * The values are taken as they are (as rtk_scene_create takes the scene's).  The call touches no device memory, synchronises
+ * nothing, needs no GPU and works on an accel that has never been on one; frames already enqueued keep the camera they were
+ * launched with.  The camera survives rtk_accel_update_vertices / _geometry.
+ * Neither the cost-feedback launch order nor RTK_TRACE_AUTO's engine verdict changes a result.  The launch order of megakernel
+ * frames STARTS OVER (first-frame prior, then the new camera's costs), as after an update of the geometry, and does so even
+ * when the new camera equals the old one.  Measured at 1920x1080 after a 5 degree step: on the first frame neither
+ * choice wins every run (medians 0.33 ms kept, 0.35 ms reset); the third frame takes 0.20 ms after a reset and 0.30 ms under the
+ * old camera's order, which a kept order serves until its next re-sort.  RTK_CAMERA_KEEPS_ORDER=1 keeps it.
+ * The engine verdict is KEPT: started over at every move, the trial of a camera in motion would never end.
+ * NULL accel or view -> RTK_ERR_INVALID; never RTK_ERR_NO_DEVICE. */
+int rtk_accel_set_camera(rtk_accel *accel, const rtk_view *view);
+
+/* n_views frames of the same rtk_render_params, one per camera: out is [n_views][h][w][3].  View v is, bit for bit and with the
+ * same `rays`, what rtk_accel_set_camera(views[v]) + rtk_render_frame[_device] with *p gives; the accel's own camera is not
+ * changed.  Random numbers are keyed by the pixel index INSIDE the view, sample and seed, as for a frame: equal cameras give
+ * equal views.  sample_begin / sample_count work as for a frame, the running sums of all views live in the output buffer (the
+ * host variant uploads them for a pass with sample_begin > 0).  Counters are summed over the views (primary = n_views * w * h *
+ * samples); rtk_render_last_counters gives the call's totals, rtk_render_last_critical_path its longest block.
+ * What runs: under RTK_TRACE_GROUP4 / 8 / 16, and RTK_TRACE_AUTO on scenes whose ray trees do not fork, with collect_stats == 0,
+ * the pixel blocks of ALL views are the units of one megakernel launch, ordered by cost and packed together (RTK_TRACE_AUTO
+ * chooses its workgroup size by the total).  A call of more than 131,072 blocks is cut into launches of whole views.  Every
+ * other case (LANE / WAVE / STREAM / TWOPASS, forking scenes under AUTO, collect_stats != 0) renders view after view through
+ * the existing engines with the view's camera in the launch arguments: same bits, same counts.
+ * Errors, in this order: what rtk_render_frame refuses for *p; n_views < 0, world_size > 1 (views are not sharded: a multi-GPU
+ * caller deals whole views to ranks), NULL views / output with n_views > 0 -> RTK_ERR_INVALID; then n_views == 0 -> RTK_OK with
+ * nothing touched, device or not; then RTK_ERR_NO_DEVICE.
+ * The device variant (d_views in DEVICE memory, 4-byte aligned) is stream-ordered.  On the one-launch path it never blocks the
+ * host, except that it may allocate, and then synchronise once, when a call needs larger order / cost tables than any call
+ * before it.  On the view-after-view path it copies the views back to the host first (their cameras go into launch
+ * arguments), which waits for `hip_stream` once.  NOT stream-capturable. */
+int rtk_render_views(rtk_accel *accel, const rtk_render_params *p, const rtk_view *views /* host */, int32_t n_views,
+                     float *rgb /* host */, rtk_counters *counters /* may be NULL: totals over the views */);
+int rtk_render_views_device(rtk_accel *accel, const rtk_render_params *p, const rtk_view *d_views /* DEVICE, 4-byte aligned */,
+                            int32_t n_views, float *d_out /* device */, void *hip_stream);
+
 /* ---- image out: replaces write_ppm (io/image/ppm.hpp:7-25) ---- */
 /* The quantisation of write_ppm on the device: out[i] = uint8(255.999 * clamp(rgb[i], 0, 1)) (ppm.hpp:17-19, the product in
  * double), n = number of floats.  A finished frame leaves the GPU as 3 bytes per pixel instead of 12. */

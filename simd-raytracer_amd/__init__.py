@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
+    "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_frame_to_rgb8_device", "rtk_format_ppm_rgb8", "rtk_write_ppm", "rtk_format_ppm",
 ]
 
@@ -171,6 +172,10 @@ _L.rtk_render_last_critical_path.argtypes = [_vp, C.POINTER(C.c_double)]
 _L.rtk_tiles_assemble_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]
 _L.rtk_camera_rays.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp]
 _L.rtk_camera_rays_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, _vp]
+_L.rtk_accel_get_camera.argtypes = [_vp, _vp]
+_L.rtk_accel_set_camera.argtypes = [_vp, _vp]
+_L.rtk_render_views.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, C.POINTER(Counters)]
+_L.rtk_render_views_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, _vp]
 _L.rtk_frame_to_rgb8_device.argtypes = [_vp, C.c_size_t, _vp, _vp]
 _L.rtk_format_ppm_rgb8.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
 _L.rtk_write_ppm.argtypes = [_vp, C.c_int32, C.c_int32, C.c_char_p]
@@ -542,6 +547,46 @@ class KdTreeSimdAccel:
     def camera_rays_device(self, cfg: RenderConfig, d_rays_ptr: int, sample: int = 0, stream: int = 0) -> None:
         p = cfg.to_c()
         _check(_L.rtk_camera_rays_device(self._h, C.byref(p), sample, d_rays_ptr, stream))
+
+    # ---- the camera of a live accel, and many cameras in one call (rtk.h rtk_view: position[3], matrix[9] row-major)
+    def camera(self):
+        """(position [3], matrix [9]) float32: the camera later frames are rendered from."""
+        v = np.zeros(12, np.float32)
+        _check(_L.rtk_accel_get_camera(self._h, v.ctypes.data))
+        return v[:3].copy(), v[3:].copy()
+
+    def set_camera(self, position, matrix) -> None:
+        """Later frames, camera rays and sharded frames are those of a fresh accel of the scene with this camera; needs no GPU."""
+        v = np.concatenate([np.asarray(position, np.float32).reshape(-1), np.asarray(matrix, np.float32).reshape(-1)])
+        if v.shape != (12,):
+            raise ValueError("position has 3 floats, matrix 9 (row-major)")
+        v = np.ascontiguousarray(v)
+        _check(_L.rtk_accel_set_camera(self._h, v.ctypes.data))
+
+    def render_views(self, cfg: RenderConfig, views: np.ndarray, rgb: np.ndarray | None = None):
+        """views: [K, 12] float32 (position, matrix) in host memory -> ([K, h, w, 3] float32, counters summed over the views).
+        View k is what set_camera(views[k]) + render_frame(cfg) gives; the accel's own camera stays.  `rgb`: as for render_frame."""
+        views = np.asarray(views)
+        if views.dtype != np.float32 or views.ndim != 2 or views.shape[1] != 12:
+            raise ValueError("views must be float32 of shape (K, 12)")
+        views = np.ascontiguousarray(views)
+        k = views.shape[0]
+        w = cfg.width or self.scene.info.width
+        h = cfg.height or self.scene.info.height
+        if rgb is None:
+            if cfg.sample_begin > 0:
+                raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
+            rgb = np.zeros((k, h, w, 3), np.float32)
+        assert rgb.dtype == np.float32 and rgb.shape == (k, h, w, 3) and rgb.flags.c_contiguous
+        p = cfg.to_c()
+        c = Counters()
+        _check(_L.rtk_render_views(self._h, C.byref(p), views.ctypes.data if k else None, k, rgb.ctypes.data if k else None, C.byref(c)))
+        return rgb, c.as_dict()
+
+    def render_views_device(self, cfg: RenderConfig, d_views_ptr: int, n_views: int, d_out_ptr: int, stream: int = 0) -> None:
+        """d_views_ptr: device float32 [n_views, 12]; d_out_ptr: device float32 [n_views, h, w, 3]; stream-ordered (rtk.h)."""
+        p = cfg.to_c()
+        _check(_L.rtk_render_views_device(self._h, C.byref(p), d_views_ptr or None, n_views, d_out_ptr or None, stream))
 
     def last_critical_path_ms(self) -> float:
         """Longest 8x8 pixel block of the most recent megakernel frame (ms): the frame's critical path."""

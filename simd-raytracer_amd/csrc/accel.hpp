@@ -47,6 +47,8 @@ struct rtk_knobs {
     int stream_side_below = 2;                              // RTK_STREAM_SIDE_BELOW: k_shadow on side streams while at most this many samples are in flight
     bool first_frame_prior = true;                          // RTK_FIRST_FRAME_PRIOR: launch order of a shape's first frame from k_block_prior
     bool fast_occluders = true;                             // RTK_FAST_OCCLUDERS: RTK_TRAVERSAL_FAST answers occlusion through transmissive surfaces from the opaque triangles alone
+    bool camera_keeps_order = false;                        // RTK_CAMERA_KEEPS_ORDER: rtk_accel_set_camera leaves the cost-feedback launch order of the previous camera in place
+    size_t views_launch_units = 131072;                     // RTK_VIEWS_LAUNCH_UNITS: pixel blocks of one rtk_render_views launch (api_frame.hip; a test lowers it)
     bool traversal_fast = false;                            // RTK_TRAVERSAL_FAST: front-to-back leaf order (rtk.h; NOT the parity mode)
 
     static rtk_knobs from_env() {
@@ -86,8 +88,33 @@ struct rtk_knobs {
         if (geti("RTK_STREAM_MEM_GB", v) && v >= 1 && v <= 256) k.stream_mem_gb = int(v);
         if (geti("RTK_FAST_OCCLUDERS", v)) k.fast_occluders = v != 0;
         if (geti("RTK_STREAM_SIDE_BELOW", v) && v >= 0) k.stream_side_below = int(v);
+        if (geti("RTK_VIEWS_LAUNCH_UNITS", v) && v >= 1 && v <= (1l << 30)) k.views_launch_units = size_t(v);
+        if (geti("RTK_CAMERA_KEEPS_ORDER", v)) k.camera_keeps_order = v != 0;
         if (geti("RTK_STREAM_LANES", v) && v >= 1 && v <= rtk::dev::kStreamLanes) k.stream_lanes = int(v);
         return k;
+    }
+};
+
+// Per-pixel-block cost of the last frame of shape `sig`, and the launch order made from it.
+struct rtk_cost_feedback {
+    uint32_t *cost = nullptr, *order = nullptr;
+    uint8_t *bins = nullptr;
+    size_t units = 0;
+    uint64_t sig[5] = {0, 0, 0, 0, 0};
+    bool valid = false;              // cost holds the costs of a frame of shape sig
+    bool order_valid = false;        // order was made from such costs
+    unsigned age = 0;                // frames rendered with the current order
+    // number of workgroups in order's workgroup list, read back behind the sort that made it (pinned host word + event)
+    uint32_t *nwgs_host = nullptr;
+    hipEvent_t nwgs_ev = nullptr;
+    bool nwgs_pending = false, nwgs_known = false;
+
+    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; }
+    void release() {
+        (void)hipFree(cost); (void)hipFree(order); (void)hipFree(bins);
+        if (nwgs_ev) (void)hipEventDestroy(nwgs_ev);
+        if (nwgs_host) (void)hipHostFree(nwgs_host);
+        *this = rtk_cost_feedback();
     }
 };
 
@@ -150,18 +177,17 @@ struct rtk_accel {
     uint32_t *tp_bins = nullptr;       // [kCostBins] counts, [1] n_listed
     uint32_t *tp_bin_list = nullptr, *tp_order = nullptr;
     size_t tp_pixels = 0, tp_tiles = 0;
-    // ---- fb_*: cost feedback (megakernel frames): per-pixel-block cost of the last frame of shape fb_sig, and the order made from it
-    uint32_t *fb_cost = nullptr, *fb_order = nullptr;
-    uint8_t *fb_bins = nullptr;
-    size_t fb_units = 0;
-    uint64_t fb_sig[4] = {0, 0, 0, 0};
-    bool fb_valid = false;           // fb_cost holds the costs of a frame of shape fb_sig
-    bool fb_order_valid = false;     // fb_order was made from such costs
-    unsigned fb_age = 0;             // frames rendered with the current order
-    // number of workgroups in fb_order's workgroup list, read back behind the sort that made it (pinned host word + event)
-    uint32_t *fb_nwgs_host = nullptr;
-    hipEvent_t fb_nwgs_ev = nullptr;
-    bool fb_nwgs_pending = false, fb_nwgs_known = false;
+    // ---- fb / fb_views: cost feedback (megakernel frames, api_frame.hip render_megakernel).  Frames have one set of tables;
+    // rtk_render_views has one per launch of a call (a call is cut into launches of whole views), so that a caller who
+    // alternates frames and views calls keeps the order of both.
+    rtk_cost_feedback fb;
+    std::vector<rtk_cost_feedback> fb_views;
+    // ---- views_*: rtk_render_views (api_frame.hip).  The host variant's staging (view table, output) grows and never shrinks.
+    float *views_tab = nullptr;
+    size_t views_tab_cap = 0;                  // views
+    float *views_out = nullptr;
+    size_t views_out_cap = 0;                  // floats
+    unsigned long long *d_views_counters = nullptr;   // [kCounterWords] the call's totals while its frames / launches run
     // ---- trial_*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     hipEvent_t trial_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t trial_sig[3] = {0, 0, 0};

@@ -355,7 +355,9 @@ void rtk_accel_destroy(rtk_accel *a) {
             }
         (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
         (void)hipFree(a->rp_bounds); (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
-        (void)hipFree(a->fb_cost); (void)hipFree(a->fb_order); (void)hipFree(a->fb_bins);
+        a->fb.release();
+        for (rtk_cost_feedback &f : a->fb_views) f.release();
+        (void)hipFree(a->views_tab); (void)hipFree(a->views_out); (void)hipFree(a->d_views_counters);
         (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
         (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb); (void)hipFree(a->d_rad_counters);
         if (a->ws_done) (void)hipEventDestroy(a->ws_done);
@@ -363,8 +365,6 @@ void rtk_accel_destroy(rtk_accel *a) {
         if (a->rp_done) (void)hipEventDestroy(a->rp_done);
         if (a->rp_probe_ev) (void)hipEventDestroy(a->rp_probe_ev);
         if (a->rp_host) (void)hipHostFree(a->rp_host);
-        if (a->fb_nwgs_ev) (void)hipEventDestroy(a->fb_nwgs_ev);
-        if (a->fb_nwgs_host) (void)hipHostFree(a->fb_nwgs_host);
     }
     delete a;
 }

@@ -348,8 +348,8 @@ int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hip
     a->coords_small = (~hdr.ok & dev::kBuildCoordsBig) == 0u;
     a->stream_slices_auto = stream_slices_for(a->tree);
     // the launch order learnt from the old silhouette and the engines' trial on it say nothing about the new geometry
-    a->fb_valid = false; a->fb_order_valid = false; a->fb_age = 0;
-    a->fb_nwgs_pending = false; a->fb_nwgs_known = false;
+    a->fb.forget();
+    for (rtk_cost_feedback &f : a->fb_views) f.forget();
     a->trial_state = 0;
     return RTK_OK;
 }

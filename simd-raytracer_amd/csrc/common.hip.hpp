@@ -117,7 +117,9 @@ __device__ __forceinline__ float albedo_reach(const V3 a) {
 __device__ __forceinline__ bool unlit_query(const float contrib, const float reach) { return contrib * reach == 0.0f; }
 
 // Camera ray of pixel (px, py) (render.hpp:35-62); `key` is the sample's root key (draws 0 and 1 jitter the sample).
-__device__ __forceinline__ Ray camera_ray(const RenderArgs &A, const uint32_t px, const uint32_t py, const uint32_t key) {
+// `pos` [3], `M` [9]: the camera -- the launch arguments' own (camera_ray), or a view of the table of a views launch.
+__device__ __forceinline__ Ray camera_ray_of(const RenderArgs &A, const float *pos, const float *M, const uint32_t px, const uint32_t py,
+                                             const uint32_t key) {
     float rx = (float)px, ry = (float)py;
     if (A.spp == 1) { rx += 0.5f; ry += 0.5f; }
     else {
@@ -130,11 +132,14 @@ __device__ __forceinline__ Ray camera_ray(const RenderArgs &A, const uint32_t px
     sx *= A.aspect;
     sx *= A.tan_half_fov;                                       // render.hpp:55-57: float *= tanf(float) (host, api_frame.hip camera_args)
     sy *= A.tan_half_fov;
-    const float *M = A.cam_mat;                                 // transpose(camera.matrix) * dir
+    // transpose(camera.matrix) * dir
     V3 d = mk(M[0] * sx + M[3] * sy + M[6] * -1.0f, M[1] * sx + M[4] * sy + M[7] * -1.0f,
               M[2] * sx + M[5] * sy + M[8] * -1.0f);
     d = normalized(d);
-    return make_ray(mk(A.cam_pos[0], A.cam_pos[1], A.cam_pos[2]), d);
+    return make_ray(mk(pos[0], pos[1], pos[2]), d);
+}
+__device__ __forceinline__ Ray camera_ray(const RenderArgs &A, const uint32_t px, const uint32_t py, const uint32_t key) {
+    return camera_ray_of(A, A.cam_pos, A.cam_mat, px, py, key);
 }
 
 }  // namespace dev

@@ -179,7 +179,7 @@ struct Frame {            // 15 dwords, lives in scratch; touched only at refrac
     uint32_t key;         // RNG key of the ray whose hit this frame shades
 };
 
-template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRIMED = false>
+template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRIMED = false, bool VIEWS = false>
 // GROUP4 without per-ray statistics is built for RTK_G4_WAVES (5) waves per SIMD = 96 VGPRs: a fifth resident workgroup per CU.
 // The lean build (FORKS = false) fits with its cold state parked in LDS (`park_lds`); 4 waves / 128 VGPRs and 6 / 80 are slower.
 __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : SLICES == 8 ? 2 : (SLICES == 4 && !STATS ? RTK_G4_WAVES : 4)) void k_render(RenderArgs A) {
@@ -227,6 +227,18 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         const uint32_t unit = SLICES > 1 ? blockIdx.x : blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
         gwave = (A.order_in != nullptr && unit < A.n_units) ? A.order_in[unit] : unit;
     }
+    // VIEWS (rtk_render_views as one launch): the units in the lists above are (view, pixel block) pairs.  The view belongs to the
+    // WAVE's unit, never to the workgroup: the four blocks of a light workgroup may come from four views.  It is wave-uniform
+    // (gwave is), so the camera is fetched through the scalar cache like a node, and the output pointer is a scalar add.  Only the
+    // view's number is kept: the two pointers are made where they are used (a camera ray, the pixel's store), four scalar registers
+    // less across the traversal.
+    uint32_t block = gwave, view = 0u;
+    if constexpr (VIEWS) {
+        view = (uint32_t)__builtin_amdgcn_readfirstlane((int)(gwave / A.units_per_view));
+        if (view >= A.n_views) return;                   // purely defensive: launch_render refuses a launch whose units are not n_views x units_per_view
+        block = gwave - view * A.units_per_view;
+    }
+    const auto view_out = [&]() { return VIEWS ? A.out + (size_t)view * A.view_stride : A.out; };
     // one parking area per wave that can own rays: every wave of a light or SLICES == 1 workgroup, one otherwise -- the
     // others then hold the answers of a light burst's jobs (ShadowBurstService)
     constexpr int kParkSlots = 4;                        // light workgroups exist for SLICES == 4 only (api_frame.hip)
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     constexpr bool writer = true;
     // (block_map() / block_pixel() written out: through them the benchmark's kernel loses its register allocation)
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint32_t local_bucket = gwave / bpb, sub = gwave % bpb;
+    const uint32_t local_bucket = block / bpb, sub = block % bpb;
     const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
     bool valid = bucket < A.n_buckets;
     const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
@@ -285,7 +297,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     V3 pixel_sum = black, ret = black;
     if (A.sample_begin > 0 && valid) {                                     // a later pass of a progressive frame: the running sum so far
         const Pixel p = my_pixel();
-        const float *o = A.out + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
+        const float *o = view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
         pixel_sum = mk(o[0], o[1], o[2]);
     }
     // hit being shaded / lit
@@ -315,7 +327,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                     const float inv = A.spp_f;
                     if (writer) {
                         const Pixel p = my_pixel();
-                        float *o = A.out + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
+                        float *o = view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
                         // the last pass divides (render.hpp:72; x / 1.0f == x, bit for bit); earlier passes leave the running sum
                         if (A.spp == 1 || A.sample_end != A.spp) { o[0] = pixel_sum.x; o[1] = pixel_sum.y; o[2] = pixel_sum.z; }
                         else { o[0] = pixel_sum.x / inv; o[1] = pixel_sum.y / inv; o[2] = pixel_sum.z / inv; }
@@ -325,7 +337,12 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 }
                 const Pixel p = my_pixel();
                 rkey = root_key(seed_hash, p.py * A.width + p.px, (uint32_t)sample);
-                ray = camera_ray(A, p.px, p.py, rkey);
+                // (the RNG key is the pixel's index inside ITS view: equal cameras give equal views)
+                if constexpr (VIEWS) {
+                    const float *cam = A.views + (size_t)view * 12u;
+                    ray = camera_ray_of(A, cam, cam + 3, p.px, p.py, rkey);
+                }
+                else ray = camera_ray(A, p.px, p.py, rkey);
                 mirror_apex = ray.o;
                 cull = true; depth = 0; pend = PEND_CHILD_BG; fsp = 0;
                 primed = PRIMED;
@@ -648,7 +665,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const uint32_t lane = fresh_lane();
     if (kPhases && valid && writer) {
         const Pixel p = my_pixel();
-        phases.write(sx.probe(), lane, A.out + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3);
+        phases.write(sx.probe(), lane, view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3);
     }
     if (A.cost_out != nullptr && lane == 0u && gwave < A.n_units) {        // what this block cost, for the next frame's order
         // (a block that ran alone on one wave of a packed workgroup took about twice as long as it would with helpers)
@@ -802,6 +819,14 @@ hipError_t launch_render_m(const dev::RenderArgs &A, unsigned blocks, bool lds, 
     return hipGetLastError();
 }
 
+// rtk_render_views as one launch: the GROUP modes without per-ray statistics
+template <int SLICES>
+hipError_t launch_render_views_m(const dev::RenderArgs &A, unsigned blocks, bool forks, hipStream_t s) {
+    if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, true, false, SLICES, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
+    else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, SLICES, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
+    return hipGetLastError();
+}
+
 template <int MODE, int SLICES>
 hipError_t launch_render_mode(const dev::RenderArgs &A, unsigned blocks, bool stats, bool forks, bool lds, size_t lds_bytes,
                               hipStream_t s) {
@@ -837,9 +862,20 @@ hipError_t launch_render(const dev::RenderArgs &A, int mode, bool stats, bool fo
     const size_t lds_bytes = (size_t)A.tree.n_nodes * sizeof(DevNode);
     const bool lds = lds_bytes <= kMaxNodeLdsBytes;
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint64_t waves = (uint64_t)A.buckets_per_rank * bpb;          // one per 8x8 pixel block
+    const uint64_t waves = (uint64_t)A.buckets_per_rank * bpb * (A.views != nullptr ? A.n_views : 1u);   // one per 8x8 pixel block (of every view)
     if (waves == 0) return hipSuccess;
     if (waves > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (A.views != nullptr) {
+        // (view, block) units: the caller made them consistent; whoever did not gets an error, not a kernel that indexes by them
+        if (stats || (uint64_t)A.units_per_view * A.n_views != waves || A.n_units != waves) return hipErrorInvalidValue;
+        const unsigned listed = (n_workgroups != 0u && n_workgroups < waves) ? n_workgroups : (unsigned)waves;
+        switch (mode) {
+            case RTK_TRACE_GROUP4: return launch_render_views_m<4>(A, listed, forks, s);
+            case RTK_TRACE_GROUP8: return launch_render_views_m<8>(A, (unsigned)waves, forks, s);
+            case RTK_TRACE_GROUP16: return launch_render_views_m<16>(A, (unsigned)waves, forks, s);
+            default: return hipErrorInvalidValue;
+        }
+    }
     const unsigned packed = (unsigned)((waves + 3) / 4);                  // 4 pixel blocks per workgroup
     switch (mode) {
         case RTK_TRACE_LANE: return launch_render_mode<RTK_TRACE_LANE, 1>(A, packed, stats, forks, lds, lds_bytes, s);
@@ -863,15 +899,23 @@ hipError_t launch_render(const dev::RenderArgs &A, int mode, bool stats, bool fo
 //   (2 is kept for a class to be started before both)
 // Only the launch order depends on the classes, no result.  From the second frame on the measured costs take over.
 namespace dev {
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void k_block_prior(RenderArgs A, uint8_t *cls, uint32_t *count /* [3], zeroed */) {
     const uint32_t unit = blockIdx.x * blockDim.x + threadIdx.x;
     const bool have = unit < A.n_units;
-    const BlockMap blk = block_map(A, have ? unit : 0u);
+    // VIEWS: unit = view * units_per_view + block, and the probe rays leave that view's camera (a thread each: per-lane loads)
+    const uint32_t view = (VIEWS && have) ? unit / A.units_per_view : 0u;
+    const BlockMap blk = block_map(A, have ? unit - view * (VIEWS ? A.units_per_view : 0u) : 0u);
     const uint32_t x0 = blk.bx + blk.sub_x0, y0 = blk.by + blk.sub_y0;
     const bool in_frame = have && blk.bucket < A.n_buckets && x0 < A.width && y0 < A.height;
     const uint32_t x1 = x0 + 7u < A.width ? x0 + 7u : A.width - 1u, y1 = y0 + 7u < A.height ? y0 + 7u : A.height - 1u;
     RenderArgs P = A;
     P.spp = 1;                                                                  // pixel centres: this is an estimate
+    if constexpr (VIEWS) {
+        const float *cam = A.views + (size_t)(view < A.n_views ? view : 0u) * 12u;
+        for (int i = 0; i < 3; ++i) P.cam_pos[i] = cam[i];
+        for (int i = 0; i < 9; ++i) P.cam_mat[i] = cam[3 + i];
+    }
     const float4 *root = reinterpret_cast<const float4 *>(A.tree.nodes);
     const float4 r0 = root[0], r1 = root[1];
     float t_min;
@@ -932,8 +976,24 @@ hipError_t launch_block_prior(const dev::RenderArgs &A, uint8_t *cls, uint32_t *
     // (`scratch` comes zeroed: it lies behind the frame's counters and is cleared with them -- a fill of its own, two in fact for 24
     // bytes, was 15 us in front of the first frame)
     const unsigned blocks = (A.n_units + 255u) / 256u;
-    hipLaunchKernelGGL(dev::k_block_prior, dim3(blocks), dim3(256), 0, s, A, cls, scratch);
+    if (A.views != nullptr) hipLaunchKernelGGL(dev::k_block_prior<true>, dim3(blocks), dim3(256), 0, s, A, cls, scratch);
+    else hipLaunchKernelGGL(dev::k_block_prior<false>, dim3(blocks), dim3(256), 0, s, A, cls, scratch);
     hipLaunchKernelGGL(dev::k_prior_layout, dim3(blocks), dim3(256), 0, s, cls, scratch, scratch + 3, order, wg_list, hdr, A.n_units, pack);
+    return hipGetLastError();
+}
+
+namespace dev {
+__global__ __launch_bounds__(256) void k_counters_fold(const unsigned long long *cur, unsigned long long *acc) {
+    const uint32_t i = threadIdx.x;
+    if (i >= (uint32_t)kCounterWords) return;
+    const bool longest = i >= (uint32_t)kCriticalWord;                      // the critical path of a call is its longest block
+    const unsigned long long a = acc[i], c = cur[i];
+    acc[i] = longest ? (a < c ? c : a) : a + c;
+}
+}  // namespace dev
+
+hipError_t launch_counters_fold(const unsigned long long *cur, unsigned long long *acc, hipStream_t s) {
+    hipLaunchKernelGGL(dev::k_counters_fold, dim3(1), dim3(256), 0, s, cur, acc);
     return hipGetLastError();
 }
 

@@ -106,6 +106,11 @@ struct RenderArgs {
     // query of the streaming pipeline (k_shadow) is ONE any-hit query against it instead of is_occluded's stepping loop (rtk.h)
     int occl_on;
     TreeView occl;
+    // rtk_render_views as ONE launch (k_render<..., VIEWS>; api_frame.hip render_views_impl / render_megakernel): the launch's units are (view, pixel
+    // block) pairs, unit = view * units_per_view + block, and n_units counts them all.  Null / 0 for a frame.
+    const float *views;               // [n_views][12] position, matrix (rtk_view), on the device
+    uint32_t n_views, units_per_view;
+    size_t view_stride;               // floats from one view's output to the next (width * height * 3)
 
     __device__ __forceinline__ size_t out_index(uint32_t local_bucket, uint32_t lx, uint32_t ly, uint32_t px,
                                                 uint32_t py) const {
@@ -136,6 +141,9 @@ hipError_t launch_order_by_cost(const uint32_t *cost, uint8_t *bins /* [n] scrat
 // to a workgroup.  cls [n_units] and scratch [6] are work space.
 hipError_t launch_block_prior(const dev::RenderArgs &A, uint8_t *cls, uint32_t *order, uint32_t *wg_list, uint32_t *hdr,
                               uint32_t *scratch, uint32_t pack, hipStream_t s);
+// a call made of several frames (the views of a fallback rtk_render_views, the launches of a chunked one): acc[] += cur[] for the
+// counts, max for the critical-path words; both [kCounterWords]
+hipError_t launch_counters_fold(const unsigned long long *cur, unsigned long long *acc, hipStream_t s);
 hipError_t launch_twopass(const dev::RenderArgs &A, bool stats, bool forks, hipStream_t s);
 hipError_t launch_assemble(const dev::AssembleArgs &A, hipStream_t s);
 hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_rays, hipStream_t s);

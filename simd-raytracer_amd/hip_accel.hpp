@@ -19,6 +19,7 @@
 #include <cstring>
 #include <memory>
 #include <optional>
+#include <span>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -266,6 +267,45 @@ struct hip_accel {
         scene_ptr = std::move(changed);
     }
 
+    // The camera of later frames (rtk_accel_set_camera): what constructing a new accel from the scene with this viewpoint would
+    // render.  Moves the ACCEL ONLY: scene_ptr->viewpoint stays (the scene is const); camera_now() reads the accel's back.
+    void set_camera(const camera<F> &c) {
+        const rtk_view v = to_view(c);
+        check(rtk_accel_set_camera(accel_.get(), &v));
+    }
+    [[nodiscard]] camera<F> camera_now() const {
+        rtk_view v{};
+        check(rtk_accel_get_camera(accel_.get(), &v));
+        camera<F> c{};
+        c.position = vec3<F>{v.position[0], v.position[1], v.position[2]};
+        for (std::size_t i = 0; i < 9; ++i) c.matrix.m[i] = v.matrix[i];
+        return c;
+    }
+
+    // One whole frame per camera from one call (rtk_render_views): image v is what set_camera(views[v]) + render_frame(params)
+    // gives, and the accel's own camera stays.  counters: totals over the views.
+    [[nodiscard]] std::vector<std::vector<std::vector<color<F>>>> render_views(std::span<const camera<F>> views, const rtk_render_params &params,
+                                                                              rtk_counters *counters = nullptr) const {
+        if (params.sample_begin != 0 || (params.sample_count != 0 && params.sample_count != params.spp))
+            throw std::invalid_argument("hip_accel::render_views renders whole frames (sample_begin = 0, all spp samples)");
+        std::size_t n = 0;
+        check(rtk_render_output_floats(accel_.get(), &params, &n));
+        std::vector<rtk_view> in(views.size());
+        for (std::size_t v = 0; v < views.size(); ++v) in[v] = to_view(views[v]);
+        std::vector<float> rgb(n * views.size() + 1);
+        check(rtk_render_views(accel_.get(), &params, in.empty() ? nullptr : in.data(), static_cast<int32_t>(views.size()), rgb.data(), counters));
+        const std::size_t w = params.width > 0 ? static_cast<std::size_t>(params.width) : scene_ptr->config.image_width;
+        const std::size_t h = n / 3 / w;
+        std::vector<std::vector<std::vector<color<F>>>> out(views.size(), std::vector<std::vector<color<F>>>(h, std::vector<color<F>>(w)));
+        for (std::size_t v = 0; v < views.size(); ++v)
+            for (std::size_t y = 0; y < h; ++y)
+                for (std::size_t x = 0; x < w; ++x) {
+                    const float *px = rgb.data() + v * n + (y * w + x) * 3;
+                    out[v][y][x] = color<F>{px[0], px[1], px[2]};
+                }
+        return out;
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running
@@ -309,6 +349,13 @@ private:
     std::shared_ptr<rtk_accel> accel_;
     std::vector<std::size_t> first_triangle_;     // global triangle index of each mesh's first triangle
     std::size_t n_triangles_ = 0;
+
+    static rtk_view to_view(const camera<F> &c) noexcept {
+        rtk_view v{};
+        v.position[0] = c.position.x; v.position[1] = c.position.y; v.position[2] = c.position.z;
+        for (std::size_t i = 0; i < 9; ++i) v.matrix[i] = c.matrix.m[i];
+        return v;
+    }
 
     static void check(int rc) {
         if (rc != RTK_OK) throw std::runtime_error(std::string("rtk: ") + rtk_last_error());

@@ -3,9 +3,9 @@
 TEST INFRASTRUCTURE ONLY.  Allowed importers: tests/, __graft_entry__.smoke(), and the
 cpu_baseline leg of bench.py.  The product package (simd-raytracer_amd/) never imports this.
 
-Parity-pin status: see oracle/rt_oracle.h — pinned by the reference's own committed renders
-(tests/golden/ref_outputs/, every byte of refractive_dragon.png and textures.png) and by the
-reference-measured counters recorded in SURVEY.md.
+Parity-pin status: see oracle/rt_oracle.h — pinned bit for bit by a build of the reference's own headers (RefProbe below,
+oracle/ref_probe.cpp; tests/test_ref_probe.py), by the reference's own committed renders (tests/golden/ref_outputs/, every
+byte of refractive_dragon.png and textures.png) and by the reference-measured counters recorded in SURVEY.md.
 """
 from __future__ import annotations
 
@@ -136,6 +136,7 @@ def _lib(fast: bool = False, isa: str | None = None):
     L.ora_accel_dump.argtypes = [vp, vp, vp, vp]
     L.ora_scene_vertex_normals.argtypes = [vp, C.c_int, vp]
     L.ora_intersect.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
+    L.ora_intersect_rest.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
     L.ora_render_frame.restype = C.c_int
     L.ora_render_frame.argtypes = [vp, C.POINTER(_RenderParams), vp, vp]
     L.ora_camera_rays.restype = C.c_int
@@ -431,6 +432,13 @@ class Accel:
         self.L.ora_intersect(self.h, rays.ctypes.data, rays.shape[0], 1 if cull else 0, out.ctypes.data, cp)
         return out
 
+    def intersect_rest(self, rays: np.ndarray, cull: bool) -> dict:
+        """The fields of hit<F> that HIT_DTYPE leaves out: position [n,3], face_normal [n,3], uvs [n,6], w [n] (zeros on a miss)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((rays.shape[0], 16), np.float32)
+        self.L.ora_intersect_rest(self.h, rays.ctypes.data, rays.shape[0], 1 if cull else 0, out.ctypes.data)
+        return {"position": out[:, 0:3], "face_normal": out[:, 3:6], "uvs": out[:, 6:12], "w": out[:, 12]}
+
     def render(self, width=0, height=0, spp=1, max_depth=5, diffuse_rays=0, seed=42, fov_degrees=90.0,
                shadow_bias=1e-4, reflection_bias=1e-4, refraction_bias=1e-4, n_threads=0, count_work=True):
         p = _RenderParams(width, height, spp, max_depth, diffuse_rays, seed, fov_degrees,
@@ -488,3 +496,134 @@ def sincos(angle: float):
     s, c = C.c_float(), C.c_float()
     _lib().ora_sincos(np.float32(angle), C.byref(s), C.byref(c))
     return s.value, c.value
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The live build of the reference: oracle/ref_probe.cpp over the reference's own headers (recipe: oracle/ref.mk).
+# oracle/_ref/ is never committed; tests/golden/ref_probe/ holds arrays it wrote (tools/make_ref_probe_fixtures.py).
+
+from .ref_build import REF_COMPILER, REF_OUT, build_ref, reference_dir  # noqa: E402,F401
+
+FLT_MIN = 1.17549435e-38
+# name: (max_depth, max_leaf_size, eps); keep in step with oracle/ref.mk
+REF_TREES = {
+    "default": (8, 64, 1e-6), "root_leaf": (0, 64, 1e-6), "d12_l8": (12, 8, 1e-6), "d13_l4": (13, 4, 1e-6),
+    "d16_l1": (16, 1, 1e-6), "long_leaves": (8, 1000, 1e-6),
+    "eps_flt_min": (8, 64, FLT_MIN), "eps_1e-9": (8, 64, 1e-9), "eps_1e-3": (8, 64, 1e-3), "eps_0.25": (8, 64, 0.25),
+}
+_REF_ISA_FLAGS = {4: set(), 8: {"avx2", "fma", "bmi2"}, 16: {"avx512f", "avx512vl", "avx512bw", "avx512dq", "avx512cd"}}
+REF_HIT_DTYPE = np.dtype([("hit", "<u4"), ("mesh", "<u4"), ("tri", "<u4"), ("owners", "<u4"), ("t", "<f4"), ("u", "<f4"),
+                          ("v", "<f4"), ("w", "<f4"), ("position", "<f4", (3,)), ("hit_normal", "<f4", (3,)),
+                          ("face_normal", "<f4", (3,)), ("uvs", "<f4", (6,)), ("pad", "<u4")])
+assert REF_HIT_DTYPE.itemsize == 96
+REF_TIMEOUT_S = 600          # per probe command; the largest one of the suite (a 1080p frame) takes about a second
+
+
+def ref_widths() -> list:
+    """Packet widths (native_simd<float>::size()) whose binaries this host can run."""
+    fl = _cpu_flags()
+    return [w for w, need in _REF_ISA_FLAGS.items() if need <= fl]
+
+
+def ref_binary(width: int = 8, depth: int = 5, tree: str = "default", scalar: bool = False) -> str:
+    name = f"ref_probe_scalar_d{depth}_{tree}" if scalar else f"ref_probe_w{width}_d{depth}_{tree}"
+    return os.path.join(REF_OUT, name)
+
+
+def ref_available(width: int = 8, depth: int = 5, tree: str = "default", scalar: bool = False) -> bool:
+    return (scalar or width in ref_widths()) and os.access(ref_binary(width, depth, tree, scalar), os.X_OK)
+
+
+def write_scene_dump(flat: FlatScene, path: str, width: int = 0, height: int = 0) -> None:
+    """Everything of `flat` the probe builds scene<float> from, as one flat little-endian file (layout: load_scene in
+    ref_probe.cpp): a header of 13 int32, then the arrays, each padded to a multiple of 4 bytes."""
+    n = len(flat.mat_kind)
+    nm = len(flat.mesh_material)
+    opt = lambda a, d: np.ascontiguousarray(d if a is None else a)
+    tex_kind = opt(flat.tex_kind, np.zeros(0, np.int32)).astype(np.int32)
+    nt = len(tex_kind)
+    pixels = opt(flat.tex_pixels, np.zeros(0, np.uint8)).astype(np.uint8)
+    uvs = opt(flat.uvs, np.zeros((0, 2), np.float32)).astype(np.float32).reshape(-1, 2)
+    verts = np.ascontiguousarray(flat.vertices, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(flat.indices, np.uint32).reshape(-1, 3)
+    head = np.array([0x534B5452, 1, nm, n, nt, len(flat.light_intensity), width or flat.width, height or flat.height,
+                     flat.bucket_size, len(verts), len(idx), len(uvs), pixels.size], np.int32)
+    parts = [
+        head, np.asarray(flat.mesh_material, np.int32), np.asarray(flat.mesh_nverts, np.int32), np.asarray(flat.mesh_ntris, np.int32),
+        opt(flat.mesh_has_uvs, np.zeros(nm, np.int32)).astype(np.int32), verts, idx, uvs,
+        np.asarray(flat.mat_kind, np.int32), np.asarray(flat.mat_albedo, np.float32), np.asarray(flat.mat_ior, np.float32),
+        np.asarray(flat.mat_smooth, np.int32), opt(flat.mat_texture, np.full(n, -1, np.int32)).astype(np.int32),
+        tex_kind, opt(flat.tex_color_a, np.zeros((nt, 3), np.float32)).astype(np.float32),
+        opt(flat.tex_color_b, np.zeros((nt, 3), np.float32)).astype(np.float32),
+        opt(flat.tex_param, np.zeros(nt, np.float32)).astype(np.float32),
+        opt(flat.tex_bitmap, np.zeros((nt, 3), np.int32)).astype(np.int32), pixels,
+        np.asarray(flat.light_pos, np.float32), np.asarray(flat.light_intensity, np.float32),
+        np.asarray(flat.cam_pos, np.float32), np.asarray(flat.cam_mat, np.float32), np.asarray(flat.background, np.float32),
+    ]
+    with open(path, "wb") as f:
+        for a in parts:
+            b = np.ascontiguousarray(a).tobytes()
+            f.write(b + b"\0" * (-len(b) % 4))
+
+
+class RefProbe:
+    """One scene in front of one variant of the probe.  Every call starts the binary afresh (subprocess), files in a
+    temporary directory.  size = (width, height) of `frame`; default: the scene's own."""
+
+    def __init__(self, flat: FlatScene, width: int = 8, depth: int = 5, tree: str = "default", scalar: bool = False, size=None):
+        import tempfile
+        self.binary = ref_binary(width, depth, tree, scalar)
+        self.scalar = scalar
+        self.size = size or (flat.width, flat.height)
+        self._tmp = tempfile.TemporaryDirectory(prefix="ref_probe_")
+        self._scene = os.path.join(self._tmp.name, "scene.bin")
+        write_scene_dump(flat, self._scene, *self.size)
+        self.calls = self.hits = self.width = None       # of the last command
+        self.argv = None
+
+    def _run(self, cmd: str, data: bytes | None) -> bytes:
+        inp, out = os.path.join(self._tmp.name, "in.bin"), os.path.join(self._tmp.name, "out.bin")
+        if data is not None:
+            with open(inp, "wb") as f:
+                f.write(data)
+        self.argv = [self.binary] + (["--scalar"] if self.scalar else []) + [self._scene, cmd, inp if data is not None else "-", out]
+        # the reference's is_occluded loop has no bound: a query that never ends must fail the test, not hang the suite
+        r = subprocess.run(self.argv, capture_output=True, text=True, timeout=REF_TIMEOUT_S)
+        if r.returncode != 0:
+            raise RuntimeError(f"{' '.join(self.argv)}: exit {r.returncode}: {r.stderr.strip()}")
+        kv = dict(x.split("=") for x in r.stdout.split())
+        self.calls, self.hits, self.width = int(kv["calls"]), int(kv["hits"]), int(kv["width"])
+        with open(out, "rb") as f:
+            return f.read()
+
+    @staticmethod
+    def _rays(rays) -> np.ndarray:
+        return np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+
+    def tree(self):
+        """-> (box [n,6], link [n,4], leaf_refs) as ora.Accel.dump(), packets (0 for --scalar)"""
+        b = self._run("tree", None)
+        n, nrefs, packets, _ = np.frombuffer(b, np.int32, 4)
+        box = np.frombuffer(b, np.float32, n * 6, 16).reshape(n, 6)
+        link = np.frombuffer(b, np.int32, n * 4, 16 + n * 24).reshape(n, 4)
+        refs = np.frombuffer(b, np.int32, nrefs, 16 + n * 40)
+        return box, link, refs, int(packets)
+
+    def intersect(self, rays) -> np.ndarray:
+        """-> REF_HIT_DTYPE [2, n]: row 0 intersect<false>, row 1 intersect<true> (back-face culling)"""
+        rays = self._rays(rays)
+        return np.frombuffer(self._run("intersect", rays.tobytes()), REF_HIT_DTYPE).reshape(2, len(rays))
+
+    def occluded(self, rays, max_t) -> np.ndarray:
+        rays = self._rays(rays)
+        max_t = np.ascontiguousarray(max_t, np.float32).reshape(-1)
+        assert len(max_t) == len(rays)
+        return np.frombuffer(self._run("occluded", rays.tobytes() + max_t.tobytes()), np.uint8)
+
+    def radiance(self, rays) -> np.ndarray:
+        rays = self._rays(rays)
+        return np.frombuffer(self._run("radiance", rays.tobytes()), np.float32).reshape(len(rays), 3)
+
+    def frame(self) -> np.ndarray:
+        w, h = self.size
+        return np.frombuffer(self._run("frame", None), np.float32).reshape(h, w, 3)

@@ -6,7 +6,7 @@
  * operation order so that IEEE add/mul/div/sqrt give bit-identical results to a
  * reference build with the same flag.
  *
- * File:line citations are relative to /root/reference/include/raytracer/.
+ * File:line citations are relative to the reference's include/raytracer/.
  */
 #define _GNU_SOURCE
 #include "rt_oracle.h"
@@ -586,6 +586,23 @@ void ora_intersect(const ora_accel *a, const float *rays, size_t n, int cull, or
         }
     }
     if (counters) for (int k = 0; k < ORA_C_COUNT; ++k) counters[k] += local[k];
+}
+
+/* The fields of hit<F> (render/hit.hpp:9-21) that ora_hit leaves out, [n][16]: position, face_normal, uvs[6], w, and three
+ * zeros; all zero on a miss. */
+void ora_intersect_rest(const ora_accel *a, const float *rays, size_t n, int cull, float *out) {
+    memset(out, 0, sizeof(float) * 16 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = &rays[i * 6];
+        const ray3 ray = mkray(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]));
+        hit_rec h;
+        if (!accel_intersect(a, &ray, cull, &h, NULL)) continue;
+        float *o = &out[i * 16];
+        o[0] = h.position.x; o[1] = h.position.y; o[2] = h.position.z;
+        o[3] = h.face_normal.x; o[4] = h.face_normal.y; o[5] = h.face_normal.z;
+        memcpy(&o[6], h.uvs, sizeof(float) * 6);
+        o[12] = h.w;
+    }
 }
 
 /* ------------------------------------------------------------------ RNG / trig shared with the HIP path */

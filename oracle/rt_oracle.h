@@ -6,19 +6,23 @@
  * and bench.py's cpu_baseline leg may load this library.  The shipped path
  * (simd-raytracer_amd/) never links, imports or calls anything in oracle/.
  *
- * PARITY PIN STATUS: PINNED by the reference's own committed renders.  The reference cannot
- * be built in this image without stand-in headers (libstdc++ >= 13, simdjson and stb from the
- * network) and ships no tests, but its outputs/*.png are its image.ppm files converted
- * losslessly (README.md:43-68); decoded into tests/golden/ref_outputs/ they are golden frames:
+ * PARITY PIN STATUS: PINNED, bit for bit, by a build of the reference's own headers: oracle/ref_probe.cpp (recipe
+ * oracle/ref.mk, stand-ins for the missing C++23 library pieces in oracle/ref_shim/) answers tree, intersect, occluded,
+ * radiance and frame queries; tests/test_ref_probe.py compares this restatement with the arrays it recorded
+ * (tests/golden/ref_probe/) and, where the build exists, with the probe itself over every loadable scene, generated scenes,
+ * tree shapes, eps values, packet widths 4 / 8 / 16 and the scalar kd-tree.  Not covered there: the scene loader, the JPEG
+ * decode (tests/golden/jpeg/), GI and multi-sample frames (the reference's RNG is a race).
+ * Also pinned by the reference's own committed renders: its outputs (PNG conversions of its image.ppm files, README.md:43-68),
+ * decoded into tests/golden/ref_outputs/, are golden frames:
  *   - refractive_dragon.png (hw11/scene8, 1920x1080): this restatement's write_ppm bytes are
  *     equal on all 6,220,800 bytes (tests/test_reference_outputs.py);
  *   - textures.png (hw12/scene4): equal on every byte, incl. the bitmap-textured quad;
  *   - gi_*.png (hw15/scene2, stochastic): statistically (block means vs the 512-spp render).
- * Also pinned by the reference-measured counters recorded in SURVEY.md §6/§8 (tree topology,
+ * And by the reference-measured counters recorded in SURVEY.md §6/§8 (tree topology,
  * intersect-call counts per frame, per-ray node/packet averages), tests/test_oracle_pins.py.
  *
  * Every function cites the reference file:line it follows (paths relative to
- * /root/reference/include/raytracer/).
+ * the reference's include/raytracer/).
  */
 #ifndef RT_ORACLE_H
 #define RT_ORACLE_H
@@ -127,6 +131,9 @@ void ora_scene_vertex_normals(const ora_scene *s, int mesh, float *out);
 /* Batched closest-hit: rays [n][6] = origin xyz, direction xyz. */
 void ora_intersect(const ora_accel *a, const float *rays, size_t n, int cull, ora_hit *out,
                    uint64_t *counters /* ORA_C_COUNT, accumulated; may be NULL */);
+
+/* The rest of hit<F> for the same rays: out [n][16] = position xyz, face_normal xyz, uvs[6], w, 0, 0, 0 (zeros on a miss). */
+void ora_intersect_rest(const ora_accel *a, const float *rays, size_t n, int cull, float *out);
 
 /* render_frame (render/render.hpp:18-108).  rgb [h][w][3] float. */
 int ora_render_frame(const ora_accel *a, const ora_render_params *p, float *rgb,

@@ -8,6 +8,8 @@
 namespace rtk {
 namespace dev {
 
+constexpr float kExitBelowMiss = 0x1.fffffcp+127f;    // the largest float below kFltMax, the t of a lane that has hit nothing
+
 // The reference's loop, per lane, around ONE wave-wide closest-hit query per round (the shape of k_shadow's inner loop,
 // stream.hip): a lane whose closest hit lies on a transmissive surface steps through it and asks again, the others have their
 // answer and idle until the wave's last lane has one.  The reference's loop has no bound; this one gives up on a lane after
@@ -37,7 +39,9 @@ __global__ __launch_bounds__(256) void k_occluded(OccludedArgs A) {
     while (wave_any(pending)) {
         // no transmissive material in the scene: the lane may stop at the first hit nearer than max_t (trace(), `exit_t`);
         // with them the closest hit is needed to know what was crossed
-        const float exit_t = A.has_refractive ? -1.0f : max_t;
+        // (a lane without a hit carries t = FLT_MAX: the exit is held below it, or max_t = inf or FLT_MAX would end the walk
+        // before it began and answer "clear" whatever lay ahead)
+        const float exit_t = A.has_refractive ? -1.0f : (max_t > kExitBelowMiss ? kExitBelowMiss : max_t);
         const Cand c = trace<MODE, false, LDS_NODES>(A.tree, lds_nodes, r, false, pending, st, sx, kAutoMinLanes, exit_t);
         if (pending) {
             queries += 1u;

@@ -328,7 +328,8 @@ typedef struct {
  * n > 0 with NULL rays / rgb, ids == NULL with n > 2^32 -> RTK_ERR_INVALID, and the accel stays usable.  Then n == 0 -> RTK_OK,
  * nothing touched, device or not.  Then no device -> RTK_ERR_NO_DEVICE.
  * The host variant is synchronous.  The device variant is stream-ordered and never synchronises the host; it allocates
- * (and then synchronises the device once) when a batch needs more queue space than any call before it on this accel.  It is
+ * (and then synchronises the device once) when a batch needs more queue space than any call before it on this accel -- more
+ * rays, or more lights than before (the queues hold one contribution per light: rtk_accel_set_lights).  It is
  * NOT stream-capturable: the pipeline forks onto streams of its own.
  * The queues belong to the accel and are shared with RTK_TRACE_STREAM frames.  A radiance batch (or such a frame) issued on
  * another stream than the previous user of the queues waits for that user ON THE DEVICE (an event) before it touches them:
@@ -467,6 +468,64 @@ int rtk_render_views(rtk_accel *accel, const rtk_render_params *p, const rtk_vie
                      float *rgb /* host */, rtk_counters *counters /* may be NULL: totals over the views */);
 int rtk_render_views_device(rtk_accel *accel, const rtk_render_params *p, const rtk_view *d_views /* DEVICE, 4-byte aligned */,
                             int32_t n_views, float *d_out /* device */, void *hip_stream);
+
+/* ---- lights, materials and background of a live accel ----
+ * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
+ * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the
+ * layout of the tables the kernels read, so a table is one copy.
+ * The contract of all three setters: after RTK_OK everything observable through the accel is, bit for bit and with the same
+ * `rays`, what a fresh rtk_accel_build gives for a scene that differs only in the replaced part (same params, same environment
+ * knobs): frames through every RTK_TRACE_* engine, sharded frames, rtk_render_views*, rtk_accel_radiance*, rtk_accel_occluded*
+ * (its answers depend on which materials are refractive) and the counters.  The tree, rtk_accel_tree_dump, rtk_accel_intersect*
+ * and rtk_camera_rays* depend on none of it and do not change.  The state survives rtk_accel_update_vertices / _update_geometry
+ * and rtk_accel_set_camera, in any order.  None of the calls is stream-capturable. */
+typedef struct { float position[3]; float intensity; } rtk_light;            /* scene/light.hpp; 16 bytes */
+typedef struct { int32_t kind, smooth; float albedo[3]; float ior; int32_t texture; int32_t reserved; } rtk_material;  /* 32 bytes */
+
+/* *n = the number of lights; with `out`, the first min(cap, *n) of them.  After rtk_accel_set_lights_device the table is fetched
+ * from the device, which synchronises it. */
+int rtk_accel_get_lights(const rtk_accel *accel, rtk_light *out /* may be NULL */, int32_t cap, int32_t *n);
+/* n is free: 0, fewer, or more than ever before.  The values are taken as they are, as rtk_scene_create takes them (a negative,
+ * zero, infinite or NaN intensity is the caller's business, as in the reference).
+ * On an accel that has never been on a device the host variant only stores: it needs no GPU and never returns
+ * RTK_ERR_NO_DEVICE.  Once the accel is on the device it SYNCHRONISES THE DEVICE AT ENTRY, as rtk_accel_update_vertices does
+ * (nothing issued earlier, on any stream, can still be reading the table), then writes the table; a table that n outgrows is
+ * replaced by one with head room, never by a smaller one, so a steady animation allocates nothing.
+ * The device variant (d_lights in DEVICE memory, 4-byte aligned) puts an accel that is not resident yet on the device first (no
+ * usable device -> RTK_ERR_NO_DEVICE), synchronises the device at entry, then copies on `hip_stream` and records the event later
+ * work on any stream waits for; after entry it does not block the host.
+ * The streaming workspace is sized by the light count: it grows at the next STREAM frame or radiance batch that needs it.
+ * Launch order: a call that leaves the COUNT as it is keeps the cost-feedback launch order (a light that moves leaves the
+ * silhouettes where they are); a changed count forgets it, because every block's cost scales with it.  RTK_TRACE_AUTO's engine
+ * verdict is kept by both.  Neither changes a result.
+ * Errors: NULL accel, n < 0, NULL lights with n > 0 -> RTK_ERR_INVALID; then (device variant) RTK_ERR_NO_DEVICE; RTK_ERR_HIP only
+ * from the runtime, and the accel is then as it was. */
+int rtk_accel_set_lights(rtk_accel *accel, const rtk_light *lights /* host */, int32_t n);
+int rtk_accel_set_lights_device(rtk_accel *accel, const rtk_light *d_lights /* DEVICE, 4-byte aligned */, int32_t n, void *hip_stream);
+
+int rtk_accel_get_materials(const rtk_accel *accel, rtk_material *out /* [n_materials] */);
+/* n must equal the scene's n_materials: the meshes' material indices are fixed (rtk_accel_update_geometry).  Validation is
+ * rtk_scene_create's: kind in [RTK_MAT_DIFFUSE, RTK_MAT_TEXTURE]; for RTK_MAT_TEXTURE 0 <= texture < n_textures, for every other
+ * kind texture is stored as -1; `reserved` is ignored and stored as 0.  The textures themselves are not touched: a scene built
+ * without textures cannot gain a texture material.
+ * On an accel that has never been on a device the call only stores and needs no GPU.  On a resident accel it synchronises the
+ * device at entry and writes the table.  What the launch paths derive from "some material is refractive" (early shadow exit, the
+ * unlit-shadow skip, the lean / general kernel choice, the streaming plan, the one-launch path of rtk_render_views) follows; the
+ * cost-feedback launch order and RTK_TRACE_AUTO's engine trial start over.
+ * When the SET of refractive materials changed on a resident RTK_TRAVERSAL_FAST accel (with RTK_FAST_OCCLUDERS), the opaque-only
+ * occlusion tree is re-made on the device from the active tree (csrc/occluders.hip): the host blocks once more to read one count
+ * per leaf (and until the few hundred nodes it makes from them have left its memory), the copy is built into spare buffers and
+ * swapped in at the end, and later work on any stream waits for the event recorded behind it.  The per-triangle opaque flags that later rtk_accel_update_vertices calls read are rewritten too.
+ * Errors, in this order: NULL accel or materials; n != n_materials; a bad kind or texture index -> RTK_ERR_INVALID.  Then
+ * RTK_ERR_HIP only from the runtime.  Never RTK_ERR_NO_DEVICE on an accel that is not resident.  A refused call leaves the accel
+ * exactly as it was. */
+int rtk_accel_set_materials(rtk_accel *accel, const rtk_material *materials /* host [n_materials] */, int32_t n);
+
+/* The background is launch-argument data, like the camera: the calls touch no device memory, synchronise nothing, never return
+ * RTK_ERR_NO_DEVICE and take the values as they are (a -0.0 and a denormal round-trip by their bits).  Frames already enqueued
+ * keep the background they were launched with.  NULL accel or rgb -> RTK_ERR_INVALID. */
+int rtk_accel_get_background(const rtk_accel *accel, float rgb[3]);
+int rtk_accel_set_background(rtk_accel *accel, const float rgb[3]);
 
 /* ---- image out: replaces write_ppm (io/image/ppm.hpp:7-25) ---- */
 /* The quantisation of write_ppm on the device: out[i] = uint8(255.999 * clamp(rgb[i], 0, 1)) (ppm.hpp:17-19, the product in

@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
+    "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
+    "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_frame_to_rgb8_device", "rtk_format_ppm_rgb8", "rtk_write_ppm", "rtk_format_ppm",
 ]
 
@@ -131,6 +133,10 @@ class Counters(C.Structure):
 
 
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,))])
+LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("intensity", "<f4")])                     # rtk.h rtk_light
+MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("smooth", "<i4"), ("albedo", "<f4", (3,)), ("ior", "<f4"), ("texture", "<i4"),
+                           ("reserved", "<i4")])                                             # rtk.h rtk_material
+assert LIGHT_DTYPE.itemsize == 16 and MATERIAL_DTYPE.itemsize == 32
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), ("mesh", "<u4"), ("normal", "<f4", (3,))])
 assert RAY_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
 
@@ -176,6 +182,13 @@ _L.rtk_accel_get_camera.argtypes = [_vp, _vp]
 _L.rtk_accel_set_camera.argtypes = [_vp, _vp]
 _L.rtk_render_views.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, C.POINTER(Counters)]
 _L.rtk_render_views_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, _vp]
+_L.rtk_accel_get_lights.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+_L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
+_L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
+_L.rtk_accel_get_materials.argtypes = [_vp, _vp]
+_L.rtk_accel_set_materials.argtypes = [_vp, _vp, C.c_int32]
+_L.rtk_accel_get_background.argtypes = [_vp, _vp]
+_L.rtk_accel_set_background.argtypes = [_vp, _vp]
 _L.rtk_frame_to_rgb8_device.argtypes = [_vp, C.c_size_t, _vp, _vp]
 _L.rtk_format_ppm_rgb8.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
 _L.rtk_write_ppm.argtypes = [_vp, C.c_int32, C.c_int32, C.c_char_p]
@@ -587,6 +600,62 @@ class KdTreeSimdAccel:
         """d_views_ptr: device float32 [n_views, 12]; d_out_ptr: device float32 [n_views, h, w, 3]; stream-ordered (rtk.h)."""
         p = cfg.to_c()
         _check(_L.rtk_render_views_device(self._h, C.byref(p), d_views_ptr or None, n_views, d_out_ptr or None, stream))
+
+    # ---- lights, materials and background of a live accel (rtk.h rtk_light, rtk_material)
+    def lights(self):
+        """(positions [n, 3], intensities [n]) float32: the lights later frames are lit by."""
+        n = C.c_int32(0)
+        _check(_L.rtk_accel_get_lights(self._h, None, 0, C.byref(n)))
+        tab = np.zeros(n.value, LIGHT_DTYPE)
+        _check(_L.rtk_accel_get_lights(self._h, tab.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return tab["position"].copy(), tab["intensity"].copy()
+
+    def set_lights(self, positions, intensities) -> None:
+        """positions [n, 3], intensities [n]; n is free.  Later frames are those of a fresh accel of the scene with these lights.
+        Needs no GPU on an accel that has not rendered yet."""
+        pos, inten = np.asarray(positions, np.float32), np.asarray(intensities, np.float32)
+        if inten.ndim != 1 or pos.shape != (inten.shape[0], 3):
+            raise ValueError("positions must have shape (n, 3) and intensities (n,)")
+        tab = np.zeros(inten.shape[0], LIGHT_DTYPE)
+        tab["position"], tab["intensity"] = pos, inten
+        _check(_L.rtk_accel_set_lights(self._h, tab.ctypes.data if tab.size else None, tab.shape[0]))
+
+    def set_lights_device(self, d_lights_ptr: int, n: int, stream: int = 0) -> None:
+        """d_lights_ptr: device float32 [n, 4] (x, y, z, intensity); copied on `stream`, later work on any stream sees it (rtk.h)."""
+        _check(_L.rtk_accel_set_lights_device(self._h, d_lights_ptr or None, n, stream))
+
+    def materials(self) -> dict:
+        """kind [m] int32, albedo [m, 3], ior [m] float32, smooth [m], texture [m] int32 (-1 unless kind is MAT_TEXTURE)."""
+        tab = np.zeros(self.scene.info.n_materials, MATERIAL_DTYPE)
+        _check(_L.rtk_accel_get_materials(self._h, tab.ctypes.data))
+        return {k: tab[k].copy() for k in ("kind", "albedo", "ior", "smooth", "texture")}
+
+    def set_materials(self, kind, albedo, ior, smooth, texture=None) -> None:
+        """One row per material of the scene (their number is fixed).  What the values hold is judged by the library (RtkError)."""
+        m = self.scene.info.n_materials
+        kind, smooth = np.asarray(kind), np.asarray(smooth)
+        albedo, ior = np.asarray(albedo, np.float32), np.asarray(ior, np.float32)
+        texture = np.full(m, -1, np.int32) if texture is None else np.asarray(texture)
+        for a in (kind, smooth, texture):
+            if a.shape != (m,) or a.dtype.kind not in "iub":
+                raise ValueError(f"kind, smooth and texture must be {m} integers, one per material")
+        if albedo.shape != (m, 3) or ior.shape != (m,):
+            raise ValueError(f"albedo must have shape ({m}, 3) and ior ({m},)")
+        tab = np.zeros(m, MATERIAL_DTYPE)
+        tab["kind"], tab["smooth"], tab["albedo"], tab["ior"], tab["texture"] = kind, smooth, albedo, ior, texture
+        _check(_L.rtk_accel_set_materials(self._h, tab.ctypes.data, m))
+
+    def background(self) -> np.ndarray:
+        rgb = np.zeros(3, np.float32)
+        _check(_L.rtk_accel_get_background(self._h, rgb.ctypes.data))
+        return rgb
+
+    def set_background(self, rgb) -> None:
+        rgb = np.asarray(rgb, np.float32)
+        if rgb.shape != (3,):
+            raise ValueError("the background has 3 floats")
+        rgb = np.ascontiguousarray(rgb)
+        _check(_L.rtk_accel_set_background(self._h, rgb.ctypes.data))
 
     def last_critical_path_ms(self) -> float:
         """Longest 8x8 pixel block of the most recent megakernel frame (ms): the frame's critical path."""

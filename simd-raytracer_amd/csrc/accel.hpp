@@ -250,6 +250,13 @@ struct rtk_accel {
     size_t up_stage_cap = 0;
     hipEvent_t geom_ready = nullptr;           // recorded behind an update's last kernel: later work on any stream waits for it
     bool geom_pending = false;
+    // ---- st_*: rtk_accel_set_lights / _set_materials (api_state.hip; the regather: api_update.hip, occluders.hip)
+    size_t lights_cap = 0;                     // rows d_lights has room for; grows with head room, never shrinks
+    bool lights_on_device = false;             // rtk_accel_set_lights_device: scene.lights has the COUNT, the values are in d_lights
+    rtk::DevMaterial *st_materials = nullptr;  // the spare material table: written, read by the regather, then swapped with d_materials
+    rtk::dev::OcclLeaf *st_leaves = nullptr;   // one row per leaf of the active tree
+    uint32_t *st_counts = nullptr;             // opaque references per leaf
+    size_t st_leaves_cap = 0, st_counts_cap = 0;   // bytes
     // ---- the last frame (rtk_render_last_counters, rtk_render_last_critical_path)
     hipStream_t last_stream = nullptr;
     uint64_t last_primary = 0;
@@ -305,6 +312,14 @@ struct FrameGeom {
 // (which was built on that call's stream) unless that has completed already.
 int ensure_device(rtk_accel *a, hipStream_t s = nullptr);
 dev::TreeView tree_view(const rtk_accel *a);
+// api_update.hip
+int grow_dev(void **p, size_t *cap, size_t need);
+int ensure_update_common(rtk_accel *a);
+// What follows from a new material table on a RESIDENT accel whose device is idle: the per-triangle opaque flags the updates read,
+// and -- when the set of refractive materials changed -- the opaque-only occlusion tree of a RTK_TRAVERSAL_FAST accel, re-made
+// from the active tree into the spare buffers and swapped in.  `d_materials`: the new table on the device; a->scene.materials
+// and a->has_refractive are still the old ones and stay so on failure.
+int remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &materials, const DevMaterial *d_materials, hipStream_t s);
 // api_frame.hip
 int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g);
 int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes);

@@ -66,6 +66,7 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
     }
     RTK_TRY(upload(a->scene.materials, &a->d_materials));
     RTK_TRY(upload(a->scene.lights, &a->d_lights));
+    a->lights_cap = a->scene.lights.empty() ? 1 : a->scene.lights.size();
     if (!a->scene.textures.empty()) {
         RTK_TRY(upload(a->scene.textures, &a->d_textures));
         RTK_TRY(upload(a->tree.dev_tri_uv, &a->d_tri_uv));
@@ -335,6 +336,7 @@ void rtk_accel_destroy(rtk_accel *a) {
         (void)hipFree(a->d_textures); (void)hipFree(a->d_tri_uv); (void)hipFree(a->d_tex_pixels); (void)hipFree(a->d_leaves_fast);
         (void)hipFree(a->d_occl_nodes); (void)hipFree(a->d_occl_leaves); (void)hipFree(a->d_occl_tris); (void)hipFree(a->d_occl_ids);
         (void)hipFree(a->d_leaf_refs);
+        (void)hipFree(a->st_materials); (void)hipFree(a->st_leaves); (void)hipFree(a->st_counts);
         for (void *p : a->spare) (void)hipFree(p);
         (void)hipFree(a->up_index); (void)hipFree(a->up_inc_off); (void)hipFree(a->up_inc); (void)hipFree(a->up_opaque); (void)hipFree(a->up_verts);
         (void)hipFree(a->up_tris); (void)hipFree(a->up_tbox); (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);

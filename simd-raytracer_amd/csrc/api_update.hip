@@ -9,7 +9,7 @@
 
 using namespace rtk;
 
-namespace {
+namespace rtk {
 
 // Grows a device buffer to at least `need` bytes (with head room; the old contents are not kept).  Freeing synchronises the
 // device: this is the "second block" of an update, taken only when a buffer has to grow.
@@ -24,6 +24,10 @@ int grow_dev(void **p, size_t *cap, size_t need) {
     return RTK_OK;
 }
 
+}  // namespace rtk
+
+namespace {
+
 int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
     if (*p != nullptr && need <= *cap) return RTK_OK;
     if (*p) (void)hipHostFree(*p);
@@ -34,8 +38,10 @@ int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
     return RTK_OK;
 }
 
+}  // namespace
+
 // What every update needs once: the event later work waits for, and how large the buffers are that ensure_device uploaded.
-int ensure_update_common(rtk_accel *a) {
+int rtk::ensure_update_common(rtk_accel *a) {
     if (a->geom_ready) return RTK_OK;
     RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
     const HostTree &T = a->tree;
@@ -50,6 +56,8 @@ int ensure_update_common(rtk_accel *a) {
     a->topo_active_cap[T_TRI_UV] = a->d_tri_uv ? bytes(T.dev_tri_uv.size(), sizeof(DevTriUv)) : 0;
     return RTK_OK;
 }
+
+namespace {
 
 // What an update of the vertices needs of the topology: vertex ids per triangle over the concatenated vertex array, the
 // vertex -> (triangle, corner) incidence lists and which triangles are opaque.  Made here, on the host, from the scene the accel
@@ -373,6 +381,97 @@ int check_counts(const rtk_accel *a, const int32_t *mesh_ntris, uint32_t &total)
 }
 
 }  // namespace
+
+int rtk::remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &materials, const DevMaterial *d_materials, hipStream_t s) {
+    auto refractive = [](const DevMaterial &m) { return m.kind == RTK_MAT_REFRACTIVE; };
+    bool any = false, set_changed = false;
+    for (size_t i = 0; i < materials.size(); ++i) {
+        any = any || refractive(materials[i]);
+        if (refractive(materials[i]) != refractive(a->scene.materials[i])) set_changed = true;
+    }
+    const bool tree = a->fast_traversal && a->knobs.fast_occluders && set_changed;
+    if (!tree && !(a->up_opaque && set_changed)) return RTK_OK;
+    RTK_TRY(ensure_update_common(a));
+    dev::OcclArgs O{};
+    O.materials = d_materials; O.n_materials = uint32_t(materials.size());
+    O.shade = a->d_shade; O.n_tris = uint32_t(a->scene.n_triangles);
+    if (tree && any) {
+        // the leaves of the active tree, in dev_nodes' order: as ensure_device and update_impl walk them
+        const std::vector<DevNode> &nodes = a->tree.dev_nodes;
+        std::vector<dev::OcclLeaf> leaves;
+        for (const DevNode &n : nodes) if (n.b != DEV_INNER) leaves.push_back(dev::OcclLeaf{n.a, n.b, 0u, 0u});
+        const size_t n_refs = a->refs_on_device ? size_t(a->n_leaf_refs_dev) : a->tree.dev_tris.size();
+        for (const dev::OcclLeaf &l : leaves)
+            if (size_t(l.first) + l.count > n_refs) return fail(RTK_ERR_INVALID, "internal: a leaf runs past the accel's references");
+        const size_t nl = leaves.size();
+        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->st_leaves), &a->st_leaves_cap, nl * sizeof(dev::OcclLeaf)));
+        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->st_counts), &a->st_counts_cap, nl * sizeof(uint32_t)));
+        O.leaves = a->st_leaves; O.n_leaves = uint32_t(nl); O.n_refs = uint32_t(n_refs);
+        O.tris = a->d_tris; O.tri_ids = a->d_tri_ids; O.counts = a->st_counts;
+        std::vector<uint32_t> counts(nl, 0u);
+        if (nl > 0) {
+            RTK_HIP(hipMemcpyAsync(a->st_leaves, leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
+            RTK_HIP_AS(launch_occl_count(O, s), "launch k_occl_count");
+            // the one place the call blocks after entry: one count per leaf
+            RTK_HIP(hipMemcpyAsync(counts.data(), a->st_counts, nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            RTK_HIP(hipStreamSynchronize(s));
+        }
+        // as ensure_device / update_impl: the same nodes, a leaf's a / b its run in the opaque copy, empty leaves kept as nodes
+        // and dropped from the leaf list
+        std::vector<DevNode> onodes = nodes, oleaves;
+        size_t n_opaque = 0, li = 0;
+        for (DevNode &n : onodes) {
+            if (n.b == DEV_INNER) continue;
+            const uint32_t c = counts[li];
+            if (c > leaves[li].count) return fail(RTK_ERR_INVALID, "internal: a leaf's opaque count exceeds the leaf");
+            leaves[li++].dst = uint32_t(n_opaque);
+            n.a = uint32_t(n_opaque); n.b = c;
+            n_opaque += c;
+            if (n.b != 0u) oleaves.push_back(n);
+        }
+        if (oleaves.empty()) { DevNode n = onodes.empty() ? DevNode{} : onodes[0]; n.a = 0u; n.b = 0u; oleaves.push_back(n); }
+        void **sp = a->spare;
+        size_t *sc = a->spare_cap;
+        RTK_TRY(grow_dev(&sp[G_ONODES], &sc[G_ONODES], onodes.size() * sizeof(DevNode)));
+        RTK_TRY(grow_dev(&sp[G_OLEAVES], &sc[G_OLEAVES], oleaves.size() * sizeof(DevNode)));
+        RTK_TRY(grow_dev(&sp[G_OTRIS], &sc[G_OTRIS], std::max<size_t>(1, n_opaque) * sizeof(DevTri)));
+        RTK_TRY(grow_dev(&sp[G_OIDS], &sc[G_OIDS], std::max<size_t>(1, n_opaque) * sizeof(uint32_t)));
+        // (pageable sources: these copies return when the data has left the host vectors)
+        if (!onodes.empty()) RTK_HIP(hipMemcpyAsync(sp[G_ONODES], onodes.data(), onodes.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
+        RTK_HIP(hipMemcpyAsync(sp[G_OLEAVES], oleaves.data(), oleaves.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
+        if (nl > 0) RTK_HIP(hipMemcpyAsync(a->st_leaves, leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
+        O.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); O.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]); O.cap = uint32_t(n_opaque);
+        if (n_opaque > 0) RTK_HIP_AS(launch_occl_gather(O, s), "launch k_occl_gather");
+        else {                                                              // nothing opaque: keep the pointers valid, as ensure_device does
+            if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp[G_OTRIS], a->d_tris, sizeof(DevTri), hipMemcpyDeviceToDevice, s));
+            else RTK_HIP(hipMemsetAsync(sp[G_OTRIS], 0, sizeof(DevTri), s));
+            RTK_HIP(hipMemsetAsync(sp[G_OIDS], 0, sizeof(uint32_t), s));
+        }
+        if (a->up_opaque) { O.opaque = a->up_opaque; RTK_HIP_AS(launch_occl_flags(O, s), "launch k_occl_flags"); }
+        RTK_HIP(hipStreamSynchronize(s));                                   // (the host vectors above go out of scope)
+        RTK_HIP(hipEventRecord(a->geom_ready, s));
+        // ---- nothing below fails
+        void **act[4] = {reinterpret_cast<void **>(&a->d_occl_nodes), reinterpret_cast<void **>(&a->d_occl_leaves),
+                         reinterpret_cast<void **>(&a->d_occl_tris), reinterpret_cast<void **>(&a->d_occl_ids)};
+        for (int i = G_ONODES; i <= G_OIDS; ++i) {
+            std::swap(*act[i - G_ONODES], a->spare[i]);
+            std::swap(a->active_cap[i], a->spare_cap[i]);
+        }
+        a->occl_n_leaves = uint32_t(oleaves.size());
+        a->occl_on = true;
+        a->geom_pending = true;
+        return RTK_OK;
+    }
+    // the flags alone; a FAST accel that lost its last refractive material keeps the buffers for the next time
+    if (a->up_opaque) {
+        O.opaque = a->up_opaque;
+        RTK_HIP_AS(launch_occl_flags(O, s), "launch k_occl_flags");
+        RTK_HIP(hipEventRecord(a->geom_ready, s));
+        a->geom_pending = true;
+    }
+    if (tree) { a->occl_on = false; a->occl_n_leaves = 0u; }
+    return RTK_OK;
+}
 
 int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void *hip_stream) {
     if (!a || !d_vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");

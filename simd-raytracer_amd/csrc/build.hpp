@@ -82,7 +82,36 @@ struct GatherArgs {
     uint32_t *occl_ids;
 };
 
+// rtk_accel_set_materials (occluders.hip): the opaque-only occlusion tree again, from the ACTIVE tree and a new material table.
+struct OcclLeaf {
+    uint32_t first, count;          // the leaf's run in the active tris / tri_ids
+    uint32_t dst;                   // its first slot in the opaque-only copy (the gather's; the count kernel does not read it)
+    uint32_t pad;
+};
+static_assert(sizeof(OcclLeaf) == 16, "OcclLeaf must be 16 bytes");
+
+struct OcclArgs {
+    const DevMaterial *materials;
+    uint32_t n_materials;
+    const DevShade *shade;          // the active per-triangle records: `material`
+    uint32_t n_tris;
+    const OcclLeaf *leaves;
+    uint32_t n_leaves;
+    uint32_t n_refs;                // length of tris / tri_ids
+    const DevTri *tris;             // the active leaf references
+    const uint32_t *tri_ids;
+    uint32_t *counts;               // out of the count: [n_leaves] opaque references
+    DevTri *occl_tris;              // out of the gather; `cap` slots
+    uint32_t *occl_ids;
+    uint32_t cap;
+    uint8_t *opaque;                // out of the flags: [n_tris]
+};
+
 }  // namespace dev
+
+hipError_t launch_occl_flags(const dev::OcclArgs &O, hipStream_t s);
+hipError_t launch_occl_count(const dev::OcclArgs &O, hipStream_t s);
+hipError_t launch_occl_gather(const dev::OcclArgs &O, hipStream_t s);
 
 // header memset + (with `topo`: the topology tables, topology.hip) + triangles + vertex normals + tree
 hipError_t launch_build(const dev::BuildArgs &B, const dev::TopoArgs *topo, hipStream_t s);

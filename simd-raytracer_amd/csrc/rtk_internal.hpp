@@ -2,6 +2,7 @@
 // Reference citations are relative to /root/reference/include/raytracer/.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -76,6 +77,15 @@ struct DevLight {     // scene/light.hpp
     float pos[3];
     float intensity;
 };
+
+// rtk_light / rtk_material (rtk.h) ARE these tables' rows: rtk_accel_set_lights / _set_materials copy, they do not convert
+static_assert(sizeof(DevLight) == sizeof(rtk_light) && sizeof(DevLight) == 16, "rtk_light must be a DevLight");
+static_assert(offsetof(DevLight, pos) == offsetof(rtk_light, position) && offsetof(DevLight, intensity) == offsetof(rtk_light, intensity), "rtk_light must be a DevLight");
+static_assert(sizeof(DevMaterial) == sizeof(rtk_material), "rtk_material must be a DevMaterial");
+static_assert(offsetof(DevMaterial, kind) == offsetof(rtk_material, kind) && offsetof(DevMaterial, smooth) == offsetof(rtk_material, smooth) &&
+              offsetof(DevMaterial, albedo) == offsetof(rtk_material, albedo) && offsetof(DevMaterial, ior) == offsetof(rtk_material, ior) &&
+              offsetof(DevMaterial, texture) == offsetof(rtk_material, texture) && offsetof(DevMaterial, pad) == offsetof(rtk_material, reserved),
+              "rtk_material must be a DevMaterial");
 
 // ---------------------------------------------------------------- host model
 

@@ -147,6 +147,7 @@ struct hip_accel {
         rtk_scene_destroy(rs);                       // the accel keeps its own copy (as kd_tree_simd.hpp:106-107 does)
         check(rc);
         accel_ = std::shared_ptr<rtk_accel>(ra, rtk_accel_destroy);
+        texture_names_ = std::move(texture_names);
     }
 
     // accel.template intersect<cull>(ray) — render/accel/accel.hpp:9-10
@@ -282,6 +283,62 @@ struct hip_accel {
         return c;
     }
 
+    // Lights, materials and background of later frames (rtk_accel_set_lights / _set_materials / _set_background): what constructing
+    // a new accel from the scene with these would render.  Like set_camera they move the ACCEL ONLY (the scene is const); the
+    // *_now() members read the accel's back.  The number of lights is free; materials are one per material of the scene, and a
+    // texture_material names one of the scene's textures.
+    void set_lights(std::span<const light<F>> lights) {
+        std::vector<rtk_light> in(lights.size());
+        for (std::size_t i = 0; i < lights.size(); ++i)
+            in[i] = rtk_light{{lights[i].position.x, lights[i].position.y, lights[i].position.z}, lights[i].intensity};
+        check(rtk_accel_set_lights(accel_.get(), in.empty() ? nullptr : in.data(), static_cast<int32_t>(in.size())));
+    }
+    [[nodiscard]] std::vector<light<F>> lights_now() const {
+        int32_t n = 0;
+        check(rtk_accel_get_lights(accel_.get(), nullptr, 0, &n));
+        std::vector<rtk_light> in(static_cast<std::size_t>(n) + 1);
+        check(rtk_accel_get_lights(accel_.get(), in.data(), n, &n));
+        std::vector<light<F>> out(static_cast<std::size_t>(n));
+        for (std::size_t i = 0; i < out.size(); ++i)
+            out[i] = light<F>{vec3<F>{in[i].position[0], in[i].position[1], in[i].position[2]}, in[i].intensity};
+        return out;
+    }
+
+    void set_materials(std::span<const material_variant<F>> materials) {
+        if (materials.size() != scene_ptr->materials.size()) throw std::invalid_argument("hip_accel::set_materials: one material per material of the scene");
+        std::vector<rtk_material> in(materials.size() + 1);
+        for (std::size_t i = 0; i < materials.size(); ++i) in[i] = to_material(materials[i]);
+        check(rtk_accel_set_materials(accel_.get(), in.data(), static_cast<int32_t>(materials.size())));
+    }
+    [[nodiscard]] std::vector<material_variant<F>> materials_now() const {
+        std::vector<rtk_material> in(scene_ptr->materials.size() + 1);
+        check(rtk_accel_get_materials(accel_.get(), in.data()));
+        std::vector<material_variant<F>> out;
+        for (std::size_t i = 0; i + 1 < in.size(); ++i) {
+            const rtk_material &m = in[i];
+            const color<F> albedo{m.albedo[0], m.albedo[1], m.albedo[2]};
+            const bool smooth = m.smooth != 0;
+            switch (m.kind) {
+                case RTK_MAT_REFLECTIVE: out.emplace_back(reflective_material<F>{albedo, smooth}); break;
+                case RTK_MAT_REFRACTIVE: out.emplace_back(refractive_material<F>{m.ior, smooth}); break;
+                case RTK_MAT_CONSTANT: out.emplace_back(constant_material<F>{albedo, smooth}); break;
+                case RTK_MAT_TEXTURE: out.emplace_back(texture_material<F>{texture_names_.at(static_cast<std::size_t>(m.texture)), smooth}); break;
+                default: out.emplace_back(diffuse_material<F>{albedo, smooth}); break;
+            }
+        }
+        return out;
+    }
+
+    void set_background(const color<F> &c) {
+        const float rgb[3] = {c.red, c.green, c.blue};
+        check(rtk_accel_set_background(accel_.get(), rgb));
+    }
+    [[nodiscard]] color<F> background_now() const {
+        float rgb[3] = {0.f, 0.f, 0.f};
+        check(rtk_accel_get_background(accel_.get(), rgb));
+        return color<F>{rgb[0], rgb[1], rgb[2]};
+    }
+
     // One whole frame per camera from one call (rtk_render_views): image v is what set_camera(views[v]) + render_frame(params)
     // gives, and the accel's own camera stays.  counters: totals over the views.
     [[nodiscard]] std::vector<std::vector<std::vector<color<F>>>> render_views(std::span<const camera<F>> views, const rtk_render_params &params,
@@ -349,6 +406,28 @@ private:
     std::shared_ptr<rtk_accel> accel_;
     std::vector<std::size_t> first_triangle_;     // global triangle index of each mesh's first triangle
     std::size_t n_triangles_ = 0;
+    std::vector<std::string> texture_names_;      // the C-ABI's texture indices, in the order the constructor met scene.textures
+
+    // one row of the material table, as the constructor flattens scene.materials
+    [[nodiscard]] rtk_material to_material(const material_variant<F> &mv) const {
+        rtk_material out{};
+        out.kind = RTK_MAT_DIFFUSE; out.ior = 1.f; out.texture = -1;
+        std::visit([&](const auto &m) {
+            using M = std::decay_t<decltype(m)>;
+            out.smooth = m.smooth_shading ? 1 : 0;
+            if constexpr (std::is_same_v<M, diffuse_material<F>>) out.kind = RTK_MAT_DIFFUSE;
+            else if constexpr (std::is_same_v<M, reflective_material<F>>) out.kind = RTK_MAT_REFLECTIVE;
+            else if constexpr (std::is_same_v<M, refractive_material<F>>) { out.kind = RTK_MAT_REFRACTIVE; out.ior = m.ior; }
+            else if constexpr (std::is_same_v<M, constant_material<F>>) out.kind = RTK_MAT_CONSTANT;
+            else {
+                out.kind = RTK_MAT_TEXTURE;
+                for (std::size_t ti = 0; ti < texture_names_.size(); ++ti) if (texture_names_[ti] == m.texture) out.texture = static_cast<int32_t>(ti);
+                if (out.texture < 0) throw std::invalid_argument("hip_accel: material uses unknown texture '" + m.texture + "'");
+            }
+            if constexpr (requires { m.albedo; }) { out.albedo[0] = m.albedo.red; out.albedo[1] = m.albedo.green; out.albedo[2] = m.albedo.blue; }
+        }, mv);
+        return out;
+    }
 
     static rtk_view to_view(const camera<F> &c) noexcept {
         rtk_view v{};

@@ -469,6 +469,53 @@ int rtk_render_views(rtk_accel *accel, const rtk_render_params *p, const rtk_vie
 int rtk_render_views_device(rtk_accel *accel, const rtk_render_params *p, const rtk_view *d_views /* DEVICE, 4-byte aligned */,
                             int32_t n_views, float *d_out /* device */, void *hip_stream);
 
+/* ---- rectangles of a frame in one call ----
+ * render_tile {x0, y0, x1, y1} (render/tile/tile.hpp), the unit of work tile_worker consumes (render/render.hpp:30-77): pixels
+ * [x0, x1) x [y0, y1) of the frame *p describes.  The reference's single / region / bucket schedulers differ only in which
+ * rectangles they hand out; here the caller hands them out.
+ * Contract: every pixel inside a rectangle ends up, bit for bit, as rtk_render_frame with *p leaves it: the accel's camera, the
+ * frame's RNG keys (pixel index py * width + px, sample, seed), the same sample_begin / sample_count semantics (a pass with
+ * sample_begin > 0 continues the running sums in the output; the pass that ends at spp divides).  On an RTK_TRAVERSAL_FAST accel
+ * "the same" means equal to that accel's own frame (that order is chosen per wave of 64 pixels: a rectangle made of whole 8x8
+ * blocks of the frame's grid runs the frame's own waves; for any other rectangle the winner of an EXACT tie of t may differ from
+ * the frame's as it may between two engines, the tie caveat of RTK_TRAVERSAL_FAST).  counters.primary = sum of the areas x samples of the pass; counters.rays =
+ * the reference's intersect() invocations for exactly those pixels, so the `rays` of rectangles that tile the frame add up to
+ * the frame's.  rtk_render_last_counters / rtk_render_last_critical_path report the call.  The accel's camera, the cost tables
+ * of plain frames and RTK_TRACE_AUTO's engine verdict are left alone.
+ * Layouts:
+ *   RTK_REGIONS_IN_FRAME  the output is the whole frame [h][w][3].  Only pixels inside a rectangle are read (sample_begin > 0) or
+ *                         written; every other float keeps its bits.  The rectangles must be pairwise disjoint.
+ *   RTK_REGIONS_PACKED    rectangle r is a dense [y1-y0][x1-x0][3] array at float offset 3 * (sum of the areas of the rectangles
+ *                         before it).  Overlaps are legal: each rectangle gets its own copy.  The running sums of a progressive
+ *                         render live in this packed buffer.
+ * `rects` is in HOST memory in both variants (the host sizes the launch from it), at most 65,536 of them; empty rectangles
+ * (x0 == x1 or y0 == y1) are legal and cost nothing.
+ * What runs: under RTK_TRACE_GROUP4 / 8 / 16, and RTK_TRACE_AUTO on scenes whose ray trees do not fork, the 8x8 pixel blocks of ALL
+ * rectangles -- anchored at each rectangle's own corner -- are the units of ONE megakernel launch with one cost order and one
+ * packed list of cheap blocks.  A call of more than 131,072 units (RTK_VIEWS_LAUNCH_UNITS) is cut into launches of whole
+ * rectangles.  The measured launch order is reused only by a call whose rectangle list, layout and parameters equal the previous
+ * call's; any other list starts in the natural order.  RTK_TRACE_STREAM, and RTK_TRACE_AUTO on forking scenes (refraction,
+ * diffuse GI), run sample by sample: the rectangles' camera rays and frame pixel indices, the streaming pipeline of
+ * rtk_accel_radiance over them, and a kernel that adds the colours into the output in sample order (bit-equal: radiance
+ * returns +0 + c, and a running sum that starts at +0 never holds -0).  Its workspace belongs to the accel, grows with head
+ * room and is walked in chunks of 2^20 pixels.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL accel or p, then what rtk_render_frame refuses for *p; RTK_TRACE_LANE /
+ * _WAVE / _TWOPASS, collect_stats != 0, world_size > 1 (the caller deals rectangles to ranks), n_rects < 0 or > 65,536, another
+ * layout; NULL rects or output with n_rects > 0; a rectangle with x0 < 0, y0 < 0, x1 < x0, y1 < y0, x1 > width or y1 > height;
+ * overlapping rectangles under RTK_REGIONS_IN_FRAME.  Then n_rects == 0 or zero total area -> RTK_OK with nothing touched, device
+ * or not.  Then RTK_ERR_NO_DEVICE.  A refused call leaves the accel usable and unchanged.
+ * The host variant moves what the layout needs: the packed buffer, or the whole frame up and down (so the caller's pixels outside
+ * the rectangles come back as they went).  The device variant is stream-ordered; it copies the small rectangle table from a
+ * buffer of its own (it waits for the previous call's table to be consumed first) and may allocate, and then synchronise once,
+ * when a call needs larger tables than any before.  NOT stream-capturable. */
+typedef struct { int32_t x0, y0, x1, y1; } rtk_rect;
+enum { RTK_REGIONS_IN_FRAME = 0, RTK_REGIONS_PACKED = 1 };
+
+int rtk_render_regions(rtk_accel *accel, const rtk_render_params *p, const rtk_rect *rects /* host */, int32_t n_rects,
+                       int layout, float *rgb /* host */, rtk_counters *counters /* may be NULL: totals */);
+int rtk_render_regions_device(rtk_accel *accel, const rtk_render_params *p, const rtk_rect *rects /* HOST */, int32_t n_rects,
+                              int layout, float *d_out /* device */, void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

@@ -32,6 +32,8 @@ TRAVERSAL_REFERENCE, TRAVERSAL_FAST = 0, 1     # rtk.h RTK_TRAVERSAL_*: leaf ord
 TRACE_REPACK = 8        # batched intersect only: rays sorted by origin / direction cell before the trace (csrc/repack.hip)
 OCC_CLEAR, OCC_OCCLUDED, OCC_STEP_LIMIT = 0, 1, 2     # rtk.h RTK_OCC_*: answers of the batched occlusion query
 OCCLUDED_MAX_STEPS = 1024                             # rtk.h RTK_OCCLUDED_MAX_STEPS
+REGIONS_IN_FRAME, REGIONS_PACKED = 0, 1               # rtk.h RTK_REGIONS_*: where render_regions puts a rectangle's pixels
+MAX_REGIONS = 65536                                   # rectangles of one render_regions call at most
 
 # every symbol include/rtk.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -49,6 +51,7 @@ ABI_SYMBOLS = [
     "rtk_render_last_critical_path",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
+    "rtk_render_regions", "rtk_render_regions_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_frame_to_rgb8_device", "rtk_format_ppm_rgb8", "rtk_write_ppm", "rtk_format_ppm",
@@ -182,6 +185,8 @@ _L.rtk_accel_get_camera.argtypes = [_vp, _vp]
 _L.rtk_accel_set_camera.argtypes = [_vp, _vp]
 _L.rtk_render_views.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, C.POINTER(Counters)]
 _L.rtk_render_views_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, _vp]
+_L.rtk_render_regions.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, C.POINTER(Counters)]
+_L.rtk_render_regions_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, _vp]
 _L.rtk_accel_get_lights.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
@@ -356,6 +361,40 @@ class RenderConfig:
                             self.fov_degrees, np.float32(self.shadow_bias), np.float32(self.reflection_bias),
                             np.float32(self.refraction_bias), self.trace_mode, self.rank, self.world_size,
                             int(self.collect_stats), self.sample_begin, self.sample_count)
+
+
+@dataclass(frozen=True)
+class Rect:
+    """rtk_rect / render_tile (render/tile/tile.hpp): pixels [x0, x1) x [y0, y1) of the frame."""
+    x0: int
+    y0: int
+    x1: int
+    y1: int
+
+    @property
+    def width(self) -> int:
+        return self.x1 - self.x0
+
+    @property
+    def height(self) -> int:
+        return self.y1 - self.y0
+
+    @property
+    def area(self) -> int:
+        return self.width * self.height
+
+
+def _rects_array(rects) -> np.ndarray:
+    """Rects, 4-tuples or a (K, 4) integer array -> contiguous (K, 4) int32 rows of x0, y0, x1, y1 (the layout of rtk_rect)."""
+    if isinstance(rects, np.ndarray):
+        arr = rects
+    else:
+        arr = np.array([(r.x0, r.y0, r.x1, r.y1) if isinstance(r, Rect) else tuple(r) for r in rects], np.int64).reshape(-1, 4)
+    if arr.ndim != 2 or arr.shape[1] != 4 or arr.dtype.kind not in "iu":
+        raise ValueError("rects must be Rects or a (K, 4) integer array of x0, y0, x1, y1")
+    if arr.size and (int(arr.min()) < -2**31 or int(arr.max()) >= 2**31):
+        raise ValueError("rectangle coordinates are 32-bit integers")
+    return np.ascontiguousarray(arr, np.int32)
 
 
 @dataclass
@@ -600,6 +639,48 @@ class KdTreeSimdAccel:
         """d_views_ptr: device float32 [n_views, 12]; d_out_ptr: device float32 [n_views, h, w, 3]; stream-ordered (rtk.h)."""
         p = cfg.to_c()
         _check(_L.rtk_render_views_device(self._h, C.byref(p), d_views_ptr or None, n_views, d_out_ptr or None, stream))
+
+    # ---- rectangles of a frame in one call (rtk.h rtk_rect, RTK_REGIONS_*)
+    def render_regions(self, cfg: RenderConfig, rects, layout: int = REGIONS_IN_FRAME, rgb: np.ndarray | None = None):
+        """rects: Rects or a (K, 4) int32 array of x0, y0, x1, y1.  Every pixel inside a rectangle comes out as render_frame(cfg)
+        leaves it; counters are the call's totals.
+        REGIONS_IN_FRAME -> ([h, w, 3] float32, counters): only the rectangles' pixels of `rgb` are written (a new buffer is zeros).
+        REGIONS_PACKED   -> (list of K views [y1-y0, x1-x0, 3] into one packed float32 array, counters); `rgb`: that packed array
+        (1-D, 3 * the sum of the areas), e.g. `views[0].base` of an earlier pass of a progressive render."""
+        arr = _rects_array(rects)
+        k = arr.shape[0]
+        w = cfg.width or self.scene.info.width
+        h = cfg.height or self.scene.info.height
+        if layout == REGIONS_PACKED:
+            areas = (arr[:, 2].astype(np.int64) - arr[:, 0]) * (arr[:, 3].astype(np.int64) - arr[:, 1])
+            shape = (int(np.maximum(areas, 0).sum()) * 3,)
+        else:
+            shape = (h, w, 3)
+        if rgb is None:
+            if cfg.sample_begin > 0:
+                raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
+            rgb = np.zeros(shape, np.float32)
+        if rgb.dtype != np.float32 or rgb.shape != shape or not rgb.flags.c_contiguous:
+            raise ValueError(f"rgb must be contiguous float32 of shape {shape}")
+        p = cfg.to_c()
+        c = Counters()
+        out = rgb if rgb.size else np.zeros(1, np.float32)         # (a packed list without pixels: a valid pointer nothing is written through)
+        _check(_L.rtk_render_regions(self._h, C.byref(p), arr.ctypes.data if k else None, k, layout, out.ctypes.data, C.byref(c)))
+        if layout != REGIONS_PACKED:
+            return rgb, c.as_dict()
+        views, at = [], 0
+        for x0, y0, x1, y1 in arr.tolist():
+            n = (x1 - x0) * (y1 - y0) * 3
+            views.append(rgb[at:at + n].reshape(y1 - y0, x1 - x0, 3))
+            at += n
+        return views, c.as_dict()
+
+    def render_regions_device(self, cfg: RenderConfig, rects, layout: int, d_out_ptr: int, stream: int = 0) -> None:
+        """rects in HOST memory (as render_regions); d_out_ptr: device float32, the frame or the packed array; stream-ordered (rtk.h)."""
+        arr = _rects_array(rects)
+        p = cfg.to_c()
+        _check(_L.rtk_render_regions_device(self._h, C.byref(p), arr.ctypes.data if arr.shape[0] else None, arr.shape[0], layout,
+                                            d_out_ptr or None, stream))
 
     # ---- lights, materials and background of a live accel (rtk.h rtk_light, rtk_material)
     def lights(self):

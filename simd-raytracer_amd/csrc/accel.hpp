@@ -188,6 +188,26 @@ struct rtk_accel {
     float *views_out = nullptr;
     size_t views_out_cap = 0;                  // floats
     unsigned long long *d_views_counters = nullptr;   // [kCounterWords] the call's totals while its frames / launches run
+    // ---- rg_* / fb_regions: rtk_render_regions (api_frame.hip).  One set of cost tables per launch of a call, as for views; they are
+    // reused only by a call whose rectangle list, layout and frame width equal the previous call's (rg_rects, rg_layout, rg_width), and
+    // then the table on the device is that call's too and is not uploaded again.
+    std::vector<rtk_cost_feedback> fb_regions;
+    std::vector<rtk_rect> rg_rects;
+    rtk::RegionsPlan rg_plan;                  // the plan of rg_rects (regions_plan.hpp): entries and launches
+    int rg_layout = -1;
+    uint32_t rg_width = 0;
+    size_t rg_limit = 0;                       // the launch limit the table on the device was cut with
+    rtk::RegionEntry *rg_table = nullptr;      // the entries of all launches of the call, one behind the other
+    size_t rg_table_cap = 0;                   // entries
+    bool rg_table_valid = false;               // rg_table holds the plan of rg_rects
+    hipEvent_t rg_done = nullptr;              // recorded behind a call's last kernel: the next table upload, on any stream, waits for it
+    bool rg_in_use = false;
+    rtk_ray *rg_rays = nullptr;                // streaming path: rays, frame pixel indices and colours of one chunk of pixels
+    uint32_t *rg_ids = nullptr;
+    float *rg_rgb = nullptr;
+    size_t rg_cap = 0;                         // pixels
+    float *rg_out = nullptr;                   // staging of the host variant
+    size_t rg_out_cap = 0;                     // floats
     // ---- trial_*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     hipEvent_t trial_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t trial_sig[3] = {0, 0, 0};

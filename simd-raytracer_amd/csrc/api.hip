@@ -359,6 +359,9 @@ void rtk_accel_destroy(rtk_accel *a) {
         (void)hipFree(a->rp_bounds); (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
         a->fb.release();
         for (rtk_cost_feedback &f : a->fb_views) f.release();
+        for (rtk_cost_feedback &f : a->fb_regions) f.release();
+        (void)hipFree(a->rg_table); (void)hipFree(a->rg_rays); (void)hipFree(a->rg_ids); (void)hipFree(a->rg_rgb); (void)hipFree(a->rg_out);
+        if (a->rg_done) (void)hipEventDestroy(a->rg_done);
         (void)hipFree(a->views_tab); (void)hipFree(a->views_out); (void)hipFree(a->d_views_counters);
         (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
         (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb); (void)hipFree(a->d_rad_counters);

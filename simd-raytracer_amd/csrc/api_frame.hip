@@ -401,7 +401,8 @@ int ensure_feedback_ws(rtk_accel *a, rtk_cost_feedback &fb, const FrameGeom &g, 
 int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general,
                       hipStream_t s) {
     const size_t per_view = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
-    const size_t units = A.views ? per_view * A.n_views : per_view;
+    // (a regions launch, rtk_render_regions, comes with its units counted: the blocks of its rectangles)
+    const size_t units = A.regions ? size_t(A.n_units) : (A.views ? per_view * A.n_views : per_view);
     A.n_units = uint32_t(units);
     // RTK_TRACE_AUTO for frames: four waves per pixel block when there are enough blocks to fill the chip several times over,
     // eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
@@ -413,7 +414,8 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
                                  (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
                                  (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays),
                                  (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode),
-                                 A.views ? uint64_t(A.n_views) : 0ull};           // (0: a frame; a views launch of one view is not one)
+                                 A.regions ? ((1ull << 63) | (uint64_t(A.n_regions) << 32) | uint64_t(A.n_units))   // (its list is compared by the caller)
+                                           : (A.views ? uint64_t(A.n_views) : 0ull)};   // (0: a frame; a views launch of one view is not one)
         RTK_TRY(ensure_feedback_ws(a, fb, g, units));
         uint32_t *const order_hdr = fb.order + units, *const wg_list = fb.order + units + 4;
         auto use_order = [&] { A.order_in = fb.order; A.order_hdr = order_hdr; A.wg_list = wg_list; };
@@ -422,7 +424,8 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
         // The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in for them
         // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at).
         // A one-shot render is exactly this frame (the reference CLI renders one, src/main.cpp:13-25).
-        const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0;
+        // (the first launch of a new rectangle list runs in the natural order: k_block_prior maps units through the buckets)
+        const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0 && !A.regions;
         if (prior) {
             RTK_HIP_AS(launch_block_prior(A, fb.bins, fb.order, wg_list, order_hdr,
                                           reinterpret_cast<uint32_t *>(a->d_counters + kCounterWords), 4u, s), "launch k_block_prior");
@@ -651,6 +654,133 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
     return release_stream_ws(a, s);
 }
 
+// ---------------------------------------------------------------- rtk_render_regions
+
+// Pixels of one chunk of the streaming path: rays, ids and colours are 40 B per pixel, so a chunk's workspace is 40 MB however
+// large the rectangles are; a chunk is also one radiance batch, which likes a few hundred thousand rays at least.
+constexpr uint64_t kRegionChunkPixels = uint64_t(1) << 20;
+
+// everything the call refuses, in the order rtk.h gives
+int regions_check(const rtk_accel *a, const rtk_render_params *p, const rtk_rect *rects, int32_t n_rects, int layout, const void *out,
+                  FrameGeom &g) {
+    RTK_TRY(frame_geom(a, p, g));
+    if (p->trace_mode == RTK_TRACE_LANE || p->trace_mode == RTK_TRACE_WAVE || p->trace_mode == RTK_TRACE_TWOPASS)
+        return fail(RTK_ERR_INVALID, "regions run through RTK_TRACE_AUTO, _GROUP4 / 8 / 16 or _STREAM");
+    if (p->collect_stats != 0) return fail(RTK_ERR_INVALID, "regions collect no per-ray statistics");
+    if (p->world_size > 1) return fail(RTK_ERR_INVALID, "regions are not sharded: deal rectangles to the ranks");
+    if (n_rects < 0 || n_rects > kMaxRegions) return fail(RTK_ERR_INVALID, "n_rects must be in [0, 65536]");
+    if (layout != RTK_REGIONS_IN_FRAME && layout != RTK_REGIONS_PACKED) return fail(RTK_ERR_INVALID, "unknown layout");
+    if (n_rects > 0 && (!rects || !out)) return fail(RTK_ERR_INVALID, "null rectangles or output buffer");
+    for (int32_t i = 0; i < n_rects; ++i)
+        if (!region_valid(rects[i], g.width, g.height)) return fail(RTK_ERR_INVALID, "rectangle " + std::to_string(i) + " is not inside the frame");
+    if (layout == RTK_REGIONS_IN_FRAME && regions_overlap(rects, size_t(n_rects)))
+        return fail(RTK_ERR_INVALID, "rectangles overlap: RTK_REGIONS_IN_FRAME needs them pairwise disjoint");
+    return RTK_OK;
+}
+
+uint64_t regions_pixels(const rtk_rect *rects, int32_t n_rects) {
+    uint64_t px = 0;
+    for (int32_t i = 0; i < n_rects; ++i) px += region_area(rects[i]);
+    return px;
+}
+
+// The plan of the call and its table on the device.  A call whose list, layout, frame width and launch limit equal the previous
+// call's finds both in place (a re-render loop uploads nothing and keeps its measured launch order); any other list is planned
+// and uploaded on `s`, behind the previous call's last kernel, and every launch of it starts without an order.
+int regions_table(rtk_accel *a, const FrameGeom &g, const rtk_rect *rects, size_t n, int layout, hipStream_t s) {
+    const size_t limit = a->knobs.views_launch_units;
+    if (a->rg_table_valid && a->rg_layout == layout && a->rg_width == g.width && a->rg_limit == limit && a->rg_rects.size() == n &&
+        std::memcmp(a->rg_rects.data(), rects, n * sizeof(rtk_rect)) == 0) return RTK_OK;
+    a->rg_table_valid = false;
+    for (rtk_cost_feedback &f : a->fb_regions) f.forget();
+    a->rg_plan = plan_regions(rects, n, layout, g.width, limit);
+    const size_t n_entries = a->rg_plan.entries.size();
+    if (!a->rg_done) RTK_HIP(hipEventCreateWithFlags(&a->rg_done, hipEventDisableTiming));
+    if (a->rg_table_cap < n_entries) {
+        const size_t cap = n_entries + n_entries / 2 + 16;
+        RTK_HIP(hipDeviceSynchronize());
+        (void)hipFree(a->rg_table); a->rg_table = nullptr; a->rg_table_cap = 0;
+        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_table), cap * sizeof(RegionEntry)));
+        a->rg_table_cap = cap;
+    } else if (a->rg_in_use) {
+        RTK_HIP(hipStreamWaitEvent(s, a->rg_done, 0));                // a call on another stream may still be reading the old table
+    }
+    RTK_HIP(hipMemcpyAsync(a->rg_table, a->rg_plan.entries.data(), n_entries * sizeof(RegionEntry), hipMemcpyHostToDevice, s));
+    a->rg_rects.assign(rects, rects + n);
+    a->rg_layout = layout; a->rg_width = g.width; a->rg_limit = limit;
+    a->rg_table_valid = true;
+    return RTK_OK;
+}
+
+// (the rectangles have pixels: the callers return before this for a call without any)
+int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_rect *rects, int32_t n_rects, int layout,
+                        float *d_out, hipStream_t s) {
+    RTK_TRY(regions_table(a, g, rects, size_t(n_rects), layout, s));
+    const RegionsPlan &P = a->rg_plan;
+    const bool forks = a->has_refractive || p->diffuse_rays > 0;
+    const bool general = forks || !a->scene.textures.empty();
+    const bool stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
+    dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_out);
+    if (!stream) {
+        // the megakernel: one launch per RegionLaunch, each with cost tables of its own; several are folded into the call's totals
+        const size_t n_parts = P.launches.size();
+        if (a->fb_regions.size() < n_parts) a->fb_regions.resize(n_parts);
+        if (n_parts > 1) {
+            if (!a->d_views_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_views_counters), kCounterWords * sizeof(unsigned long long)));
+            RTK_HIP(hipMemsetAsync(a->d_views_counters, 0, kCounterWords * sizeof(unsigned long long), s));
+        }
+        for (size_t c = 0; c < n_parts; ++c) {
+            const RegionLaunch &L = P.launches[c];
+            A.regions = a->rg_table + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
+            A.order_in = nullptr; A.order_hdr = nullptr; A.wg_list = nullptr; A.cost_out = nullptr;
+            RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+            RTK_TRY(render_megakernel(a, a->fb_regions[c], p, g, A, general, s));
+            if (n_parts > 1) RTK_HIP_AS(launch_counters_fold(a->d_counters, a->d_views_counters, s), "launch k_counters_fold");
+        }
+        if (n_parts > 1) RTK_HIP(hipMemcpyAsync(a->d_counters, a->d_views_counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    } else {
+        // sample by sample and chunk by chunk: camera rays + frame pixel indices, the radiance pipeline, the sums.  All of a
+        // pixel's launches are on `s` (the pipeline forks onto its lanes and joins `s` again), so its sum stays in sample order.
+        uint64_t largest = 0;
+        for (const RegionLaunch &L : P.launches) largest = L.n_pixels > largest ? L.n_pixels : largest;
+        const size_t chunk = size_t(largest < kRegionChunkPixels ? largest : kRegionChunkPixels);
+        if (a->rg_cap < chunk) {
+            const size_t cap = chunk + chunk / 2 < kRegionChunkPixels ? chunk + chunk / 2 : size_t(kRegionChunkPixels);
+            RTK_HIP(hipDeviceSynchronize());
+            (void)hipFree(a->rg_rays); (void)hipFree(a->rg_ids); (void)hipFree(a->rg_rgb);
+            a->rg_rays = nullptr; a->rg_ids = nullptr; a->rg_rgb = nullptr; a->rg_cap = 0;
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_rays), cap * sizeof(rtk_ray)));
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_ids), cap * sizeof(uint32_t)));
+            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_rgb), cap * 3 * sizeof(float)));
+            a->rg_cap = cap;
+        }
+        rtk_radiance_params rp;
+        rp.max_ray_depth = p->max_ray_depth; rp.diffuse_rays = p->diffuse_rays; rp.seed = p->seed; rp.sample = 0;
+        rp.shadow_bias = p->shadow_bias; rp.reflection_bias = p->reflection_bias; rp.refraction_bias = p->refraction_bias;
+        rp.cull = 1; rp.trace_mode = RTK_TRACE_STREAM;
+        RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+        for (const RegionLaunch &L : P.launches) {
+            A.regions = a->rg_table + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
+            for (uint64_t first = 0; first < L.n_pixels; first += chunk) {
+                const uint32_t cn = uint32_t(L.n_pixels - first < chunk ? L.n_pixels - first : chunk);
+                for (int smp = g.sample_begin; smp < g.sample_end; ++smp) {
+                    RTK_HIP_AS(launch_region_rays(A, smp, first, cn, a->rg_rays, a->rg_ids, s), "launch k_region_rays");
+                    rp.sample = smp;
+                    RTK_TRY(radiance_device_impl(a, a->rg_rays, a->rg_ids, cn, &rp, a->rg_rgb, s, nullptr));
+                    RTK_HIP_AS(launch_add_word(a->d_counters, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, s), "launch k_add_word");
+                    RTK_HIP_AS(launch_region_accumulate(A, first, cn, a->rg_rgb, smp == 0, p->spp != 1 && smp + 1 == p->spp, s), "launch k_region_accumulate");
+                }
+            }
+        }
+    }
+    RTK_HIP(hipEventRecord(a->rg_done, s));
+    a->rg_in_use = true;
+    a->last_stream = s;
+    a->last_stats = false;
+    a->last_primary = P.total_pixels * uint64_t(g.sample_end - g.sample_begin);
+    return RTK_OK;
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -799,7 +929,10 @@ int rtk_accel_set_camera(rtk_accel *a, const rtk_view *view) {
     // frame, and the third takes 0.20 ms against 0.30 under a kept order, which is served until its next re-sort (rtk.h;
     // RTK_CAMERA_KEEPS_ORDER=1 keeps it).  RTK_TRACE_AUTO's
     // engine verdict stays: started over at every move, the trial of a camera in motion would never end.
-    if (!a->knobs.camera_keeps_order) a->fb.forget();
+    if (!a->knobs.camera_keeps_order) {
+        a->fb.forget();
+        for (rtk_cost_feedback &f : a->fb_regions) f.forget();       // (rectangles are seen from the accel's camera; views bring their own)
+    }
     return RTK_OK;
 }
 
@@ -840,6 +973,50 @@ int rtk_render_views(rtk_accel *a, const rtk_render_params *p, const rtk_view *v
     }
     if (counters) return rtk_render_last_counters(a, counters);
     return RTK_OK;
+}
+
+// ---------------------------------------------------------------- regions
+
+int rtk_render_regions_device(rtk_accel *a, const rtk_render_params *p, const rtk_rect *rects, int32_t n_rects, int layout, float *d_out,
+                              void *stream) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    try {
+        FrameGeom g;
+        RTK_TRY(regions_check(a, p, rects, n_rects, layout, d_out, g));
+        if (n_rects == 0 || regions_pixels(rects, n_rects) == 0) return RTK_OK;
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return render_regions_impl(a, p, g, rects, n_rects, layout, d_out, static_cast<hipStream_t>(stream));
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+}
+
+int rtk_render_regions(rtk_accel *a, const rtk_render_params *p, const rtk_rect *rects, int32_t n_rects, int layout, float *rgb,
+                       rtk_counters *counters) {
+    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+    try {
+        FrameGeom g;
+        RTK_TRY(regions_check(a, p, rects, n_rects, layout, rgb, g));
+        const uint64_t pixels = n_rects > 0 ? regions_pixels(rects, n_rects) : 0;
+        if (pixels == 0) return RTK_OK;
+        {
+            std::lock_guard<std::mutex> lock(a->mu);
+            RTK_TRY(ensure_device(a));
+            // what the layout needs: the packed buffer, or the whole frame up and down, so that the caller's pixels outside the
+            // rectangles come back with the bits they went up with
+            const bool packed = layout == RTK_REGIONS_PACKED;
+            const size_t nf = packed ? size_t(pixels) * 3 : size_t(g.width) * g.height * 3;
+            if (a->rg_out_cap < nf) {
+                (void)hipFree(a->rg_out); a->rg_out = nullptr; a->rg_out_cap = 0;
+                RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_out), nf * sizeof(float)));
+                a->rg_out_cap = nf;
+            }
+            if (!packed || p->sample_begin > 0) RTK_HIP(hipMemcpy(a->rg_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice));
+            RTK_TRY(render_regions_impl(a, p, g, rects, n_rects, layout, a->rg_out, nullptr));
+            RTK_HIP(hipMemcpy(rgb, a->rg_out, nf * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        if (counters) return rtk_render_last_counters(a, counters);
+        return RTK_OK;
+    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }
 
 // ---------------------------------------------------------------- camera rays

@@ -29,6 +29,7 @@ void lights_changed(rtk_accel *a, size_t n_before) {
     if (a->scene.lights.size() == n_before) return;
     a->fb.forget();
     for (rtk_cost_feedback &f : a->fb_views) f.forget();
+    for (rtk_cost_feedback &f : a->fb_regions) f.forget();
 }
 
 }  // namespace
@@ -136,6 +137,7 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
         // a scene that starts or stops forking runs other kernels over other block costs, and needs a new verdict
         a->fb.forget();
         for (rtk_cost_feedback &f : a->fb_views) f.forget();
+        for (rtk_cost_feedback &f : a->fb_regions) f.forget();
         a->trial_state = 0;
         return RTK_OK;
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }

@@ -358,6 +358,7 @@ int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hip
     // the launch order learnt from the old silhouette and the engines' trial on it say nothing about the new geometry
     a->fb.forget();
     for (rtk_cost_feedback &f : a->fb_views) f.forget();
+    for (rtk_cost_feedback &f : a->fb_regions) f.forget();
     a->trial_state = 0;
     return RTK_OK;
 }

@@ -168,6 +168,13 @@ __device__ __forceinline__ Ray spawn_ray(const V3 o, const V3 d) {
     return r;
 }
 
+// An entry of a regions launch's table, through the scalar cache (trace.hip.hpp "Wave-uniform loads": as plain global loads the
+// compiler fetched the entry per lane, and the block's corner then lived in -- and was spilled from -- vector registers).
+typedef const RegionEntry __attribute__((address_space(4))) *cptr_region;
+__device__ __forceinline__ cptr_region region_entry(const RegionEntry *table, const uint32_t r) {
+    return (cptr_region)(const void __attribute__((address_space(4))) *)(table + r);
+}
+
 enum : int { ST_NEW_SAMPLE = 0, ST_TRACE, ST_SHADE, ST_LIGHT, ST_RETURN, ST_DONE };
 enum : int { PEND_CHILD_BG = 0, PEND_CHILD_BLACK = 1, PEND_SHADOW = 2 };
 enum : uint32_t { FR_REFR_A = 0, FR_REFR_B = 1, FR_DIFFUSE = 2 };
@@ -179,7 +186,7 @@ struct Frame {            // 15 dwords, lives in scratch; touched only at refrac
     uint32_t key;         // RNG key of the ray whose hit this frame shades
 };
 
-template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRIMED = false, bool VIEWS = false>
+template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRIMED = false, bool VIEWS = false, bool REGIONS = false>
 // GROUP4 without per-ray statistics is built for RTK_G4_WAVES (5) waves per SIMD = 96 VGPRs: a fifth resident workgroup per CU.
 // The lean build (FORKS = false) fits with its cold state parked in LDS (`park_lds`); 4 waves / 128 VGPRs and 6 / 80 are slower.
 __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : SLICES == 8 ? 2 : (SLICES == 4 && !STATS ? RTK_G4_WAVES : 4)) void k_render(RenderArgs A) {
@@ -238,6 +245,22 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         if (view >= A.n_views) return;                   // purely defensive: launch_render refuses a launch whose units are not n_views x units_per_view
         block = gwave - view * A.units_per_view;
     }
+    // REGIONS (rtk_render_regions as one launch): the units are (rectangle, 8x8 block) pairs, the blocks anchored at the rectangle's own
+    // corner.  The rectangle belongs to the WAVE's unit, as a view does, and is found wave-uniformly: a binary search over the
+    // entries' first_unit with scalar loads (gwave is wave-uniform; 17 steps for 65,536 rectangles, once per block).  Only its
+    // number is kept; the entry is read again through the scalar cache where a pixel is stored.
+    uint32_t rect = 0u;
+    if constexpr (REGIONS) {
+        const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)gwave);
+        if (unit >= A.n_units || A.n_regions == 0u) return;      // purely defensive: launch_render refuses a launch without units or entries
+        uint32_t lo = 0u, hi = A.n_regions;                      // regions[lo].first_unit <= unit < regions[hi].first_unit (or hi == n)
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (region_entry(A.regions, mid)->first_unit <= unit) lo = mid; else hi = mid;
+        }
+        rect = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+        block = unit - region_entry(A.regions, rect)->first_unit;
+    }
     const auto view_out = [&]() { return VIEWS ? A.out + (size_t)view * A.view_stride : A.out; };
     // one parking area per wave that can own rays: every wave of a light or SLICES == 1 workgroup, one otherwise -- the
     // others then hold the answers of a light burst's jobs (ShadowBurstService)
@@ -262,12 +285,25 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const unsigned long long real_t0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz, for the frame's critical path (bench.py)
     constexpr bool writer = true;
     // (block_map() / block_pixel() written out: through them the benchmark's kernel loses its register allocation)
+    uint32_t local_bucket, bx, by, sub_x0, sub_y0;
+    bool valid;
+    if constexpr (REGIONS) {
+        // the block's corner in the frame: the pixels, their RNG keys and camera rays below are the frame's own (px, py, width, height)
+        const cptr_region R = region_entry(A.regions, rect);
+        const uint32_t blocks_x = ((uint32_t)R->w + 7u) >> 3;
+        const uint32_t row = block / blocks_x;
+        local_bucket = 0u; sub_x0 = 0u; sub_y0 = 0u;
+        bx = (uint32_t)R->x0 + (block - row * blocks_x) * 8u; by = (uint32_t)R->y0 + row * 8u;
+        valid = true;
+    } else {
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint32_t local_bucket = block / bpb, sub = block % bpb;
+    local_bucket = block / bpb;
+    const uint32_t sub = block % bpb;
     const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
-    bool valid = bucket < A.n_buckets;
-    const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
-    const uint32_t sub_x0 = (sub % A.blocks_per_bucket_side) * 8u, sub_y0 = (sub / A.blocks_per_bucket_side) * 8u;   // wave-uniform
+    valid = bucket < A.n_buckets;
+    bx = (bucket % A.tiles_x) * A.bucket; by = (bucket / A.tiles_x) * A.bucket;
+    sub_x0 = (sub % A.blocks_per_bucket_side) * 8u; sub_y0 = (sub / A.blocks_per_bucket_side) * 8u;   // wave-uniform
+    }
     // this lane's pixel: recomputed where it is needed (see fresh_lane) instead of living in registers across the traversal
     const auto my_pixel = [&]() {
         const uint32_t l = fresh_lane();
@@ -276,9 +312,23 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         p.px = bx + p.lx; p.py = by + p.ly;
         return p;
     };
+    // where that pixel lives in the output, in pixels (REGIONS: the entry says, so the kernel does not know the two layouts apart)
+    const auto pixel_slot = [&](const Pixel &p) -> size_t {
+        if constexpr (REGIONS) {
+            const cptr_region R = region_entry(A.regions, rect);
+            return (size_t)(R->base + (long long)p.py * (long long)R->pitch + (long long)p.px);
+        } else {
+            return A.out_index(local_bucket, p.lx, p.ly, p.px, p.py);
+        }
+    };
     {
         const Pixel p = my_pixel();
+        if constexpr (REGIONS) {
+            const cptr_region R = region_entry(A.regions, rect);
+            valid = (p.px < (uint32_t)(R->x0 + R->w)) & (p.py < (uint32_t)(R->y0 + R->h));
+        } else {
         valid = valid & (p.lx < A.bucket) & (p.ly < A.bucket) & (p.px < A.width) & (p.py < A.height);
+        }
     }
 
     phases.prologue_done();
@@ -297,7 +347,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     V3 pixel_sum = black, ret = black;
     if (A.sample_begin > 0 && valid) {                                     // a later pass of a progressive frame: the running sum so far
         const Pixel p = my_pixel();
-        const float *o = view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
+        const float *o = view_out() + pixel_slot(p) * 3;
         pixel_sum = mk(o[0], o[1], o[2]);
     }
     // hit being shaded / lit
@@ -327,7 +377,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                     const float inv = A.spp_f;
                     if (writer) {
                         const Pixel p = my_pixel();
-                        float *o = view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3;
+                        float *o = view_out() + pixel_slot(p) * 3;
                         // the last pass divides (render.hpp:72; x / 1.0f == x, bit for bit); earlier passes leave the running sum
                         if (A.spp == 1 || A.sample_end != A.spp) { o[0] = pixel_sum.x; o[1] = pixel_sum.y; o[2] = pixel_sum.z; }
                         else { o[0] = pixel_sum.x / inv; o[1] = pixel_sum.y / inv; o[2] = pixel_sum.z / inv; }
@@ -665,7 +715,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const uint32_t lane = fresh_lane();
     if (kPhases && valid && writer) {
         const Pixel p = my_pixel();
-        phases.write(sx.probe(), lane, view_out() + A.out_index(local_bucket, p.lx, p.ly, p.px, p.py) * 3);
+        phases.write(sx.probe(), lane, view_out() + pixel_slot(p) * 3);
     }
     if (A.cost_out != nullptr && lane == 0u && gwave < A.n_units) {        // what this block cost, for the next frame's order
         // (a block that ran alone on one wave of a packed workgroup took about twice as long as it would with helpers)
@@ -783,6 +833,56 @@ __global__ __launch_bounds__(256) void k_camera_rays(RenderArgs A, int sample, r
     o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
 }
 
+// The streaming path of rtk_render_regions.  Pixel i of a launch's entries (RegionEntry::first_pixel order: rectangle after
+// rectangle, each row-major) -> its rectangle (a binary search per thread: one thread per pixel, nothing here is hot) and its
+// frame coordinates.
+struct RegionPixel { const RegionEntry *R; uint32_t px, py; };
+__device__ __forceinline__ RegionPixel region_pixel(const RenderArgs &A, const uint64_t i) {
+    uint32_t lo = 0u, hi = A.n_regions;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (A.regions[mid].first_pixel <= i) lo = mid; else hi = mid;
+    }
+    RegionPixel q;
+    q.R = A.regions + lo;
+    const uint64_t local = i - q.R->first_pixel;
+    const uint32_t w = (uint32_t)q.R->w, row = (uint32_t)(local / w);
+    q.py = (uint32_t)q.R->y0 + row;
+    q.px = (uint32_t)q.R->x0 + (uint32_t)(local - (uint64_t)row * w);
+    return q;
+}
+
+// camera rays (k_camera_rays' arithmetic: the frame's px, py, width, height and RNG key) and frame pixel indices of pixels
+// [first, first + n) at `sample`: what rtk_accel_radiance needs to give exactly that sample of the frame
+__global__ __launch_bounds__(256) void k_region_rays(RenderArgs A, int sample, uint64_t first, uint32_t n, rtk_ray *out, uint32_t *ids) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n || A.n_regions == 0u) return;
+    const RegionPixel q = region_pixel(A, first + t);
+    const uint32_t pixel = q.py * A.width + q.px;
+    const Ray r = camera_ray(A, q.px, q.py, root_key(pcg_hash(A.seed), pixel, (uint32_t)sample));
+    float *o = reinterpret_cast<float *>(out + t);
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
+    ids[t] = pixel;
+}
+
+// pixel_sum += colour (render.hpp:66), in sample order because the launches of a pixel are on one stream; the sample that ends
+// the frame divides (render.hpp:72), as k_render's ST_NEW_SAMPLE does.  A colour arrives as +0 + c (rtk.h, rtk_accel_radiance).
+__global__ __launch_bounds__(256) void k_region_accumulate(RenderArgs A, uint64_t first, uint32_t n, const float *rgb, int start, int divide) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n || A.n_regions == 0u) return;
+    const RegionPixel q = region_pixel(A, first + t);
+    float *o = A.out + (size_t)(q.R->base + (long long)q.py * (long long)q.R->pitch + (long long)q.px) * 3;
+    const float *c = rgb + (size_t)t * 3;
+    V3 sum = start ? mk(0.f, 0.f, 0.f) : mk(o[0], o[1], o[2]);
+    sum = sum + mk(c[0], c[1], c[2]);
+    if (divide) { const float inv = A.spp_f; sum = mk(sum.x / inv, sum.y / inv, sum.z / inv); }
+    o[0] = sum.x; o[1] = sum.y; o[2] = sum.z;
+}
+
+__global__ void k_add_word(unsigned long long *dst, const unsigned long long *src) {
+    if (threadIdx.x == 0u && blockIdx.x == 0u) dst[0] += src[0];
+}
+
 // write_ppm's quantisation (io/image/ppm.hpp:17-19): uint8(255.999 * clamp(c, 0, 1)), the product in double.
 __global__ __launch_bounds__(256) void k_to_rgb8(const float *rgb, size_t n, uint8_t *out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -827,6 +927,14 @@ hipError_t launch_render_views_m(const dev::RenderArgs &A, unsigned blocks, bool
     return hipGetLastError();
 }
 
+// rtk_render_regions as one launch: the same set
+template <int SLICES>
+hipError_t launch_render_regions_m(const dev::RenderArgs &A, unsigned blocks, bool forks, hipStream_t s) {
+    if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, true, false, SLICES, false, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
+    else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, SLICES, false, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
+    return hipGetLastError();
+}
+
 template <int MODE, int SLICES>
 hipError_t launch_render_mode(const dev::RenderArgs &A, unsigned blocks, bool stats, bool forks, bool lds, size_t lds_bytes,
                               hipStream_t s) {
@@ -859,6 +967,17 @@ hipError_t launch_render(const dev::RenderArgs &A, int mode, bool stats, bool fo
     hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, 4>), dim3(A.n_units), dim3(256), 0, s, A);
     return hipGetLastError();
 #else
+    if (A.regions != nullptr) {
+        // (rectangle, block) units: the entries say how many there are; a launch that is not made of them gets an error
+        if (stats || A.views != nullptr || A.n_regions == 0u || A.n_units == 0u || A.n_units > 0x7FFFFFFFu || A.world > 1) return hipErrorInvalidValue;
+        const unsigned listed = (n_workgroups != 0u && n_workgroups < A.n_units) ? n_workgroups : A.n_units;
+        switch (mode) {
+            case RTK_TRACE_GROUP4: return launch_render_regions_m<4>(A, listed, forks, s);
+            case RTK_TRACE_GROUP8: return launch_render_regions_m<8>(A, A.n_units, forks, s);
+            case RTK_TRACE_GROUP16: return launch_render_regions_m<16>(A, A.n_units, forks, s);
+            default: return hipErrorInvalidValue;
+        }
+    }
     const size_t lds_bytes = (size_t)A.tree.n_nodes * sizeof(DevNode);
     const bool lds = lds_bytes <= kMaxNodeLdsBytes;
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
@@ -1154,6 +1273,25 @@ hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_r
     const size_t n = (size_t)A.width * A.height;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(dev::k_camera_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, sample, d_rays);
+    return hipGetLastError();
+}
+
+hipError_t launch_region_rays(const dev::RenderArgs &A, int sample, uint64_t first, uint32_t n, rtk_ray *d_rays, uint32_t *d_ids, hipStream_t s) {
+    if (n == 0u) return hipSuccess;
+    if (A.regions == nullptr || A.n_regions == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_region_rays, dim3((n + 255u) / 256u), dim3(256), 0, s, A, sample, first, n, d_rays, d_ids);
+    return hipGetLastError();
+}
+
+hipError_t launch_region_accumulate(const dev::RenderArgs &A, uint64_t first, uint32_t n, const float *d_rgb, bool start, bool divide, hipStream_t s) {
+    if (n == 0u) return hipSuccess;
+    if (A.regions == nullptr || A.n_regions == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_region_accumulate, dim3((n + 255u) / 256u), dim3(256), 0, s, A, first, n, d_rgb, start ? 1 : 0, divide ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_add_word(unsigned long long *dst, const unsigned long long *src, hipStream_t s) {
+    hipLaunchKernelGGL(dev::k_add_word, dim3(1), dim3(64), 0, s, dst, src);
     return hipGetLastError();
 }
 

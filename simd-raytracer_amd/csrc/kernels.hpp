@@ -19,6 +19,7 @@ constexpr size_t kMaxNodeLdsBytes = 48 * 1024;   // node arrays up to this size 
 }  // namespace rtk
 
 #include "trace.hip.hpp"
+#include "regions_plan.hpp"
 
 namespace rtk {
 namespace dev {
@@ -111,6 +112,10 @@ struct RenderArgs {
     const float *views;               // [n_views][12] position, matrix (rtk_view), on the device
     uint32_t n_views, units_per_view;
     size_t view_stride;               // floats from one view's output to the next (width * height * 3)
+    // rtk_render_regions as ONE launch (k_render<..., REGIONS>; api_frame.hip): the launch's units are (rectangle, 8x8 block) pairs, the
+    // blocks anchored at the rectangle's own corner; unit = regions[r].first_unit + block.  Null / 0 for a frame.
+    const RegionEntry *regions;       // [n_regions] regions_plan.hpp, on the device; every entry has pixels
+    uint32_t n_regions;
 
     __device__ __forceinline__ size_t out_index(uint32_t local_bucket, uint32_t lx, uint32_t ly, uint32_t px,
                                                 uint32_t py) const {
@@ -148,5 +153,12 @@ hipError_t launch_twopass(const dev::RenderArgs &A, bool stats, bool forks, hipS
 hipError_t launch_assemble(const dev::AssembleArgs &A, hipStream_t s);
 hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_rays, hipStream_t s);
 hipError_t launch_to_rgb8(const float *d_rgb, size_t n, uint8_t *d_out, hipStream_t s);
+// The streaming path of rtk_render_regions, per sample and chunk of `n` pixels starting at pixel `first` of the launch's entries
+// (RegionEntry::first_pixel order): the camera rays of those pixels at `sample` with their frame pixel indices ...
+hipError_t launch_region_rays(const dev::RenderArgs &A, int sample, uint64_t first, uint32_t n, rtk_ray *d_rays, uint32_t *d_ids, hipStream_t s);
+// ... and their colours added into A.out: `start` = the pixel's sum starts at +0 (sample 0), `divide` = this is sample spp - 1 of spp > 1
+hipError_t launch_region_accumulate(const dev::RenderArgs &A, uint64_t first, uint32_t n, const float *d_rgb, bool start, bool divide, hipStream_t s);
+// dst[0] += src[0] (a radiance batch's ray count into the call's counters)
+hipError_t launch_add_word(unsigned long long *dst, const unsigned long long *src, hipStream_t s);
 
 }  // namespace rtk

@@ -363,6 +363,56 @@ struct hip_accel {
         return out;
     }
 
+    // Rectangles of the frame `params` describes, all in one call (rtk_render_regions).  Tile: anything with x0, y0, x1, y1 --
+    // the reference's render_tile (render/tile/tile.hpp), what its single / region / bucket schedulers hand to tile_worker, or
+    // rtk_rect.  Every pixel is what render_frame(params) gives there; counters: the call's totals.
+    // RTK_REGIONS_PACKED: image r is tile r alone, [y1-y0][x1-x0]; tiles may overlap.
+    template <typename Tile>
+    [[nodiscard]] std::vector<std::vector<std::vector<color<F>>>> render_regions(std::span<const Tile> tiles, const rtk_render_params &params,
+                                                                                rtk_counters *counters = nullptr) const {
+        whole_samples(params, "hip_accel::render_regions");
+        const std::vector<rtk_rect> in = to_rects(tiles);
+        std::size_t total = 0;
+        for (const rtk_rect &r : in) total += r.x1 > r.x0 && r.y1 > r.y0 ? static_cast<std::size_t>(r.x1 - r.x0) * static_cast<std::size_t>(r.y1 - r.y0) : 0;
+        std::vector<float> rgb(total * 3 + 1);
+        check(rtk_render_regions(accel_.get(), &params, in.empty() ? nullptr : in.data(), static_cast<int32_t>(in.size()), RTK_REGIONS_PACKED,
+                                 rgb.data(), counters));
+        std::vector<std::vector<std::vector<color<F>>>> out(in.size());
+        const float *px = rgb.data();
+        for (std::size_t r = 0; r < in.size(); ++r) {
+            const std::size_t w = static_cast<std::size_t>(in[r].x1 - in[r].x0), h = static_cast<std::size_t>(in[r].y1 - in[r].y0);
+            out[r].assign(h, std::vector<color<F>>(w));
+            for (std::size_t y = 0; y < h; ++y)
+                for (std::size_t x = 0; x < w; ++x, px += 3) out[r][y][x] = color<F>{px[0], px[1], px[2]};
+        }
+        return out;
+    }
+
+    // RTK_REGIONS_IN_FRAME: the tiles' pixels of `image` ([h][w], the frame of `params`) are rendered, every other pixel of it is
+    // left as it is.  The tiles must be pairwise disjoint.
+    template <typename Tile>
+    void render_regions_into(std::vector<std::vector<color<F>>> &image, std::span<const Tile> tiles, const rtk_render_params &params,
+                             rtk_counters *counters = nullptr) const {
+        whole_samples(params, "hip_accel::render_regions_into");
+        std::size_t n = 0;
+        check(rtk_render_output_floats(accel_.get(), &params, &n));
+        const std::size_t w = params.width > 0 ? static_cast<std::size_t>(params.width) : scene_ptr->config.image_width;
+        const std::size_t h = n / 3 / w;
+        if (image.size() != h) throw std::invalid_argument("hip_accel::render_regions_into: the image has not the frame's height");
+        for (const auto &row : image)
+            if (row.size() != w) throw std::invalid_argument("hip_accel::render_regions_into: the image has not the frame's width");
+        const std::vector<rtk_rect> in = to_rects(tiles);
+        std::vector<float> rgb(n + 1);
+        check(rtk_render_regions(accel_.get(), &params, in.empty() ? nullptr : in.data(), static_cast<int32_t>(in.size()), RTK_REGIONS_IN_FRAME,
+                                 rgb.data(), counters));
+        for (const rtk_rect &r : in)
+            for (std::size_t y = static_cast<std::size_t>(r.y0); y < static_cast<std::size_t>(r.y1); ++y)
+                for (std::size_t x = static_cast<std::size_t>(r.x0); x < static_cast<std::size_t>(r.x1); ++x) {
+                    const float *px = rgb.data() + (y * w + x) * 3;
+                    image[y][x] = color<F>{px[0], px[1], px[2]};
+                }
+    }
+
     // render_frame<A,F>(accel, BUCKET_TILES) with the whole loop device-side; pixels [h][w] as in image<F>
     [[nodiscard]] std::vector<std::vector<color<F>>> render_frame(const rtk_render_params &params, rtk_counters *counters = nullptr) const {
         // this returns a finished image: a partial pass of a progressive frame (sample_begin / sample_count) needs the running
@@ -434,6 +484,28 @@ private:
         v.position[0] = c.position.x; v.position[1] = c.position.y; v.position[2] = c.position.z;
         for (std::size_t i = 0; i < 9; ++i) v.matrix[i] = c.matrix.m[i];
         return v;
+    }
+
+    // render_tile's std::size_t corners as rtk_rect's int32 ones; a corner that does not fit becomes one the library refuses
+    template <typename Tile>
+    static std::vector<rtk_rect> to_rects(std::span<const Tile> tiles) {
+        const auto corner = [](auto v) -> int32_t {
+            if constexpr (std::is_unsigned_v<decltype(v)>) {
+                return static_cast<unsigned long long>(v) > 0x7FFFFFFFull ? int32_t(0x7FFFFFFF) : static_cast<int32_t>(v);
+            } else {
+                const long long s = static_cast<long long>(v);
+                return s > 0x7FFFFFFFll ? int32_t(0x7FFFFFFF) : (s < -0x7FFFFFFFll ? int32_t(-0x7FFFFFFF) : static_cast<int32_t>(s));
+            }
+        };
+        std::vector<rtk_rect> out(tiles.size());
+        for (std::size_t i = 0; i < tiles.size(); ++i) out[i] = rtk_rect{corner(tiles[i].x0), corner(tiles[i].y0), corner(tiles[i].x1), corner(tiles[i].y1)};
+        return out;
+    }
+
+    // the calls that return finished images take no partial pass of a progressive frame (see render_frame)
+    static void whole_samples(const rtk_render_params &params, const char *who) {
+        if (params.sample_begin != 0 || (params.sample_count != 0 && params.sample_count != params.spp))
+            throw std::invalid_argument(std::string(who) + " renders finished pixels (sample_begin = 0, all spp samples)");
     }
 
     static void check(int rc) {

@@ -1,4 +1,8 @@
 // Internal to the host side of the C-ABI (api*.hip), not part of the ABI: an accel's state and what more than one of those files needs.
+// Ownership: every device or pinned allocation and every event of an accel is a member of rtk_accel (or of a struct it holds) of
+// one of dev_mem.hpp's owning types, over the three memory sources below; they free themselves when the accel is deleted.  A new
+// buffer is one field here and one reserve() where it is used.  The structs the kernels take by value (dev::TreeView,
+// dev::RenderArgs, dev::StreamWs, StreamSide ...) stay plain and are filled from the owners.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +15,7 @@
 #include "kernels.hpp"
 #include "stream.hpp"
 #include "build.hpp"
+#include "dev_mem.hpp"
 
 // Environment knobs (all optional).  Read ONCE, when an accel is built: nothing on the launch path
 // calls getenv.
@@ -95,34 +100,81 @@ struct rtk_knobs {
     }
 };
 
+namespace rtk {
+// The three real memory sources of dev_mem.hpp.  Nothing else in the C-ABI files allocates, frees, or makes an event.
+struct DeviceMem {
+    static int alloc(void **p, size_t bytes) { return int(hipMalloc(p, bytes)); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static int alloc(void **p, size_t bytes) { return int(hipHostMalloc(p, bytes, hipHostMallocDefault)); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <unsigned Flags> struct EventSrc {
+    using handle = hipEvent_t;
+    static int create(handle *h) { return int(Flags == hipEventDefault ? hipEventCreate(h) : hipEventCreateWithFlags(h, Flags)); }
+    static void destroy(handle h) { (void)hipEventDestroy(h); }
+};
+template <typename T> using DevBuf = Buf<T, DeviceMem>;
+template <typename T> using PinBuf = Buf<T, PinnedMem>;
+using DevEvent = Event<EventSrc<hipEventDisableTiming>>;
+using TimedEvent = Event<EventSrc<hipEventDefault>>;
+
+// The geometry of an accel exists twice, as two values of this struct: an update builds into the spare one and swaps it with
+// the active one at the end, so a failed update leaves the accel as it was and a steady animation allocates nothing.
+struct GeomBufs {
+    DevBuf<DevNode> nodes, leaves;
+    DevBuf<DevNode> leaves_fast;              // RTK_TRAVERSAL_FAST: 8 front-to-back orders of the leaves (empty in the parity mode)
+    DevBuf<DevTri> tris;
+    DevBuf<uint32_t> tri_ids;
+    DevBuf<DevShade> shade;
+    DevBuf<int32_t> leaf_refs;                // leaf_refs in reference order, written by the device build
+    // RTK_TRAVERSAL_FAST on a scene with transmissive materials: the tree again with the opaque triangles only (occlusion queries, k_shadow)
+    DevBuf<DevNode> occl_nodes, occl_leaves;
+    DevBuf<DevTri> occl_tris;
+    DevBuf<uint32_t> occl_ids;
+    void swap_occl(GeomBufs &o) { occl_nodes.swap(o.occl_nodes); occl_leaves.swap(o.occl_leaves); occl_tris.swap(o.occl_tris); occl_ids.swap(o.occl_ids); }
+    void swap(GeomBufs &o, bool fast, bool occl) {
+        nodes.swap(o.nodes); leaves.swap(o.leaves); tris.swap(o.tris); tri_ids.swap(o.tri_ids); shade.swap(o.shade); leaf_refs.swap(o.leaf_refs);
+        if (fast) leaves_fast.swap(o.leaves_fast);
+        if (occl) swap_occl(o);
+    }
+};
+// Likewise the topology tables of an update (vertex ids per triangle, incidence lists, opaque flags, per-triangle uvs), which
+// rtk_accel_update_geometry replaces.
+struct TopoBufs {
+    DevBuf<uint32_t> index, inc_off, inc;
+    DevBuf<uint8_t> opaque;
+    DevBuf<DevTriUv> tri_uv;
+    void swap(TopoBufs &o, bool uv) { index.swap(o.index); inc_off.swap(o.inc_off); inc.swap(o.inc); opaque.swap(o.opaque); if (uv) tri_uv.swap(o.tri_uv); }
+};
+// the queues of one lane of the streaming pipeline: what a dev::StreamWs points into
+struct StreamBufs {
+    DevBuf<dev::RayRec> rays;
+    DevBuf<dev::NodeRes> nodes;
+    DevBuf<dev::HitRec> hits;
+    DevBuf<float2> contrib;
+    DevBuf<uint32_t> ctrl, node_bins, hit_bins, node_order, hit_order;
+    void reset() { rays.reset(); nodes.reset(); hits.reset(); contrib.reset(); ctrl.reset(); node_bins.reset(); hit_bins.reset(); node_order.reset(); hit_order.reset(); }
+};
+}  // namespace rtk
+
 // Per-pixel-block cost of the last frame of shape `sig`, and the launch order made from it.
 struct rtk_cost_feedback {
-    uint32_t *cost = nullptr, *order = nullptr;
-    uint8_t *bins = nullptr;
+    rtk::DevBuf<uint32_t> cost, order;
+    rtk::DevBuf<uint8_t> bins;
     size_t units = 0;
     uint64_t sig[5] = {0, 0, 0, 0, 0};
     bool valid = false;              // cost holds the costs of a frame of shape sig
     bool order_valid = false;        // order was made from such costs
     unsigned age = 0;                // frames rendered with the current order
     // number of workgroups in order's workgroup list, read back behind the sort that made it (pinned host word + event)
-    uint32_t *nwgs_host = nullptr;
-    hipEvent_t nwgs_ev = nullptr;
+    rtk::PinBuf<uint32_t> nwgs_host;
+    rtk::DevEvent nwgs_ev;
     bool nwgs_pending = false, nwgs_known = false;
 
     void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; }
-    void release() {
-        (void)hipFree(cost); (void)hipFree(order); (void)hipFree(bins);
-        if (nwgs_ev) (void)hipEventDestroy(nwgs_ev);
-        if (nwgs_host) (void)hipHostFree(nwgs_host);
-        *this = rtk_cost_feedback();
-    }
 };
-
-namespace rtk {
-enum { G_NODES, G_LEAVES, G_FAST, G_TRIS, G_IDS, G_SHADE, G_LREFS, G_ONODES, G_OLEAVES, G_OTRIS, G_OIDS, kGeomBufs };
-// the topology tables of an update (up_index, up_inc_off, up_inc, up_opaque, d_tri_uv), which rtk_accel_update_geometry replaces
-enum { T_INDEX, T_INC_OFF, T_INC, T_OPAQUE, T_TRI_UV, kTopoBufs };
-}
 
 struct rtk_accel {
     rtk_knobs knobs;
@@ -140,42 +192,39 @@ struct rtk_accel {
     // ---- device residency (api.hip ensure_device; lazy: built on first compute call so host-only use needs no GPU)
     bool on_device = false;
     int device = -1;
-    rtk::DevNode *d_nodes = nullptr;
-    rtk::DevNode *d_leaves = nullptr;
-    rtk::DevNode *d_leaves_fast = nullptr;    // RTK_TRAVERSAL_FAST: 8 front-to-back orders of the leaves (null in the parity mode)
-    rtk::DevTri *d_tris = nullptr;
-    uint32_t *d_tri_ids = nullptr;
-    rtk::DevShade *d_shade = nullptr;
-    rtk::DevMaterial *d_materials = nullptr;
-    rtk::DevLight *d_lights = nullptr;
-    rtk::DevTexture *d_textures = nullptr;
-    rtk::DevTriUv *d_tri_uv = nullptr;
-    uint8_t *d_tex_pixels = nullptr;
-    unsigned long long *d_counters = nullptr;     // 8 x u64 in rtk_counters order + kRayCounterShards ray-count shards
-    // RTK_TRAVERSAL_FAST on a scene with transmissive materials: the tree again with the opaque triangles only (occlusion queries, k_shadow)
-    rtk::DevNode *d_occl_nodes = nullptr, *d_occl_leaves = nullptr;
-    rtk::DevTri *d_occl_tris = nullptr;
-    uint32_t *d_occl_ids = nullptr;
+    // the members below free themselves; the body only selects the device they live on (it runs before they are destroyed).  An
+    // accel that never reached a device holds nothing and makes no HIP call here.
+    ~rtk_accel() { if (device >= 0) (void)hipSetDevice(device); }
+    rtk::GeomBufs geom, geom_spare;   // active / spare (api_update.hip)
+    rtk::DevBuf<rtk::DevMaterial> d_materials;
+    rtk::DevBuf<rtk::DevLight> d_lights;           // its capacity is the rows it has room for: grows with head room, never shrinks
+    rtk::DevBuf<rtk::DevTexture> d_textures;
+    rtk::DevBuf<uint8_t> d_tex_pixels;
+    rtk::DevBuf<unsigned long long> d_counters;    // 8 x u64 in rtk_counters order + kRayCounterShards ray-count shards
     uint32_t occl_n_leaves = 0;
     bool occl_on = false;
     // ---- ws_* / lane_*: streaming-pipeline workspace (api_frame.hip ensure_stream_ws; grown on demand)
-    // one per sample lane (stream.hpp kStreamLanes); `ws` = lane 0; all lanes share lane 0's sumbuf
-    rtk::dev::StreamWs ws = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};
+    // one per sample lane (stream.hpp kStreamLanes); `ws` = lane 0; all lanes share lane 0's sumbuf.  ws_bufs / ws_sumbuf own the
+    // memory, ws / ws_lane are the views of it that the kernels take by value.
+    rtk::StreamBufs ws_bufs[rtk::dev::kStreamLanes];
+    rtk::DevBuf<float> ws_sumbuf;
+    rtk::dev::StreamWs ws = {};
     rtk::dev::StreamWs ws_lane[rtk::dev::kStreamLanes] = {};
     int ws_lanes = 0;
     size_t ws_pixels = 0, ws_lights = 0, ws_nodes = 0;
     bool ws_sum = false;
-    hipStream_t lane_stream[rtk::dev::kStreamLanes] = {};
-    hipEvent_t lane_done[rtk::dev::kStreamLanes] = {};
-    hipEvent_t lane_fork = nullptr;
-    rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane
+    hipStream_t lane_stream[rtk::dev::kStreamLanes] = {};       // the process's (api_frame.hip LaneStreams): not freed with an accel
+    rtk::DevEvent lane_done[rtk::dev::kStreamLanes];
+    rtk::DevEvent lane_fork;
+    struct SideEvents { rtk::DevEvent ready[2], done[2]; } lane_side_ev[rtk::dev::kStreamLanes];
+    rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane (the process's) and views of lane_side_ev
     // the streaming workspace's last user (a STREAM frame or a radiance batch) recorded ws_done: the next one on any stream waits for it
-    hipEvent_t ws_done = nullptr;
+    rtk::DevEvent ws_done;
     bool ws_in_use = false;
     // ---- tp_*: two-pass workspace (api_frame.hip ensure_twopass_ws)
-    float4 *tp_prim = nullptr;
-    uint32_t *tp_bins = nullptr;       // [kCostBins] counts, [1] n_listed
-    uint32_t *tp_bin_list = nullptr, *tp_order = nullptr;
+    rtk::DevBuf<float4> tp_prim;
+    rtk::DevBuf<uint32_t> tp_bins;     // [kCostBins] counts, [1] n_listed
+    rtk::DevBuf<uint32_t> tp_bin_list, tp_order;
     size_t tp_pixels = 0, tp_tiles = 0;
     // ---- fb / fb_views: cost feedback (megakernel frames, api_frame.hip render_megakernel).  Frames have one set of tables;
     // rtk_render_views has one per launch of a call (a call is cut into launches of whole views), so that a caller who
@@ -183,11 +232,9 @@ struct rtk_accel {
     rtk_cost_feedback fb;
     std::vector<rtk_cost_feedback> fb_views;
     // ---- views_*: rtk_render_views (api_frame.hip).  The host variant's staging (view table, output) grows and never shrinks.
-    float *views_tab = nullptr;
-    size_t views_tab_cap = 0;                  // views
-    float *views_out = nullptr;
-    size_t views_out_cap = 0;                  // floats
-    unsigned long long *d_views_counters = nullptr;   // [kCounterWords] the call's totals while its frames / launches run
+    rtk::DevBuf<rtk_view> views_tab;
+    rtk::DevBuf<float> views_out;
+    rtk::DevBuf<unsigned long long> d_views_counters;   // [kCounterWords] the call's totals while its frames / launches run
     // ---- rg_* / fb_regions: rtk_render_regions (api_frame.hip).  One set of cost tables per launch of a call, as for views; they are
     // reused only by a call whose rectangle list, layout and frame width equal the previous call's (rg_rects, rg_layout, rg_width), and
     // then the table on the device is that call's too and is not uploaded again.
@@ -197,86 +244,66 @@ struct rtk_accel {
     int rg_layout = -1;
     uint32_t rg_width = 0;
     size_t rg_limit = 0;                       // the launch limit the table on the device was cut with
-    rtk::RegionEntry *rg_table = nullptr;      // the entries of all launches of the call, one behind the other
-    size_t rg_table_cap = 0;                   // entries
+    rtk::DevBuf<rtk::RegionEntry> rg_table;    // the entries of all launches of the call, one behind the other
     bool rg_table_valid = false;               // rg_table holds the plan of rg_rects
-    hipEvent_t rg_done = nullptr;              // recorded behind a call's last kernel: the next table upload, on any stream, waits for it
+    rtk::DevEvent rg_done;                     // recorded behind a call's last kernel: the next table upload, on any stream, waits for it
     bool rg_in_use = false;
-    rtk_ray *rg_rays = nullptr;                // streaming path: rays, frame pixel indices and colours of one chunk of pixels
-    uint32_t *rg_ids = nullptr;
-    float *rg_rgb = nullptr;
-    size_t rg_cap = 0;                         // pixels
-    float *rg_out = nullptr;                   // staging of the host variant
-    size_t rg_out_cap = 0;                     // floats
+    rtk::DevBuf<rtk_ray> rg_rays;              // streaming path: rays, frame pixel indices and colours of one chunk of pixels
+    rtk::DevBuf<uint32_t> rg_ids;
+    rtk::DevBuf<float> rg_rgb;
+    rtk::DevBuf<float> rg_out;                 // staging of the host variant
     // ---- trial_*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
-    hipEvent_t trial_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    rtk::TimedEvent trial_ev[4];
     uint64_t trial_sig[3] = {0, 0, 0};
     int trial_state = 0;
     // ---- rp_*: ray repacking workspace (batched intersect: api_batch.hip, repack.hip)
-    uint32_t *rp_bounds = nullptr, *rp_keys = nullptr, *rp_idx = nullptr;
-    void *rp_temp = nullptr;
-    size_t rp_temp_bytes = 0, rp_cap = 0;
-    uint32_t *rp_host = nullptr;     // pinned: the probe's words as the host sees them
-    hipEvent_t rp_probe_ev = nullptr;
-    hipEvent_t rp_done = nullptr;    // recorded behind the k_intersect that walks rp_idx: the next repack on any stream waits for it
+    rtk::DevBuf<uint32_t> rp_bounds, rp_keys, rp_idx;
+    rtk::DevBuf<uint8_t> rp_temp;
+    size_t rp_temp_bytes = 0;
+    rtk::PinBuf<uint32_t> rp_host;   // pinned: the probe's words as the host sees them
+    rtk::DevEvent rp_probe_ev;
+    rtk::DevEvent rp_done;           // recorded behind the k_intersect that walks rp_idx: the next repack on any stream waits for it
     bool rp_in_use = false;
     // ---- oc_*: staging of the host variant of the occlusion batch (rtk_accel_occluded, api_batch.hip): grows, never shrinks
-    rtk_ray *oc_rays = nullptr;
-    float *oc_max_t = nullptr;
-    uint8_t *oc_out = nullptr;
-    size_t oc_cap = 0;
+    rtk::DevBuf<rtk_ray> oc_rays;
+    rtk::DevBuf<float> oc_max_t;
+    rtk::DevBuf<uint8_t> oc_out;
     // ---- rad_*: batched radiance (rtk_accel_radiance, api_frame.hip)
     // one kCounterWords block per lane for a chunk's pipeline, then {rays, chunks redone} of the call
-    unsigned long long *d_rad_counters = nullptr;
+    rtk::DevBuf<unsigned long long> d_rad_counters;
     // staging of the host variant: grows, never shrinks
-    rtk_ray *rad_rays = nullptr;
-    uint32_t *rad_ids = nullptr;
-    float *rad_rgb = nullptr;
-    size_t rad_cap = 0;
-    // ---- up_*: rtk_accel_update_vertices (api_update.hip, build.hip).  The geometry buffers exist twice: an update builds into
-    // the spare set and swaps it with the active one (d_nodes ... d_occl_ids, d_leaf_refs) at the end, so a failed update leaves
-    // the accel as it was and a steady animation allocates nothing.  Capacities in bytes; buffers grow, never shrink.
-    void *spare[rtk::kGeomBufs] = {};
-    size_t spare_cap[rtk::kGeomBufs] = {}, active_cap[rtk::kGeomBufs] = {};
-    int32_t *d_leaf_refs = nullptr;            // leaf_refs in reference order, written by the device build
+    rtk::DevBuf<rtk_ray> rad_rays;
+    rtk::DevBuf<uint32_t> rad_ids;
+    rtk::DevBuf<float> rad_rgb;
+    // ---- up_*: rtk_accel_update_vertices (api_update.hip, build.hip): scratch of a build; buffers grow, never shrink
     bool refs_on_device = false;               // tree.leaf_refs (and every per-triangle host array) lives on the device only
     int32_t n_leaf_refs_dev = 0;
-    bool up_static = false;                    // the tables of the current topology below are made
-    uint32_t *up_index = nullptr, *up_inc_off = nullptr, *up_inc = nullptr;
-    uint8_t *up_opaque = nullptr;
-    float *up_verts = nullptr;                 // staging of the host variant
-    rtk::DevTri *up_tris = nullptr;            // per triangle: scratch of a build, grows with the triangle count
-    float *up_tbox = nullptr;
-    size_t up_tris_cap = 0, up_tbox_cap = 0;   // bytes
-    // ---- topo_*: rtk_accel_update_geometry (api_update.hip, topology.hip).  The topology tables exist twice like the geometry:
-    // the new ones are made on the device into the spare set (with d_tri_uv, and mesh / material in the spare shading records)
-    // and swapped in with it.  The counts per mesh are numbers: the host arrays they came from are dropped by the updates.
+    bool up_static = false;                    // the tables of the current topology (topo) are made
+    rtk::TopoBufs topo, topo_spare;            // active / spare; topo.tri_uv is the scene's from ensure_device on
+    rtk::DevBuf<float> up_verts;               // staging of the host variant
+    rtk::DevBuf<rtk::DevTri> up_tris;          // per triangle: scratch of a build, grows with the triangle count
+    rtk::DevBuf<float> up_tbox;
+    // ---- topo_*: rtk_accel_update_geometry (api_update.hip, topology.hip).  The new tables are made on the device into topo_spare
+    // (with tri_uv, and mesh / material in the spare shading records) and swapped in with the geometry.  The counts per mesh are
+    // numbers: the host arrays they came from are dropped by the updates.
     std::vector<int32_t> mesh_nverts, mesh_ntris;
-    void *topo_spare[rtk::kTopoBufs] = {};
-    size_t topo_spare_cap[rtk::kTopoBufs] = {}, topo_active_cap[rtk::kTopoBufs] = {};
-    rtk::dev::TopoMesh *topo_meshes = nullptr; // [n_meshes + 1] the small per-mesh table of the call in flight
-    float *topo_vert_uv = nullptr;             // [n_vertices][2], zero for meshes without uvs; made once, with textures only
-    uint32_t *topo_keys = nullptr;             // the sorted vertex ids of the incidence sort
-    void *topo_temp = nullptr;                 // rocPRIM's
-    size_t topo_keys_cap = 0, topo_temp_cap = 0;
-    uint32_t *up_idx_stage = nullptr;          // staging of the host variant's indices
-    size_t up_idx_stage_cap = 0;
-    uint32_t *up_ref_id = nullptr, *up_ref_node = nullptr;
-    size_t up_cap_refs = 0, up_cap_nodes = 0;
-    uint8_t *up_table = nullptr, *up_table_host = nullptr;     // BuildHdr + BuildNode[up_cap_nodes]; the host copy is pinned
-    rtk::dev::GatherLeaf *up_gather = nullptr;
-    size_t up_gather_cap = 0;
-    uint8_t *up_stage = nullptr;               // pinned: the small tables on their way up
-    size_t up_stage_cap = 0;
-    hipEvent_t geom_ready = nullptr;           // recorded behind an update's last kernel: later work on any stream waits for it
+    rtk::DevBuf<rtk::dev::TopoMesh> topo_meshes;   // [n_meshes + 1] the small per-mesh table of the call in flight
+    rtk::DevBuf<float> topo_vert_uv;           // [n_vertices][2], zero for meshes without uvs; made once, with textures only
+    rtk::DevBuf<uint32_t> topo_keys;           // the sorted vertex ids of the incidence sort
+    rtk::DevBuf<uint8_t> topo_temp;            // rocPRIM's
+    rtk::DevBuf<uint32_t> up_idx_stage;        // staging of the host variant's indices
+    rtk::DevBuf<uint32_t> up_ref_id, up_ref_node;  // reference lists of a build: their capacity is the build's cap_refs
+    rtk::DevBuf<uint8_t> up_table;             // BuildHdr + BuildNode[cap_nodes], sized exactly
+    rtk::PinBuf<uint8_t> up_table_host;        // its pinned host copy
+    rtk::DevBuf<rtk::dev::GatherLeaf> up_gather;
+    rtk::PinBuf<uint8_t> up_stage;             // pinned: the small tables on their way up
+    rtk::DevEvent geom_ready;                  // recorded behind an update's last kernel: later work on any stream waits for it
     bool geom_pending = false;
     // ---- st_*: rtk_accel_set_lights / _set_materials (api_state.hip; the regather: api_update.hip, occluders.hip)
-    size_t lights_cap = 0;                     // rows d_lights has room for; grows with head room, never shrinks
     bool lights_on_device = false;             // rtk_accel_set_lights_device: scene.lights has the COUNT, the values are in d_lights
-    rtk::DevMaterial *st_materials = nullptr;  // the spare material table: written, read by the regather, then swapped with d_materials
-    rtk::dev::OcclLeaf *st_leaves = nullptr;   // one row per leaf of the active tree
-    uint32_t *st_counts = nullptr;             // opaque references per leaf
-    size_t st_leaves_cap = 0, st_counts_cap = 0;   // bytes
+    rtk::DevBuf<rtk::DevMaterial> st_materials;    // the spare material table: written, read by the regather, then swapped with d_materials
+    rtk::DevBuf<rtk::dev::OcclLeaf> st_leaves;     // one row per leaf of the active tree
+    rtk::DevBuf<uint32_t> st_counts;           // opaque references per leaf
     // ---- the last frame (rtk_render_last_counters, rtk_render_last_critical_path)
     hipStream_t last_stream = nullptr;
     uint64_t last_primary = 0;
@@ -300,12 +327,15 @@ inline int hip_fail(hipError_t e, const char *what) {
 #define RTK_HIP(call) RTK_HIP_AS(call, #call)
 #define RTK_TRY(call) do { const int rc_ = (call); if (rc_ != RTK_OK) return rc_; } while (0)   // an int status: RTK_OK or the caller's return
 
+#define RTK_MEM(call) RTK_HIP_AS(static_cast<hipError_t>(call), #call)                          // a status of dev_mem.hpp: a reserve(), an ensure()
+
+// `dst` afterwards holds a copy of src (room for one element if src is empty); what a failed earlier attempt left is reused or replaced
 template <typename T>
-int upload(const std::vector<T> &src, T **dst) {
-    *dst = nullptr;
-    const size_t bytes = (src.empty() ? 1 : src.size()) * sizeof(T);
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(dst), bytes));
-    if (!src.empty()) RTK_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(const std::vector<T> &src, DevBuf<T> &dst) {
+    RTK_MEM(dst.reserve(src.empty() ? 1 : src.size()));
+    if (src.empty()) return RTK_OK;
+    const hipError_t e = hipMemcpy(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { dst.reset(); return hip_fail(e, "upload"); }
     return RTK_OK;
 }
 
@@ -333,7 +363,6 @@ struct FrameGeom {
 int ensure_device(rtk_accel *a, hipStream_t s = nullptr);
 dev::TreeView tree_view(const rtk_accel *a);
 // api_update.hip
-int grow_dev(void **p, size_t *cap, size_t need);
 int ensure_update_common(rtk_accel *a);
 // What follows from a new material table on a RESIDENT accel whose device is idle: the per-triangle opaque flags the updates read,
 // and -- when the set of refractive materials changed -- the opaque-only occlusion tree of a RTK_TRAVERSAL_FAST accel, re-made

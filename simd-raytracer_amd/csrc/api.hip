@@ -17,8 +17,8 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
     if (a->on_device) {
         RTK_HIP(hipSetDevice(a->device));
         if (a->geom_pending) {
-            if (hipEventQuery(a->geom_ready) == hipSuccess) a->geom_pending = false;
-            else { (void)hipGetLastError(); RTK_HIP(hipStreamWaitEvent(s, a->geom_ready, 0)); }
+            if (hipEventQuery(a->geom_ready.get()) == hipSuccess) a->geom_pending = false;
+            else { (void)hipGetLastError(); RTK_HIP(hipStreamWaitEvent(s, a->geom_ready.get(), 0)); }
         }
         return RTK_OK;
     }
@@ -31,12 +31,14 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
     if (dev >= count) return fail(RTK_ERR_INVALID, "device ordinal out of range");
     RTK_HIP(hipSetDevice(dev));
     a->device = dev;
-    RTK_TRY(upload(a->tree.dev_nodes, &a->d_nodes));
-    RTK_TRY(upload(a->tree.dev_leaves, &a->d_leaves));
-    if (a->fast_traversal) RTK_TRY(upload(a->tree.dev_leaves_fast, &a->d_leaves_fast));
-    RTK_TRY(upload(a->tree.dev_tris, &a->d_tris));
-    RTK_TRY(upload(a->tree.dev_tri_ids, &a->d_tri_ids));
-    RTK_TRY(upload(a->tree.dev_shade, &a->d_shade));
+    // (a retry after a failure part-way finds what the first attempt uploaded in its buffers, and uploads into them again)
+    GeomBufs &G = a->geom;
+    RTK_TRY(upload(a->tree.dev_nodes, G.nodes));
+    RTK_TRY(upload(a->tree.dev_leaves, G.leaves));
+    if (a->fast_traversal) RTK_TRY(upload(a->tree.dev_leaves_fast, G.leaves_fast));
+    RTK_TRY(upload(a->tree.dev_tris, G.tris));
+    RTK_TRY(upload(a->tree.dev_tri_ids, G.tri_ids));
+    RTK_TRY(upload(a->tree.dev_shade, G.shade));
     if (a->fast_traversal && a->has_refractive && a->knobs.fast_occluders) {
         // occlusion through transmissive surfaces as ONE query against what is not transmissive (rtk.h, RTK_TRAVERSAL_FAST): the same
         // nodes, their leaves without the transmissive triangles; leaves left empty drop out of the leaf list
@@ -57,33 +59,33 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
         }
         if (tris.empty()) { tris.push_back(t.dev_tris.empty() ? DevTri{} : t.dev_tris[0]); ids.push_back(0u); }      // (nothing opaque: keep the pointers valid)
         if (leaves.empty()) { DevNode n = nodes.empty() ? DevNode{} : nodes[0]; n.a = 0u; n.b = 0u; leaves.push_back(n); }
-        RTK_TRY(upload(nodes, &a->d_occl_nodes));
-        RTK_TRY(upload(leaves, &a->d_occl_leaves));
-        RTK_TRY(upload(tris, &a->d_occl_tris));
-        RTK_TRY(upload(ids, &a->d_occl_ids));
+        RTK_TRY(upload(nodes, G.occl_nodes));
+        RTK_TRY(upload(leaves, G.occl_leaves));
+        RTK_TRY(upload(tris, G.occl_tris));
+        RTK_TRY(upload(ids, G.occl_ids));
         a->occl_n_leaves = uint32_t(leaves.size());
         a->occl_on = true;
     }
-    RTK_TRY(upload(a->scene.materials, &a->d_materials));
-    RTK_TRY(upload(a->scene.lights, &a->d_lights));
-    a->lights_cap = a->scene.lights.empty() ? 1 : a->scene.lights.size();
+    RTK_TRY(upload(a->scene.materials, a->d_materials));
+    RTK_TRY(upload(a->scene.lights, a->d_lights));
     if (!a->scene.textures.empty()) {
-        RTK_TRY(upload(a->scene.textures, &a->d_textures));
-        RTK_TRY(upload(a->tree.dev_tri_uv, &a->d_tri_uv));
-        if (!a->scene.tex_pixels.empty()) RTK_TRY(upload(a->scene.tex_pixels, &a->d_tex_pixels));
+        RTK_TRY(upload(a->scene.textures, a->d_textures));
+        RTK_TRY(upload(a->tree.dev_tri_uv, a->topo.tri_uv));
+        if (!a->scene.tex_pixels.empty()) RTK_TRY(upload(a->scene.tex_pixels, a->d_tex_pixels));
     }
     // (+ 4 words behind the counters: the six cursors of the first-frame prior, zeroed by the same fill as the counters)
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_counters), (kCounterWords + 4) * sizeof(unsigned long long)));
-    RTK_HIP(hipMemset(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long)));
+    RTK_MEM(a->d_counters.reserve(kCounterWords + 4));
+    RTK_HIP(hipMemset(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long)));
     a->on_device = true;
     return RTK_OK;
 }
 
 dev::TreeView tree_view(const rtk_accel *a) {
     dev::TreeView t;
-    t.nodes = a->d_nodes; t.tris = a->d_tris; t.tri_ids = a->d_tri_ids; t.shade = a->d_shade;
-    t.leaves = a->d_leaves; t.n_leaves = static_cast<uint32_t>(a->tree.dev_leaves.size());
-    t.leaves_fast = a->fast_traversal ? a->d_leaves_fast : nullptr;
+    const GeomBufs &G = a->geom;
+    t.nodes = G.nodes.get(); t.tris = G.tris.get(); t.tri_ids = G.tri_ids.get(); t.shade = G.shade.get();
+    t.leaves = G.leaves.get(); t.n_leaves = static_cast<uint32_t>(a->tree.dev_leaves.size());
+    t.leaves_fast = a->fast_traversal ? G.leaves_fast.get() : nullptr;
     t.n_nodes = static_cast<uint32_t>(a->tree.dev_nodes.size());
     t.eps = a->params.eps;
     t.normalize = a->params.normalize_hit_normal;
@@ -319,8 +321,8 @@ int rtk_accel_tree_dump(const rtk_accel *a, float *nodes_box, int32_t *nodes_lin
         // the device build wrote them (build.hip, k_build_gather): fetched when someone asks
         if (a->n_leaf_refs_dev > 0) {
             RTK_HIP(hipSetDevice(a->device));
-            RTK_HIP(hipEventSynchronize(a->geom_ready));
-            RTK_HIP(hipMemcpy(leaf_refs, a->d_leaf_refs, size_t(a->n_leaf_refs_dev) * sizeof(int32_t), hipMemcpyDeviceToHost));
+            RTK_HIP(hipEventSynchronize(a->geom_ready.get()));
+            RTK_HIP(hipMemcpy(leaf_refs, a->geom.leaf_refs.get(), size_t(a->n_leaf_refs_dev) * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
     } else if (leaf_refs && !a->tree.leaf_refs.empty())
         std::memcpy(leaf_refs, a->tree.leaf_refs.data(), a->tree.leaf_refs.size() * sizeof(int32_t));
@@ -329,49 +331,7 @@ int rtk_accel_tree_dump(const rtk_accel *a, float *nodes_box, int32_t *nodes_lin
 
 void rtk_accel_destroy(rtk_accel *a) {
     if (!a) return;
-    if (a->on_device) {
-        (void)hipSetDevice(a->device);
-        (void)hipFree(a->d_nodes); (void)hipFree(a->d_leaves); (void)hipFree(a->d_tris); (void)hipFree(a->d_tri_ids); (void)hipFree(a->d_shade);
-        (void)hipFree(a->d_materials); (void)hipFree(a->d_lights); (void)hipFree(a->d_counters);
-        (void)hipFree(a->d_textures); (void)hipFree(a->d_tri_uv); (void)hipFree(a->d_tex_pixels); (void)hipFree(a->d_leaves_fast);
-        (void)hipFree(a->d_occl_nodes); (void)hipFree(a->d_occl_leaves); (void)hipFree(a->d_occl_tris); (void)hipFree(a->d_occl_ids);
-        (void)hipFree(a->d_leaf_refs);
-        (void)hipFree(a->st_materials); (void)hipFree(a->st_leaves); (void)hipFree(a->st_counts);
-        for (void *p : a->spare) (void)hipFree(p);
-        (void)hipFree(a->up_index); (void)hipFree(a->up_inc_off); (void)hipFree(a->up_inc); (void)hipFree(a->up_opaque); (void)hipFree(a->up_verts);
-        (void)hipFree(a->up_tris); (void)hipFree(a->up_tbox); (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);
-        (void)hipFree(a->up_table); (void)hipFree(a->up_gather);
-        for (void *p : a->topo_spare) (void)hipFree(p);
-        (void)hipFree(a->topo_meshes); (void)hipFree(a->topo_vert_uv); (void)hipFree(a->topo_keys); (void)hipFree(a->topo_temp); (void)hipFree(a->up_idx_stage);
-        if (a->up_table_host) (void)hipHostFree(a->up_table_host);
-        if (a->up_stage) (void)hipHostFree(a->up_stage);
-        if (a->geom_ready) (void)hipEventDestroy(a->geom_ready);
-        free_stream_ws(a);
-        // (the lane and side streams are the process's: LaneStreams)
-        for (auto &e : a->lane_done) if (e) (void)hipEventDestroy(e);
-        if (a->lane_fork) (void)hipEventDestroy(a->lane_fork);
-        for (auto &sd : a->lane_side)
-            for (int par = 0; par < 2; ++par) {
-                if (sd.ready[par]) (void)hipEventDestroy(sd.ready[par]);
-                if (sd.done[par]) (void)hipEventDestroy(sd.done[par]);
-            }
-        (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
-        (void)hipFree(a->rp_bounds); (void)hipFree(a->rp_keys); (void)hipFree(a->rp_idx); (void)hipFree(a->rp_temp);
-        a->fb.release();
-        for (rtk_cost_feedback &f : a->fb_views) f.release();
-        for (rtk_cost_feedback &f : a->fb_regions) f.release();
-        (void)hipFree(a->rg_table); (void)hipFree(a->rg_rays); (void)hipFree(a->rg_ids); (void)hipFree(a->rg_rgb); (void)hipFree(a->rg_out);
-        if (a->rg_done) (void)hipEventDestroy(a->rg_done);
-        (void)hipFree(a->views_tab); (void)hipFree(a->views_out); (void)hipFree(a->d_views_counters);
-        (void)hipFree(a->oc_rays); (void)hipFree(a->oc_max_t); (void)hipFree(a->oc_out);
-        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb); (void)hipFree(a->d_rad_counters);
-        if (a->ws_done) (void)hipEventDestroy(a->ws_done);
-        for (auto &e : a->trial_ev) if (e) (void)hipEventDestroy(e);
-        if (a->rp_done) (void)hipEventDestroy(a->rp_done);
-        if (a->rp_probe_ev) (void)hipEventDestroy(a->rp_probe_ev);
-        if (a->rp_host) (void)hipHostFree(a->rp_host);
-    }
-    delete a;
+    delete a;           // (~rtk_accel selects the device; the members free what they own)
 }
 
 // ---------------------------------------------------------------- image out

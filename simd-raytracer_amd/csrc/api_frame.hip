@@ -68,13 +68,8 @@ hipError_t lane_streams_for(int device, int lanes, LaneStreams **out) {
 }  // namespace
 
 void free_stream_ws(rtk_accel *a) {
-    (void)hipFree(a->ws.sumbuf);
-    for (int j = 0; j < dev::kStreamLanes; ++j) {
-        dev::StreamWs &w = a->ws_lane[j];
-        (void)hipFree(w.rays); (void)hipFree(w.nodes); (void)hipFree(w.hits); (void)hipFree(w.contrib); (void)hipFree(w.ctrl);
-        (void)hipFree(w.node_bins); (void)hipFree(w.hit_bins); (void)hipFree(w.node_order); (void)hipFree(w.hit_order);
-        w = dev::StreamWs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr, nullptr};
-    }
+    a->ws_sumbuf.reset();
+    for (int j = 0; j < dev::kStreamLanes; ++j) { a->ws_bufs[j].reset(); a->ws_lane[j] = dev::StreamWs{}; }
     a->ws = a->ws_lane[0];
     a->ws_lanes = 0; a->ws_pixels = 0; a->ws_nodes = 0; a->ws_lights = 0; a->ws_sum = false;
 }
@@ -94,28 +89,28 @@ int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, b
     RTK_HIP(hipDeviceSynchronize());
     free_stream_ws(a);
     const size_t nh = nn / 2 + 64;                            // every shading point belongs to a distinct node
-    float *sumbuf = nullptr;
-    if (sum) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&sumbuf), np * 3 * sizeof(float)));
+    if (sum) RTK_MEM(a->ws_sumbuf.reserve(np * 3));
     for (int j = 0; j < nlanes; ++j) {
-        dev::StreamWs &w = a->ws_lane[j];
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.rays), nn * sizeof(dev::RayRec)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.nodes), nn * sizeof(dev::NodeRes)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hits), nh * sizeof(dev::HitRec)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.contrib), nh * nl * sizeof(float2)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.ctrl), dev::kCtrlWords * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_bins), dev::kSortBins * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_bins), dev::kSortBins * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.node_order), nn * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&w.hit_order), nh * sizeof(uint32_t)));
-        w.sumbuf = sumbuf;
-        w.node_cap = uint32_t(nn); w.hit_cap = uint32_t(nh);
-        if (!a->lane_done[j]) RTK_HIP(hipEventCreateWithFlags(&a->lane_done[j], hipEventDisableTiming));
+        StreamBufs &b = a->ws_bufs[j];
+        RTK_MEM(b.rays.reserve(nn));
+        RTK_MEM(b.nodes.reserve(nn));
+        RTK_MEM(b.hits.reserve(nh));
+        RTK_MEM(b.contrib.reserve(nh * nl));
+        RTK_MEM(b.ctrl.reserve(dev::kCtrlWords));
+        RTK_MEM(b.node_bins.reserve(dev::kSortBins));
+        RTK_MEM(b.hit_bins.reserve(dev::kSortBins));
+        RTK_MEM(b.node_order.reserve(nn));
+        RTK_MEM(b.hit_order.reserve(nh));
+        a->ws_lane[j] = dev::StreamWs{b.rays.get(), b.nodes.get(), b.hits.get(), b.contrib.get(), a->ws_sumbuf.get(), b.ctrl.get(), uint32_t(nn), uint32_t(nh),
+                                      b.node_bins.get(), b.hit_bins.get(), b.node_order.get(), b.hit_order.get()};
+        RTK_MEM(a->lane_done[j].ensure());
         for (int par = 0; par < 2; ++par) {
-            if (!a->lane_side[j].ready[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].ready[par], hipEventDisableTiming));
-            if (!a->lane_side[j].done[par]) RTK_HIP(hipEventCreateWithFlags(&a->lane_side[j].done[par], hipEventDisableTiming));
+            RTK_MEM(a->lane_side_ev[j].ready[par].ensure());
+            RTK_MEM(a->lane_side_ev[j].done[par].ensure());
+            a->lane_side[j].ready[par] = a->lane_side_ev[j].ready[par].get(); a->lane_side[j].done[par] = a->lane_side_ev[j].done[par].get();
         }
     }
-    if (!a->lane_fork) RTK_HIP(hipEventCreateWithFlags(&a->lane_fork, hipEventDisableTiming));
+    RTK_MEM(a->lane_fork.ensure());
     LaneStreams *L = nullptr;                // the process's lane streams (see LaneStreams); the events that order them stay this accel's own
     RTK_HIP(lane_streams_for(a->device, nlanes, &L));
     for (int j = 0; j < nlanes; ++j) {
@@ -133,13 +128,11 @@ int ensure_twopass_ws(rtk_accel *a, size_t pixels, size_t tiles) {
     if (pixels <= a->tp_pixels && tiles <= a->tp_tiles) return RTK_OK;
     const size_t np = pixels > a->tp_pixels ? pixels : a->tp_pixels, nt = tiles > a->tp_tiles ? tiles : a->tp_tiles;
     RTK_HIP(hipDeviceSynchronize());
-    (void)hipFree(a->tp_prim); (void)hipFree(a->tp_bins); (void)hipFree(a->tp_bin_list); (void)hipFree(a->tp_order);
-    a->tp_prim = nullptr; a->tp_bins = nullptr; a->tp_bin_list = nullptr; a->tp_order = nullptr;
     a->tp_pixels = 0; a->tp_tiles = 0;
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_prim), np * sizeof(float4)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bins), (kCostBins + 1) * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_bin_list), size_t(kCostBins) * nt * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->tp_order), nt * sizeof(uint32_t)));
+    RTK_MEM(a->tp_prim.reserve(np));
+    RTK_MEM(a->tp_bins.reserve(kCostBins + 1));
+    RTK_MEM(a->tp_bin_list.reserve(size_t(kCostBins) * nt));
+    RTK_MEM(a->tp_order.reserve(nt));
     a->tp_pixels = np; a->tp_tiles = nt;
     return RTK_OK;
 }
@@ -169,8 +162,8 @@ dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
     dev::RenderArgs A;
     std::memset(&A, 0, sizeof(A));
     A.tree = tree_view(a);
-    A.materials = a->d_materials; A.lights = a->d_lights;
-    A.textures = a->d_textures; A.tri_uv = a->d_tri_uv; A.tex_pixels = a->d_tex_pixels;
+    A.materials = a->d_materials.get(); A.lights = a->d_lights.get();
+    A.textures = a->d_textures.get(); A.tri_uv = a->topo.tri_uv.get(); A.tex_pixels = a->d_tex_pixels.get();
     A.n_lights = int(a->scene.lights.size());
     A.has_refractive = a->has_refractive ? 1 : 0;
     std::memcpy(A.background, a->scene.background, sizeof(A.background));
@@ -185,8 +178,8 @@ dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
     A.occl_on = (a->occl_on && stats_mode == 0) ? 1 : 0;
     A.occl = A.tree;
     if (A.occl_on) {
-        A.occl.nodes = a->d_occl_nodes; A.occl.leaves = a->d_occl_leaves; A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
-        A.occl.tris = a->d_occl_tris; A.occl.tri_ids = a->d_occl_ids;
+        A.occl.nodes = a->geom.occl_nodes.get(); A.occl.leaves = a->geom.occl_leaves.get(); A.occl.leaves_fast = nullptr; A.occl.n_leaves = a->occl_n_leaves;
+        A.occl.tris = a->geom.occl_tris.get(); A.occl.tri_ids = a->geom.occl_ids.get();
     }
     return A;
 }
@@ -249,22 +242,22 @@ StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffus
 
 // the queues belong to the accel: whoever used them last (a STREAM frame, a batch on another stream) finishes first, on the device
 int claim_stream_ws(rtk_accel *a, hipStream_t s) {
-    if (!a->ws_done) RTK_HIP(hipEventCreateWithFlags(&a->ws_done, hipEventDisableTiming));
-    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done, 0));
+    RTK_MEM(a->ws_done.ensure());
+    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done.get(), 0));
     a->ws_in_use = true;
     return RTK_OK;
 }
-int release_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(hipEventRecord(a->ws_done, s)); return RTK_OK; }
+int release_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(hipEventRecord(a->ws_done.get(), s)); return RTK_OK; }
 
 // fork: lane 0 is the caller's stream, the other lanes wait for everything enqueued on it so far
 int fork_lanes(rtk_accel *a, int lanes, hipStream_t s) {
-    if (lanes > 1) RTK_HIP(hipEventRecord(a->lane_fork, s));
-    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork, 0));
+    if (lanes > 1) RTK_HIP(hipEventRecord(a->lane_fork.get(), s));
+    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(a->lane_stream[j], a->lane_fork.get(), 0));
     return RTK_OK;
 }
 // join: the caller's stream continues behind the last launch of every lane
 int join_lanes(rtk_accel *a, int lanes, hipStream_t s) {
-    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j], 0));
+    for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j].get(), 0));
     return RTK_OK;
 }
 
@@ -282,19 +275,19 @@ int choose_engine(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, 
                                   (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays)};
         if (std::memcmp(tsig, a->trial_sig, sizeof(tsig)) != 0) { std::memcpy(a->trial_sig, tsig, sizeof(tsig)); a->trial_state = 0; }
         if (a->knobs.auto_trials) {
-            if (!a->trial_ev[0]) for (auto &e : a->trial_ev) RTK_HIP(hipEventCreate(&e));
+            for (TimedEvent &e : a->trial_ev) RTK_MEM(e.ensure());
             if (a->trial_state == 3) {                                      // both timed: is the verdict in?
                 float t_stream = 0.f, t_mega = 0.f;
-                if (hipEventQuery(a->trial_ev[1]) == hipSuccess && hipEventQuery(a->trial_ev[3]) == hipSuccess &&
-                    hipEventElapsedTime(&t_stream, a->trial_ev[0], a->trial_ev[1]) == hipSuccess &&
-                    hipEventElapsedTime(&t_mega, a->trial_ev[2], a->trial_ev[3]) == hipSuccess)
+                if (hipEventQuery(a->trial_ev[1].get()) == hipSuccess && hipEventQuery(a->trial_ev[3].get()) == hipSuccess &&
+                    hipEventElapsedTime(&t_stream, a->trial_ev[0].get(), a->trial_ev[1].get()) == hipSuccess &&
+                    hipEventElapsedTime(&t_mega, a->trial_ev[2].get(), a->trial_ev[3].get()) == hipSuccess)
                     a->trial_state = t_mega < t_stream ? 5 : 4;
                 else (void)hipGetLastError();                               // not ready yet: clear the sticky "not ready"
             }
             switch (a->trial_state) {
-                case 0: stream = true; trial[0] = a->trial_ev[0]; trial[1] = a->trial_ev[1]; a->trial_state = 1; break;
+                case 0: stream = true; trial[0] = a->trial_ev[0].get(); trial[1] = a->trial_ev[1].get(); a->trial_state = 1; break;
                 case 1: stream = false; a->trial_state = 2; break;          // first megakernel frame: records the block costs
-                case 2: stream = false; trial[0] = a->trial_ev[2]; trial[1] = a->trial_ev[3]; a->trial_state = 3; break;
+                case 2: stream = false; trial[0] = a->trial_ev[2].get(); trial[1] = a->trial_ev[3].get(); a->trial_state = 3; break;
                 case 5: stream = false; break;
                 default: stream = true; break;                              // 3 (waiting for the events), 4 (pipeline won)
             }
@@ -307,8 +300,8 @@ int render_twopass(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g,
     if (p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
     const size_t tiles = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
     RTK_TRY(ensure_twopass_ws(a, out_pixels(g), tiles));
-    A.prim = a->tp_prim; A.bin_count = a->tp_bins; A.n_listed = a->tp_bins + kCostBins; A.bin_list = a->tp_bin_list;
-    A.tile_order = a->tp_order; A.tile_cap = uint32_t(a->tp_tiles);
+    A.prim = a->tp_prim.get(); A.bin_count = a->tp_bins.get(); A.n_listed = a->tp_bins.get() + kCostBins; A.bin_list = a->tp_bin_list.get();
+    A.tile_order = a->tp_order.get(); A.tile_cap = uint32_t(a->tp_tiles);
     RTK_HIP_AS(launch_twopass(A, p->collect_stats != 0, general, s), "launch two-pass frame");
     return RTK_OK;
 }
@@ -347,8 +340,8 @@ int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, 
         S.ws = a->ws_lane[j];
         const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
         // ordering events: the depth-0 k_combine of a batch waits for the previous batch's, so the pixel sums stay in sample order
-        const hipEvent_t wait = (lanes > 1 && i > 0) ? a->lane_done[(i - 1) % lanes] : nullptr;
-        const hipEvent_t done = lanes > 1 ? a->lane_done[j] : nullptr;
+        const hipEvent_t wait = (lanes > 1 && i > 0) ? a->lane_done[(i - 1) % lanes].get() : nullptr;
+        const hipEvent_t done = lanes > 1 ? a->lane_done[j].get() : nullptr;
         RTK_HIP_AS(launch_stream_sample(S, p->collect_stats != 0, u.deep_level, u.deep_mode, u.sort_from, ls, wait, done,
                                         side ? &a->lane_side[j] : nullptr, u.slices), "launch streaming pipeline");
     }
@@ -377,17 +370,16 @@ int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, 
 int ensure_feedback_ws(rtk_accel *a, rtk_cost_feedback &fb, const FrameGeom &g, size_t units) {
     if (fb.units >= units) return RTK_OK;
     // (the first allocation of the frames' tables also covers the scene's own frame size, so that a small frame
-    // rendered first -- a warm-up -- does not leave three hipMallocs, ~0.1 ms, in front of the first full-size frame)
+    // rendered first -- a warm-up -- does not leave three allocations, ~0.1 ms, in front of the first full-size frame)
     size_t cap = units;
     const uint32_t bk = g.bucket, bs = g.blocks_side;
     const uint64_t tx = (uint64_t(a->scene.width > 0 ? a->scene.width : 0) + bk - 1) / bk, ty = (uint64_t(a->scene.height > 0 ? a->scene.height : 0) + bk - 1) / bk;
     const uint64_t native = tx * ty * bs * bs;
     if (&fb == &a->fb && fb.units == 0 && native > cap && native <= (1ull << 24)) cap = size_t(native);
-    (void)hipFree(fb.cost); (void)hipFree(fb.order); (void)hipFree(fb.bins);
-    fb.cost = fb.order = nullptr; fb.bins = nullptr; fb.units = 0; fb.valid = false; fb.order_valid = false;
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&fb.cost), cap * sizeof(uint32_t)));
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&fb.order), (2 * cap + 4 + 8) * sizeof(uint32_t)));   // order, header, workgroup list, prior's counters
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&fb.bins), cap));
+    fb.units = 0; fb.valid = false; fb.order_valid = false;
+    RTK_MEM(fb.cost.reserve(cap));
+    RTK_MEM(fb.order.reserve(2 * cap + 4 + 8));                       // order, header, workgroup list, prior's counters
+    RTK_MEM(fb.bins.reserve(cap));
     fb.units = cap;
     return RTK_OK;
 }
@@ -417,8 +409,8 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
                                  A.regions ? ((1ull << 63) | (uint64_t(A.n_regions) << 32) | uint64_t(A.n_units))   // (its list is compared by the caller)
                                            : (A.views ? uint64_t(A.n_views) : 0ull)};   // (0: a frame; a views launch of one view is not one)
         RTK_TRY(ensure_feedback_ws(a, fb, g, units));
-        uint32_t *const order_hdr = fb.order + units, *const wg_list = fb.order + units + 4;
-        auto use_order = [&] { A.order_in = fb.order; A.order_hdr = order_hdr; A.wg_list = wg_list; };
+        uint32_t *const order = fb.order.get(), *const order_hdr = order + units, *const wg_list = order + units + 4;
+        auto use_order = [&] { A.order_in = order; A.order_hdr = order_hdr; A.wg_list = wg_list; };
         const bool same_shape = fb.valid && std::memcmp(sig, fb.sig, sizeof(sig)) == 0;
         if (!same_shape) fb.order_valid = false;
         // The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in for them
@@ -427,8 +419,8 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
         // (the first launch of a new rectangle list runs in the natural order: k_block_prior maps units through the buckets)
         const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0 && !A.regions;
         if (prior) {
-            RTK_HIP_AS(launch_block_prior(A, fb.bins, fb.order, wg_list, order_hdr,
-                                          reinterpret_cast<uint32_t *>(a->d_counters + kCounterWords), 4u, s), "launch k_block_prior");
+            RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), order, wg_list, order_hdr,
+                                          reinterpret_cast<uint32_t *>(a->d_counters.get() + kCounterWords), 4u, s), "launch k_block_prior");
             use_order();
         }
         if (same_shape) {
@@ -436,33 +428,31 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
             // ~28 us sit in front of the frame, and an order that is a few frames old is as good (costs move slowly).
             if (!fb.order_valid || fb.age >= a->knobs.resort_every) {
                 // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
-                RTK_HIP_AS(launch_order_by_cost(fb.cost, fb.bins, fb.order, wg_list, order_hdr, uint32_t(units),
+                RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), order, wg_list, order_hdr, uint32_t(units),
                                                 frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
                            "launch k_order_by_cost");
                 fb.order_valid = true;
                 fb.age = 0;
                 // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
-                if (!fb.nwgs_host) {
-                    RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&fb.nwgs_host), sizeof(uint32_t), hipHostMallocDefault));
-                    RTK_HIP(hipEventCreateWithFlags(&fb.nwgs_ev, hipEventDisableTiming));
-                }
+                RTK_MEM(fb.nwgs_host.reserve(1));
+                RTK_MEM(fb.nwgs_ev.ensure());
                 fb.nwgs_known = false;
-                RTK_HIP(hipMemcpyAsync(fb.nwgs_host, order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                RTK_HIP(hipEventRecord(fb.nwgs_ev, s));
+                RTK_HIP(hipMemcpyAsync(fb.nwgs_host.get(), order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                RTK_HIP(hipEventRecord(fb.nwgs_ev.get(), s));
                 fb.nwgs_pending = true;
             }
             fb.age += 1;
             use_order();
         }
-        A.cost_out = fb.cost;
+        A.cost_out = fb.cost.get();
         std::memcpy(fb.sig, sig, sizeof(sig));
         fb.valid = true;
     }
     unsigned n_wgs = 0;
-    if (A.wg_list != nullptr && A.order_in == fb.order && fb.order_valid) {
-        if (fb.nwgs_pending && hipEventQuery(fb.nwgs_ev) == hipSuccess) { fb.nwgs_pending = false; fb.nwgs_known = true; }
+    if (A.wg_list != nullptr && A.order_in == fb.order.get() && fb.order_valid) {
+        if (fb.nwgs_pending && hipEventQuery(fb.nwgs_ev.get()) == hipSuccess) { fb.nwgs_pending = false; fb.nwgs_known = true; }
         else if (fb.nwgs_pending) (void)hipGetLastError();            // not ready: clear the sticky status
-        if (fb.nwgs_known && !fb.nwgs_pending) n_wgs = *fb.nwgs_host;
+        if (fb.nwgs_known && !fb.nwgs_pending) n_wgs = *fb.nwgs_host.get();
     }
     RTK_HIP_AS(launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs), "launch k_render");
     return RTK_OK;
@@ -479,7 +469,7 @@ dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const
     A.bucket = g.bucket; A.tiles_x = g.tiles_x; A.tiles_y = g.tiles_y; A.n_buckets = g.n_buckets;
     A.blocks_per_bucket_side = g.blocks_side; A.buckets_per_rank = g.buckets_per_rank;
     A.rank = g.rank; A.world = g.world; A.compact = g.world > 1 ? 1 : 0; A.skew_q = g.skew_q;
-    A.out = d_out; A.counters = a->d_counters;
+    A.out = d_out; A.counters = a->d_counters.get();
     return A;
 }
 
@@ -491,7 +481,7 @@ int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
     // the megakernel comes in two builds: the lean one (diffuse / reflective / constant materials only) and the general one
     // (template FORKS: + refraction, diffuse GI, textures), so that the lean one does not carry the general one's registers
     const bool general = forks || !a->scene.textures.empty();
-    RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+    RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
     // buckets past the end of the frame (padding so that every rank has equal length) stay zero
     if (g.world > 1 && g.sample_begin == 0) RTK_HIP(hipMemsetAsync(d_out, 0, out_pixels(g) * 3 * sizeof(float), s));
     bool stream = false;
@@ -539,14 +529,32 @@ int views_check(const rtk_accel *a, const rtk_render_params *p, const void *view
     return RTK_OK;
 }
 
+// A call of several launches ("parts": launches of views or regions, or whole frames) with one set of counters: each part counts
+// from zero in d_counters (an engine may reset its counters: the streaming pipeline's overflow fallback does) and is folded into
+// the call's totals on the device; d_counters holds them at the end.  A call of one part needs, and issues, none of this.
+struct CallCounters {
+    rtk_accel *a;
+    bool many;
+    hipStream_t s;
+    int begin() {
+        if (!many) return RTK_OK;
+        RTK_MEM(a->d_views_counters.reserve(kCounterWords));
+        RTK_HIP(hipMemsetAsync(a->d_views_counters.get(), 0, kCounterWords * sizeof(unsigned long long), s));
+        return RTK_OK;
+    }
+    int zero_part() { RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s)); return RTK_OK; }   // (a frame zeroes its own)
+    int after_part() { if (many) RTK_HIP_AS(launch_counters_fold(a->d_counters.get(), a->d_views_counters.get(), s), "launch k_counters_fold"); return RTK_OK; }
+    int end() {
+        if (many) RTK_HIP(hipMemcpyAsync(a->d_counters.get(), a->d_views_counters.get(), kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        return RTK_OK;
+    }
+};
+
 // `h_views`: the views in host memory, or null when the caller has them on the device only (`d_views`, always set).
 int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view *h_views, const rtk_view *d_views,
                       int32_t n_views, float *d_out, hipStream_t s) {
     const size_t stride = size_t(g.width) * g.height * 3;
     const size_t n = size_t(n_views);
-    // a call of several frames / launches: each counts from zero (an engine may reset its counters: the streaming pipeline's
-    // overflow fallback does) and is folded into the call's totals on the device; d_counters holds them at the end
-    if (!a->d_views_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_views_counters), kCounterWords * sizeof(unsigned long long)));
     size_t n_parts = n;
     if (views_one_launch(a, p)) {
         const size_t per_view = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;       // <= 2^26: a launch of one view fits 31 bits
@@ -555,16 +563,18 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
         n_parts = (n + per_launch - 1) / per_launch;
         if (a->fb_views.size() < n_parts) a->fb_views.resize(n_parts);
         const bool general = a->has_refractive || p->diffuse_rays > 0 || !a->scene.textures.empty();
-        if (n_parts > 1) RTK_HIP(hipMemsetAsync(a->d_views_counters, 0, kCounterWords * sizeof(unsigned long long), s));
+        CallCounters cc{a, n_parts > 1, s};
+        RTK_TRY(cc.begin());
         for (size_t c = 0; c < n_parts; ++c) {
             const size_t first = c * per_launch, cnt = n - first < per_launch ? n - first : per_launch;
             dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_out + first * stride);     // (the camera in the arguments is not read)
             A.views = reinterpret_cast<const float *>(d_views + first);
             A.n_views = uint32_t(cnt); A.units_per_view = uint32_t(per_view); A.view_stride = stride;
-            RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+            RTK_TRY(cc.zero_part());
             RTK_TRY(render_megakernel(a, a->fb_views[c], p, g, A, general, s));
-            if (n_parts > 1) RTK_HIP_AS(launch_counters_fold(a->d_counters, a->d_views_counters, s), "launch k_counters_fold");
+            RTK_TRY(cc.after_part());
         }
+        RTK_TRY(cc.end());
     } else {
         std::vector<rtk_view> back;
         if (!h_views) {                          // the engines of this path take the camera in their launch arguments: fetch the views
@@ -573,13 +583,14 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
             RTK_HIP(hipStreamSynchronize(s));
             h_views = back.data();
         }
-        if (n_parts > 1) RTK_HIP(hipMemsetAsync(a->d_views_counters, 0, kCounterWords * sizeof(unsigned long long), s));
+        CallCounters cc{a, n_parts > 1, s};
+        RTK_TRY(cc.begin());
         for (size_t v = 0; v < n; ++v) {
             RTK_TRY(render_frame_impl(a, p, g, h_views[v], d_out + v * stride, s));
-            if (n_parts > 1) RTK_HIP_AS(launch_counters_fold(a->d_counters, a->d_views_counters, s), "launch k_counters_fold");
+            RTK_TRY(cc.after_part());
         }
+        RTK_TRY(cc.end());
     }
-    if (n_parts > 1) RTK_HIP(hipMemcpyAsync(a->d_counters, a->d_views_counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
     a->last_stream = s;
     a->last_stats = p->collect_stats != 0;
     a->last_primary = primary_rays_of_rank(g) * uint64_t(n);
@@ -619,8 +630,8 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
     if (n_chunks_out) *n_chunks_out = uint32_t(plan.n_chunks);
     RTK_TRY(ensure_stream_ws(a, 0, plan.nodes, a->scene.lights.size(), false, lanes));
     const size_t lane_words = size_t(dev::kStreamLanes) * kCounterWords;
-    if (!a->d_rad_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_rad_counters), (lane_words + 2) * sizeof(unsigned long long)));
-    unsigned long long *const total = a->d_rad_counters + lane_words;
+    RTK_MEM(a->d_rad_counters.reserve(lane_words + 2));
+    unsigned long long *const total = a->d_rad_counters.get() + lane_words;
     RTK_TRY(claim_stream_ws(a, s));
     RTK_HIP(hipMemsetAsync(total, 0, 2 * sizeof(unsigned long long), s));
     dev::StreamArgs &S = u.S;
@@ -638,7 +649,7 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
         S.user_n = uint32_t(cn); S.user_id0 = uint32_t(first);
         S.n_root = uint32_t((cn + 63) / 64 * 64); S.n_level0 = S.n_root;
         S.r.out = d_rgb + first * 3;
-        S.r.counters = a->d_rad_counters + size_t(j) * kCounterWords;
+        S.r.counters = a->d_rad_counters.get() + size_t(j) * kCounterWords;
         // ctrl: a chunk zeroes its lane's and its counter block on the lane's stream (the overflow word included: it is the chunk's)
         RTK_HIP(hipMemsetAsync(S.ws.ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), ls));
         RTK_HIP(hipMemsetAsync(S.r.counters, 0, kCounterWords * sizeof(unsigned long long), ls));
@@ -648,7 +659,7 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
         if (e == hipSuccess) e = launch_radiance_fold(S, total, ls);
         if (e == hipSuccess) e = launch_radiance_fallback(S, total, ls);
         if (e != hipSuccess) return hip_fail(e, "launch radiance chunk");
-        if (j != 0) RTK_HIP(hipEventRecord(a->lane_done[j], ls));
+        if (j != 0) RTK_HIP(hipEventRecord(a->lane_done[j].get(), ls));
     }
     RTK_TRY(join_lanes(a, lanes, s));
     return release_stream_ws(a, s);
@@ -695,17 +706,14 @@ int regions_table(rtk_accel *a, const FrameGeom &g, const rtk_rect *rects, size_
     for (rtk_cost_feedback &f : a->fb_regions) f.forget();
     a->rg_plan = plan_regions(rects, n, layout, g.width, limit);
     const size_t n_entries = a->rg_plan.entries.size();
-    if (!a->rg_done) RTK_HIP(hipEventCreateWithFlags(&a->rg_done, hipEventDisableTiming));
-    if (a->rg_table_cap < n_entries) {
-        const size_t cap = n_entries + n_entries / 2 + 16;
+    RTK_MEM(a->rg_done.ensure());
+    if (a->rg_table.capacity() < n_entries) {
         RTK_HIP(hipDeviceSynchronize());
-        (void)hipFree(a->rg_table); a->rg_table = nullptr; a->rg_table_cap = 0;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_table), cap * sizeof(RegionEntry)));
-        a->rg_table_cap = cap;
+        RTK_MEM(a->rg_table.reserve(n_entries, grow_table()));
     } else if (a->rg_in_use) {
-        RTK_HIP(hipStreamWaitEvent(s, a->rg_done, 0));                // a call on another stream may still be reading the old table
+        RTK_HIP(hipStreamWaitEvent(s, a->rg_done.get(), 0));                // a call on another stream may still be reading the old table
     }
-    RTK_HIP(hipMemcpyAsync(a->rg_table, a->rg_plan.entries.data(), n_entries * sizeof(RegionEntry), hipMemcpyHostToDevice, s));
+    RTK_HIP(hipMemcpyAsync(a->rg_table.get(), a->rg_plan.entries.data(), n_entries * sizeof(RegionEntry), hipMemcpyHostToDevice, s));
     a->rg_rects.assign(rects, rects + n);
     a->rg_layout = layout; a->rg_width = g.width; a->rg_limit = limit;
     a->rg_table_valid = true;
@@ -725,55 +733,50 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
         // the megakernel: one launch per RegionLaunch, each with cost tables of its own; several are folded into the call's totals
         const size_t n_parts = P.launches.size();
         if (a->fb_regions.size() < n_parts) a->fb_regions.resize(n_parts);
-        if (n_parts > 1) {
-            if (!a->d_views_counters) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_views_counters), kCounterWords * sizeof(unsigned long long)));
-            RTK_HIP(hipMemsetAsync(a->d_views_counters, 0, kCounterWords * sizeof(unsigned long long), s));
-        }
+        CallCounters cc{a, n_parts > 1, s};
+        RTK_TRY(cc.begin());
         for (size_t c = 0; c < n_parts; ++c) {
             const RegionLaunch &L = P.launches[c];
-            A.regions = a->rg_table + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
+            A.regions = a->rg_table.get() + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
             A.order_in = nullptr; A.order_hdr = nullptr; A.wg_list = nullptr; A.cost_out = nullptr;
-            RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+            RTK_TRY(cc.zero_part());
             RTK_TRY(render_megakernel(a, a->fb_regions[c], p, g, A, general, s));
-            if (n_parts > 1) RTK_HIP_AS(launch_counters_fold(a->d_counters, a->d_views_counters, s), "launch k_counters_fold");
+            RTK_TRY(cc.after_part());
         }
-        if (n_parts > 1) RTK_HIP(hipMemcpyAsync(a->d_counters, a->d_views_counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        RTK_TRY(cc.end());
     } else {
         // sample by sample and chunk by chunk: camera rays + frame pixel indices, the radiance pipeline, the sums.  All of a
         // pixel's launches are on `s` (the pipeline forks onto its lanes and joins `s` again), so its sum stays in sample order.
         uint64_t largest = 0;
         for (const RegionLaunch &L : P.launches) largest = L.n_pixels > largest ? L.n_pixels : largest;
         const size_t chunk = size_t(largest < kRegionChunkPixels ? largest : kRegionChunkPixels);
-        if (a->rg_cap < chunk) {
-            const size_t cap = chunk + chunk / 2 < kRegionChunkPixels ? chunk + chunk / 2 : size_t(kRegionChunkPixels);
+        if (a->rg_rays.capacity() < chunk || a->rg_ids.capacity() < chunk || a->rg_rgb.capacity() < chunk * 3) {
+            const grow_capped rule{size_t(kRegionChunkPixels)};
             RTK_HIP(hipDeviceSynchronize());
-            (void)hipFree(a->rg_rays); (void)hipFree(a->rg_ids); (void)hipFree(a->rg_rgb);
-            a->rg_rays = nullptr; a->rg_ids = nullptr; a->rg_rgb = nullptr; a->rg_cap = 0;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_rays), cap * sizeof(rtk_ray)));
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_ids), cap * sizeof(uint32_t)));
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_rgb), cap * 3 * sizeof(float)));
-            a->rg_cap = cap;
+            RTK_MEM(a->rg_rays.reserve(chunk, rule));
+            RTK_MEM(a->rg_ids.reserve(chunk, rule));
+            RTK_MEM(a->rg_rgb.reserve(rule(chunk, 0) * 3));
         }
         rtk_radiance_params rp;
         rp.max_ray_depth = p->max_ray_depth; rp.diffuse_rays = p->diffuse_rays; rp.seed = p->seed; rp.sample = 0;
         rp.shadow_bias = p->shadow_bias; rp.reflection_bias = p->reflection_bias; rp.refraction_bias = p->refraction_bias;
         rp.cull = 1; rp.trace_mode = RTK_TRACE_STREAM;
-        RTK_HIP(hipMemsetAsync(a->d_counters, 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+        RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
         for (const RegionLaunch &L : P.launches) {
-            A.regions = a->rg_table + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
+            A.regions = a->rg_table.get() + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
             for (uint64_t first = 0; first < L.n_pixels; first += chunk) {
                 const uint32_t cn = uint32_t(L.n_pixels - first < chunk ? L.n_pixels - first : chunk);
                 for (int smp = g.sample_begin; smp < g.sample_end; ++smp) {
-                    RTK_HIP_AS(launch_region_rays(A, smp, first, cn, a->rg_rays, a->rg_ids, s), "launch k_region_rays");
+                    RTK_HIP_AS(launch_region_rays(A, smp, first, cn, a->rg_rays.get(), a->rg_ids.get(), s), "launch k_region_rays");
                     rp.sample = smp;
-                    RTK_TRY(radiance_device_impl(a, a->rg_rays, a->rg_ids, cn, &rp, a->rg_rgb, s, nullptr));
-                    RTK_HIP_AS(launch_add_word(a->d_counters, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, s), "launch k_add_word");
-                    RTK_HIP_AS(launch_region_accumulate(A, first, cn, a->rg_rgb, smp == 0, p->spp != 1 && smp + 1 == p->spp, s), "launch k_region_accumulate");
+                    RTK_TRY(radiance_device_impl(a, a->rg_rays.get(), a->rg_ids.get(), cn, &rp, a->rg_rgb.get(), s, nullptr));
+                    RTK_HIP_AS(launch_add_word(a->d_counters.get(), a->d_rad_counters.get() + size_t(dev::kStreamLanes) * kCounterWords, s), "launch k_add_word");
+                    RTK_HIP_AS(launch_region_accumulate(A, first, cn, a->rg_rgb.get(), smp == 0, p->spp != 1 && smp + 1 == p->spp, s), "launch k_region_accumulate");
                 }
             }
         }
     }
-    RTK_HIP(hipEventRecord(a->rg_done, s));
+    RTK_HIP(hipEventRecord(a->rg_done.get(), s));
     a->rg_in_use = true;
     a->last_stream = s;
     a->last_stats = false;
@@ -810,7 +813,7 @@ int rtk_render_last_counters(rtk_accel *a, rtk_counters *c) {
     RTK_HIP(hipSetDevice(a->device));
     RTK_HIP(hipStreamSynchronize(a->last_stream));
     unsigned long long h[kCounterWords];
-    RTK_HIP(hipMemcpy(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+    RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
     std::memset(c, 0, sizeof(*c));
     for (int i = 0; i < kRayCounterShards; ++i) h[0] += h[8 + i];      // the frame kernel shards its ray counter
     c->rays = h[0]; c->primary = a->last_primary;
@@ -825,7 +828,7 @@ int rtk_render_last_critical_path(rtk_accel *a, double *ms) {
     RTK_HIP(hipSetDevice(a->device));
     RTK_HIP(hipStreamSynchronize(a->last_stream));
     unsigned long long shard[kRayCounterShards], ticks = 0;
-    RTK_HIP(hipMemcpy(shard, a->d_counters + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
+    RTK_HIP(hipMemcpy(shard, a->d_counters.get() + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
     for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
     *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
     return RTK_OK;
@@ -839,17 +842,12 @@ int rtk_render_frame(rtk_accel *a, const rtk_render_params *p, float *rgb, rtk_c
     {
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        float *d_out = nullptr;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d_out), nf * sizeof(float)));
-        hipError_t e = hipSuccess;
+        DevBuf<float> d_out;                     // (the call's own: freed when the block is left)
+        RTK_MEM(d_out.reserve(nf));
         // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
-        if (p->sample_begin > 0) e = hipMemcpy(d_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_out); return hip_fail(e, "upload of the running sums"); }
-        const int rc = render_device_impl(a, p, d_out, nullptr);
-        if (rc == RTK_OK) e = hipMemcpy(rgb, d_out, nf * sizeof(float), hipMemcpyDeviceToHost);
-        (void)hipFree(d_out);
-        if (rc != RTK_OK) return rc;
-        if (e != hipSuccess) return hip_fail(e, "frame copy");
+        if (p->sample_begin > 0) RTK_HIP_AS(hipMemcpy(d_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice), "upload of the running sums");
+        RTK_TRY(render_device_impl(a, p, d_out.get(), nullptr));
+        RTK_HIP_AS(hipMemcpy(rgb, d_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost), "frame copy");
     }
     if (counters) return rtk_render_last_counters(a, counters);
     return RTK_OK;
@@ -886,21 +884,16 @@ int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, s
     }
     std::lock_guard<std::mutex> lock(a->mu);
     RTK_TRY(ensure_device(a));
-    if (a->rad_cap < n) {
-        (void)hipFree(a->rad_rays); (void)hipFree(a->rad_ids); (void)hipFree(a->rad_rgb);
-        a->rad_rays = nullptr; a->rad_ids = nullptr; a->rad_rgb = nullptr; a->rad_cap = 0;
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rays), n * sizeof(rtk_ray)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_ids), n * sizeof(uint32_t)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rad_rgb), n * 3 * sizeof(float)));
-        a->rad_cap = n;
-    }
-    RTK_HIP(hipMemcpy(a->rad_rays, rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-    if (ids) RTK_HIP(hipMemcpy(a->rad_ids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    RTK_MEM(a->rad_rays.reserve(n));
+    RTK_MEM(a->rad_ids.reserve(n));
+    RTK_MEM(a->rad_rgb.reserve(n * 3));
+    RTK_HIP(hipMemcpy(a->rad_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+    if (ids) RTK_HIP(hipMemcpy(a->rad_ids.get(), ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     uint32_t n_chunks = 0;
-    RTK_TRY(radiance_device_impl(a, a->rad_rays, ids ? a->rad_ids : nullptr, n, p, a->rad_rgb, nullptr, &n_chunks));
-    RTK_HIP(hipMemcpy(rgb, a->rad_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    RTK_TRY(radiance_device_impl(a, a->rad_rays.get(), ids ? a->rad_ids.get() : nullptr, n, p, a->rad_rgb.get(), nullptr, &n_chunks));
+    RTK_HIP(hipMemcpy(rgb, a->rad_rgb.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
     unsigned long long h[2] = {0, 0};
-    RTK_HIP(hipMemcpy(h, a->d_rad_counters + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
+    RTK_HIP(hipMemcpy(h, a->d_rad_counters.get() + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
     if (counters) {
         std::memset(counters, 0, sizeof(*counters));
         counters->rays = h[0]; counters->primary = n;
@@ -955,21 +948,13 @@ int rtk_render_views(rtk_accel *a, const rtk_render_params *p, const rtk_view *v
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
         const size_t n = size_t(n_views), nf = n * g.width * g.height * 3;
-        if (a->views_tab_cap < n) {
-            (void)hipFree(a->views_tab); a->views_tab = nullptr; a->views_tab_cap = 0;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->views_tab), n * sizeof(rtk_view)));
-            a->views_tab_cap = n;
-        }
-        if (a->views_out_cap < nf) {
-            (void)hipFree(a->views_out); a->views_out = nullptr; a->views_out_cap = 0;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->views_out), nf * sizeof(float)));
-            a->views_out_cap = nf;
-        }
-        RTK_HIP(hipMemcpy(a->views_tab, views, n * sizeof(rtk_view), hipMemcpyHostToDevice));
+        RTK_MEM(a->views_tab.reserve(n));
+        RTK_MEM(a->views_out.reserve(nf));
+        RTK_HIP(hipMemcpy(a->views_tab.get(), views, n * sizeof(rtk_view), hipMemcpyHostToDevice));
         // a later pass of progressive views continues the running per-pixel sums the previous pass left in `rgb`
-        if (p->sample_begin > 0) RTK_HIP(hipMemcpy(a->views_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice));
-        RTK_TRY(render_views_impl(a, p, g, views, reinterpret_cast<const rtk_view *>(a->views_tab), n_views, a->views_out, nullptr));
-        RTK_HIP(hipMemcpy(rgb, a->views_out, nf * sizeof(float), hipMemcpyDeviceToHost));
+        if (p->sample_begin > 0) RTK_HIP(hipMemcpy(a->views_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
+        RTK_TRY(render_views_impl(a, p, g, views, a->views_tab.get(), n_views, a->views_out.get(), nullptr));
+        RTK_HIP(hipMemcpy(rgb, a->views_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
     }
     if (counters) return rtk_render_last_counters(a, counters);
     return RTK_OK;
@@ -1005,14 +990,10 @@ int rtk_render_regions(rtk_accel *a, const rtk_render_params *p, const rtk_rect 
             // rectangles come back with the bits they went up with
             const bool packed = layout == RTK_REGIONS_PACKED;
             const size_t nf = packed ? size_t(pixels) * 3 : size_t(g.width) * g.height * 3;
-            if (a->rg_out_cap < nf) {
-                (void)hipFree(a->rg_out); a->rg_out = nullptr; a->rg_out_cap = 0;
-                RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->rg_out), nf * sizeof(float)));
-                a->rg_out_cap = nf;
-            }
-            if (!packed || p->sample_begin > 0) RTK_HIP(hipMemcpy(a->rg_out, rgb, nf * sizeof(float), hipMemcpyHostToDevice));
-            RTK_TRY(render_regions_impl(a, p, g, rects, n_rects, layout, a->rg_out, nullptr));
-            RTK_HIP(hipMemcpy(rgb, a->rg_out, nf * sizeof(float), hipMemcpyDeviceToHost));
+            RTK_MEM(a->rg_out.reserve(nf));
+            if (!packed || p->sample_begin > 0) RTK_HIP(hipMemcpy(a->rg_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
+            RTK_TRY(render_regions_impl(a, p, g, rects, n_rects, layout, a->rg_out.get(), nullptr));
+            RTK_HIP(hipMemcpy(rgb, a->rg_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;
@@ -1040,18 +1021,14 @@ int rtk_camera_rays(rtk_accel *a, const rtk_render_params *p, int32_t sample, rt
     FrameGeom g;
     RTK_TRY(frame_geom(a, p, g));
     const size_t n = size_t(g.width) * g.height;
-    rtk_ray *d = nullptr;
+    DevBuf<rtk_ray> d;
     {
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        RTK_HIP(hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(rtk_ray)));
+        RTK_MEM(d.reserve(n));
     }
-    const int rc = rtk_camera_rays_device(a, p, sample, d, nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == RTK_OK) e = hipMemcpy(rays, d, n * sizeof(rtk_ray), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc != RTK_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "camera ray copy");
+    RTK_TRY(rtk_camera_rays_device(a, p, sample, d.get(), nullptr));
+    RTK_HIP_AS(hipMemcpy(rays, d.get(), n * sizeof(rtk_ray), hipMemcpyDeviceToHost), "camera ray copy");
     return RTK_OK;
 }
 

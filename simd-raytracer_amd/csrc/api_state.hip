@@ -14,13 +14,10 @@ namespace {
 // Room for n lights in d_lights, of a resident accel whose device is idle.  A larger table is made before the old one goes, so a
 // failure leaves the accel as it was.
 int reserve_lights(rtk_accel *a, size_t n) {
-    if (n <= a->lights_cap) return RTK_OK;
-    const size_t cap = n + n / 2 + 8;
-    DevLight *p = nullptr;
-    RTK_HIP(hipMalloc(reinterpret_cast<void **>(&p), cap * sizeof(DevLight)));
-    (void)hipFree(a->d_lights);
-    a->d_lights = p;
-    a->lights_cap = cap;
+    if (n <= a->d_lights.capacity()) return RTK_OK;
+    DevBuf<DevLight> larger;
+    RTK_MEM(larger.reserve(n, grow_lights()));
+    a->d_lights.swap(larger);                            // (the old table goes with `larger`)
     return RTK_OK;
 }
 
@@ -46,7 +43,7 @@ int rtk_accel_get_lights(const rtk_accel *a, rtk_light *out, int32_t cap, int32_
     if (a->lights_on_device) {
         RTK_HIP(hipSetDevice(a->device));
         RTK_HIP(hipDeviceSynchronize());
-        RTK_HIP(hipMemcpy(out, a->d_lights, take * sizeof(rtk_light), hipMemcpyDeviceToHost));
+        RTK_HIP(hipMemcpy(out, a->d_lights.get(), take * sizeof(rtk_light), hipMemcpyDeviceToHost));
     } else std::memcpy(out, a->scene.lights.data(), take * sizeof(rtk_light));
     return RTK_OK;
 }
@@ -64,7 +61,7 @@ int rtk_accel_set_lights(rtk_accel *a, const rtk_light *lights, int32_t n) {
             RTK_HIP(hipDeviceSynchronize());
             a->geom_pending = false;
             RTK_TRY(reserve_lights(a, size_t(n)));
-            if (n > 0) RTK_HIP(hipMemcpy(a->d_lights, table.data(), size_t(n) * sizeof(DevLight), hipMemcpyHostToDevice));
+            if (n > 0) RTK_HIP(hipMemcpy(a->d_lights.get(), table.data(), size_t(n) * sizeof(DevLight), hipMemcpyHostToDevice));
         }
         const size_t before = a->scene.lights.size();
         a->scene.lights.swap(table);
@@ -86,8 +83,8 @@ int rtk_accel_set_lights_device(rtk_accel *a, const rtk_light *d_lights, int32_t
         RTK_TRY(ensure_update_common(a));
         RTK_TRY(reserve_lights(a, size_t(n)));
         std::vector<DevLight> count_only(static_cast<size_t>(n), DevLight{{0.f, 0.f, 0.f}, 0.f});
-        if (n > 0) RTK_HIP(hipMemcpyAsync(a->d_lights, d_lights, size_t(n) * sizeof(DevLight), hipMemcpyDeviceToDevice, s));
-        RTK_HIP(hipEventRecord(a->geom_ready, s));
+        if (n > 0) RTK_HIP(hipMemcpyAsync(a->d_lights.get(), d_lights, size_t(n) * sizeof(DevLight), hipMemcpyDeviceToDevice, s));
+        RTK_HIP(hipEventRecord(a->geom_ready.get(), s));
         a->geom_pending = true;
         const size_t before = a->scene.lights.size();
         a->scene.lights.swap(count_only);              // the COUNT every launch path reads; the values live in d_lights
@@ -127,10 +124,10 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
             RTK_HIP(hipDeviceSynchronize());
             a->geom_pending = false;
             // the new table goes into the spare one, what follows from it is built beside what is active, and both are swapped in at the end
-            if (!a->st_materials) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->st_materials), std::max<size_t>(1, table.size()) * sizeof(DevMaterial)));
-            if (!table.empty()) RTK_HIP(hipMemcpy(a->st_materials, table.data(), table.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
-            RTK_TRY(remake_occluders(a, table, a->st_materials, nullptr));
-            std::swap(a->d_materials, a->st_materials);
+            RTK_MEM(a->st_materials.reserve(table.size()));             // (once: the number of materials is fixed)
+            if (!table.empty()) RTK_HIP(hipMemcpy(a->st_materials.get(), table.data(), table.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
+            RTK_TRY(remake_occluders(a, table, a->st_materials.get(), nullptr));
+            a->d_materials.swap(a->st_materials);
         }
         a->scene.materials.swap(table);
         a->has_refractive = any_refractive;

@@ -9,51 +9,10 @@
 
 using namespace rtk;
 
-namespace rtk {
-
-// Grows a device buffer to at least `need` bytes (with head room; the old contents are not kept).  Freeing synchronises the
-// device: this is the "second block" of an update, taken only when a buffer has to grow.
-int grow_dev(void **p, size_t *cap, size_t need) {
-    if (need == 0) need = 1;
-    if (*p != nullptr && need <= *cap) return RTK_OK;
-    (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 2 + 256;
-    RTK_HIP(hipMalloc(p, n));
-    *cap = n;
-    return RTK_OK;
-}
-
-}  // namespace rtk
-
-namespace {
-
-int grow_pinned(uint8_t **p, size_t *cap, size_t need) {
-    if (*p != nullptr && need <= *cap) return RTK_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 2 + 256;
-    RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(p), n, hipHostMallocDefault));
-    *cap = n;
-    return RTK_OK;
-}
-
-}  // namespace
-
-// What every update needs once: the event later work waits for, and how large the buffers are that ensure_device uploaded.
+// What every update needs once: the event later work waits for.  (Buffers that have to grow do so by grow_bytes; freeing
+// synchronises the device: this is the "second block" of an update, taken only then.)
 int rtk::ensure_update_common(rtk_accel *a) {
-    if (a->geom_ready) return RTK_OK;
-    RTK_HIP(hipEventCreateWithFlags(&a->geom_ready, hipEventDisableTiming));
-    const HostTree &T = a->tree;
-    auto bytes = [](size_t n, size_t each) { return (n == 0 ? 1 : n) * each; };
-    a->active_cap[G_NODES] = bytes(T.dev_nodes.size(), sizeof(DevNode));
-    a->active_cap[G_LEAVES] = bytes(T.dev_leaves.size(), sizeof(DevNode));
-    a->active_cap[G_FAST] = a->d_leaves_fast ? bytes(T.dev_leaves_fast.size(), sizeof(DevNode)) : 0;
-    a->active_cap[G_TRIS] = bytes(T.dev_tris.size(), sizeof(DevTri));
-    a->active_cap[G_IDS] = bytes(T.dev_tri_ids.size(), sizeof(uint32_t));
-    a->active_cap[G_SHADE] = bytes(T.dev_shade.size(), sizeof(DevShade));
-    // (the opaque-only copy was uploaded at its exact size, which is not kept: 0 makes the first update allocate its own)
-    a->topo_active_cap[T_TRI_UV] = a->d_tri_uv ? bytes(T.dev_tri_uv.size(), sizeof(DevTriUv)) : 0;
+    RTK_MEM(a->geom_ready.ensure());
     return RTK_OK;
 }
 
@@ -86,15 +45,12 @@ int ensure_update_static(rtk_accel *a) {
     for (size_t v = 0; v < nv; ++v) off[v + 1] += off[v];
     std::vector<uint32_t> cur(off.begin(), off.end() - 1);
     for (size_t e = 0; e < nt * 3; ++e) inc[cur[index[e]]++] = uint32_t(e);
-    int rc;
-    // (a call that failed half way left what it had made: made once, never twice)
-    if (!a->up_index && (rc = upload(index, &a->up_index)) != RTK_OK) { (void)hipFree(a->up_index); a->up_index = nullptr; return rc; }
-    if (!a->up_inc_off && (rc = upload(off, &a->up_inc_off)) != RTK_OK) { (void)hipFree(a->up_inc_off); a->up_inc_off = nullptr; return rc; }
-    if (!a->up_inc && (rc = upload(inc, &a->up_inc)) != RTK_OK) { (void)hipFree(a->up_inc); a->up_inc = nullptr; return rc; }
-    if (!a->up_opaque && (rc = upload(opaque, &a->up_opaque)) != RTK_OK) { (void)hipFree(a->up_opaque); a->up_opaque = nullptr; return rc; }
-    a->topo_active_cap[T_INDEX] = a->topo_active_cap[T_INC] = std::max<size_t>(1, nt * 3) * sizeof(uint32_t);
-    a->topo_active_cap[T_INC_OFF] = (nv + 1) * sizeof(uint32_t);
-    a->topo_active_cap[T_OPAQUE] = std::max<size_t>(1, nt);
+    // (a call that failed half way left what it had made: made once, never twice; a failed upload leaves its buffer empty)
+    TopoBufs &A = a->topo;
+    if (!A.index.get()) RTK_TRY(upload(index, A.index));
+    if (!A.inc_off.get()) RTK_TRY(upload(off, A.inc_off));
+    if (!A.inc.get()) RTK_TRY(upload(inc, A.inc));
+    if (!A.opaque.get()) RTK_TRY(upload(opaque, A.opaque));
     a->up_static = true;
     return RTK_OK;
 }
@@ -111,20 +67,18 @@ struct NewTopology {
 int prepare_topology(rtk_accel *a, const NewTopology &N, hipStream_t s, dev::TopoArgs &T) {
     const size_t nv = size_t(a->scene.n_vertices), nt = N.n_tris, nm = a->mesh_nverts.size();
     const bool textured = !a->scene.textures.empty();
-    void **sp = a->topo_spare;
-    size_t *sc = a->topo_spare_cap;
-    RTK_TRY(grow_dev(&sp[T_INDEX], &sc[T_INDEX], nt * 3 * sizeof(uint32_t)));
-    RTK_TRY(grow_dev(&sp[T_INC_OFF], &sc[T_INC_OFF], (nv + 1) * sizeof(uint32_t)));
-    RTK_TRY(grow_dev(&sp[T_INC], &sc[T_INC], nt * 3 * sizeof(uint32_t)));
-    RTK_TRY(grow_dev(&sp[T_OPAQUE], &sc[T_OPAQUE], nt));
-    if (textured) RTK_TRY(grow_dev(&sp[T_TRI_UV], &sc[T_TRI_UV], nt * sizeof(DevTriUv)));
-    size_t kcap = a->topo_keys_cap, temp_bytes = 0;
-    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->topo_keys), &kcap, nt * 3 * sizeof(uint32_t)));
-    a->topo_keys_cap = kcap;
+    TopoBufs &sp = a->topo_spare;
+    RTK_MEM(sp.index.reserve(nt * 3, grow_bytes()));
+    RTK_MEM(sp.inc_off.reserve(nv + 1, grow_bytes()));
+    RTK_MEM(sp.inc.reserve(nt * 3, grow_bytes()));
+    RTK_MEM(sp.opaque.reserve(nt, grow_bytes()));
+    if (textured) RTK_MEM(sp.tri_uv.reserve(nt, grow_bytes()));
+    size_t temp_bytes = 0;
+    RTK_MEM(a->topo_keys.reserve(nt * 3, grow_bytes()));
     RTK_HIP_AS(topology_temp_bytes(uint32_t(nt), uint32_t(nv), &temp_bytes), "size the incidence sort");
-    RTK_TRY(grow_dev(&a->topo_temp, &a->topo_temp_cap, temp_bytes));
-    if (!a->topo_meshes) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->topo_meshes), (nm + 1) * sizeof(dev::TopoMesh)));
-    if (textured && !a->topo_vert_uv) {                                     // kdtree.cpp:283-: a mesh without uvs has zeros
+    RTK_MEM(a->topo_temp.reserve(temp_bytes, grow_bytes()));
+    RTK_MEM(a->topo_meshes.reserve(nm + 1));                                // (once: the number of meshes is fixed)
+    if (textured && !a->topo_vert_uv.get()) {                                     // kdtree.cpp:283-: a mesh without uvs has zeros
         std::vector<float> uv(std::max<size_t>(1, nv) * 2, 0.0f);
         size_t voff = 0;
         for (size_t mi = 0; mi < nm; ++mi) {
@@ -133,11 +87,10 @@ int prepare_topology(rtk_accel *a, const NewTopology &N, hipStream_t s, dev::Top
             if (n > 0) std::memcpy(uv.data() + voff * 2, mu.data(), n * sizeof(float));
             voff += size_t(a->mesh_nverts[mi]);
         }
-        int rc;
-        if ((rc = upload(uv, &a->topo_vert_uv)) != RTK_OK) { (void)hipFree(a->topo_vert_uv); a->topo_vert_uv = nullptr; return rc; }
+        RTK_TRY(upload(uv, a->topo_vert_uv));
     }
-    RTK_TRY(grow_pinned(&a->up_stage, &a->up_stage_cap, (nm + 1) * sizeof(dev::TopoMesh)));
-    dev::TopoMesh *rows = reinterpret_cast<dev::TopoMesh *>(a->up_stage);
+    RTK_MEM(a->up_stage.reserve((nm + 1) * sizeof(dev::TopoMesh), grow_bytes()));
+    dev::TopoMesh *rows = reinterpret_cast<dev::TopoMesh *>(a->up_stage.get());
     uint32_t tri = 0u, vert = 0u;
     for (size_t mi = 0; mi <= nm; ++mi) {
         dev::TopoMesh r{};
@@ -151,15 +104,15 @@ int prepare_topology(rtk_accel *a, const NewTopology &N, hipStream_t s, dev::Top
         }
         rows[mi] = r;
     }
-    RTK_HIP(hipMemcpyAsync(a->topo_meshes, rows, (nm + 1) * sizeof(dev::TopoMesh), hipMemcpyHostToDevice, s));
-    T.indices = N.d_indices; T.meshes = a->topo_meshes;
+    RTK_HIP(hipMemcpyAsync(a->topo_meshes.get(), rows, (nm + 1) * sizeof(dev::TopoMesh), hipMemcpyHostToDevice, s));
+    T.indices = N.d_indices; T.meshes = a->topo_meshes.get();
     T.n_meshes = uint32_t(nm); T.n_tris = uint32_t(nt); T.n_verts = uint32_t(nv);
-    T.vert_uv = textured ? a->topo_vert_uv : nullptr;
-    T.index = static_cast<uint32_t *>(sp[T_INDEX]); T.inc_off = static_cast<uint32_t *>(sp[T_INC_OFF]); T.inc = static_cast<uint32_t *>(sp[T_INC]);
-    T.opaque = static_cast<uint8_t *>(sp[T_OPAQUE]);
-    T.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
-    T.tri_uv = textured ? static_cast<DevTriUv *>(sp[T_TRI_UV]) : nullptr;
-    T.keys = a->topo_keys; T.temp = a->topo_temp; T.temp_bytes = temp_bytes;
+    T.vert_uv = textured ? a->topo_vert_uv.get() : nullptr;
+    T.index = sp.index.get(); T.inc_off = sp.inc_off.get(); T.inc = sp.inc.get();
+    T.opaque = sp.opaque.get();
+    T.shade = a->geom_spare.shade.get();
+    T.tri_uv = textured ? sp.tri_uv.get() : nullptr;
+    T.keys = a->topo_keys.get(); T.temp = a->topo_temp.get(); T.temp_bytes = temp_bytes;
     T.hdr = nullptr;                                                        // (the caller's: the table may still be allocated)
     return RTK_OK;
 }
@@ -172,70 +125,63 @@ int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hip
     const uint32_t nv = uint32_t(a->scene.n_vertices), nt = topo ? topo->n_tris : uint32_t(a->scene.n_triangles);
     const bool occl = a->occl_on;
     // per-triangle scratch and the new shading records
-    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_tris), &a->up_tris_cap, size_t(nt) * sizeof(DevTri)));
-    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_tbox), &a->up_tbox_cap, size_t(nt) * 6 * sizeof(float)));
-    RTK_TRY(grow_dev(&a->spare[G_SHADE], &a->spare_cap[G_SHADE], size_t(nt) * sizeof(DevShade)));
+    GeomBufs &sp = a->geom_spare;
+    RTK_MEM(a->up_tris.reserve(nt, grow_bytes()));
+    RTK_MEM(a->up_tbox.reserve(size_t(nt) * 6, grow_bytes()));
+    RTK_MEM(sp.shade.reserve(nt, grow_bytes()));
     dev::TopoArgs TA{};
     if (topo) RTK_TRY(prepare_topology(a, *topo, s, TA));
-    const uint32_t *t_index = topo ? TA.index : a->up_index, *t_inc_off = topo ? TA.inc_off : a->up_inc_off, *t_inc = topo ? TA.inc : a->up_inc;
-    const uint8_t *t_opaque = topo ? TA.opaque : a->up_opaque;
+    const uint32_t *t_index = topo ? TA.index : a->topo.index.get(), *t_inc_off = topo ? TA.inc_off : a->topo.inc_off.get(), *t_inc = topo ? TA.inc : a->topo.inc.get();
+    const uint8_t *t_opaque = topo ? TA.opaque : a->topo.opaque.get();
     // Capacities of the build: a tree of depth d has at most 2^(d+1) - 1 nodes; the lists of all levels lie one behind the
     // other, a level's lists together are about as long as leaf_refs.  Both are checked on the device; a build that does not fit
     // raises a flag, and is repeated with more room.
     const size_t max_nodes = (size_t(1) << (a->params.max_depth + 1)) - 1;
-    size_t want_nodes = a->up_cap_nodes ? a->up_cap_nodes : std::max<size_t>(1024, 4 * a->tree.dev_nodes.size());
+    // (the table and the reference lists are sized exactly: their capacities are the build's, cap_nodes behind the header)
+    auto table_bytes = [](size_t nodes) { return sizeof(dev::BuildHdr) + nodes * sizeof(dev::BuildNode); };
+    auto cap_nodes = [&] { return a->up_table.get() ? (a->up_table.capacity() - sizeof(dev::BuildHdr)) / sizeof(dev::BuildNode) : size_t(0); };
+    auto cap_refs = [&] { return a->up_ref_node.capacity(); };
+    size_t want_nodes = cap_nodes() ? cap_nodes() : std::max<size_t>(1024, 4 * a->tree.dev_nodes.size());
     const size_t first_refs = std::max<size_t>(4096, 2 * size_t(nt) * size_t(std::min(a->params.max_depth, 12) + 2));
-    size_t want_refs = a->up_cap_refs ? a->up_cap_refs : first_refs;
+    size_t want_refs = cap_refs() ? cap_refs() : first_refs;
     if (topo && want_refs < first_refs) want_refs = first_refs;             // more triangles than the capacity was learnt on: no point in trying it
     dev::BuildHdr hdr;
     for (int attempt = 0;; ++attempt) {
         if (want_nodes > max_nodes) want_nodes = max_nodes;
         if (attempt > 16 || want_refs > 0x7FFFFFF0ull) return fail(RTK_ERR_INVALID, "tree too large for 32-bit node/triangle indices");
         if (want_refs < nt) want_refs = nt;
-        if (want_nodes != a->up_cap_nodes || !a->up_table) {
-            const size_t bytes = sizeof(dev::BuildHdr) + want_nodes * sizeof(dev::BuildNode);
-            (void)hipFree(a->up_table); a->up_table = nullptr; a->up_cap_nodes = 0;
-            if (a->up_table_host) (void)hipHostFree(a->up_table_host);
-            a->up_table_host = nullptr;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_table), bytes));
-            RTK_HIP(hipHostMalloc(reinterpret_cast<void **>(&a->up_table_host), bytes, hipHostMallocDefault));
-            a->up_cap_nodes = want_nodes;
-        }
-        if (want_refs != a->up_cap_refs || !a->up_ref_id) {
-            (void)hipFree(a->up_ref_id); (void)hipFree(a->up_ref_node);
-            a->up_ref_id = a->up_ref_node = nullptr; a->up_cap_refs = 0;
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_id), want_refs * sizeof(uint32_t)));
-            RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_ref_node), want_refs * sizeof(uint32_t)));
-            a->up_cap_refs = want_refs;
-        }
+        RTK_MEM(a->up_table.reserve(table_bytes(want_nodes), set_exactly()));
+        RTK_MEM(a->up_table_host.reserve(table_bytes(want_nodes), set_exactly()));
+        RTK_MEM(a->up_ref_id.reserve(want_refs, set_exactly()));
+        RTK_MEM(a->up_ref_node.reserve(want_refs, set_exactly()));
         dev::BuildArgs B;
         B.verts = d_verts; B.n_verts = nv; B.n_tris = nt;
         B.index = t_index; B.inc_off = t_inc_off; B.inc = t_inc;
         B.opaque = occl ? t_opaque : nullptr;
-        B.shade = static_cast<DevShade *>(a->spare[G_SHADE]);
-        B.shade_old = topo ? B.shade : a->d_shade;                          // (topology.hip wrote mesh / material into the new records)
-        B.tris = a->up_tris; B.tbox = a->up_tbox;
-        B.ref_id = a->up_ref_id; B.ref_node = a->up_ref_node;
-        B.cap_refs = uint32_t(a->up_cap_refs); B.cap_nodes = uint32_t(a->up_cap_nodes);
+        B.shade = sp.shade.get();
+        B.shade_old = topo ? B.shade : a->geom.shade.get();                          // (topology.hip wrote mesh / material into the new records)
+        B.tris = a->up_tris.get(); B.tbox = a->up_tbox.get();
+        B.ref_id = a->up_ref_id.get(); B.ref_node = a->up_ref_node.get();
+        B.cap_refs = uint32_t(cap_refs()); B.cap_nodes = uint32_t(cap_nodes());
         B.max_depth = a->params.max_depth; B.max_leaf = a->params.max_leaf_size;
-        B.hdr = reinterpret_cast<dev::BuildHdr *>(a->up_table);
-        B.nodes = reinterpret_cast<dev::BuildNode *>(a->up_table + sizeof(dev::BuildHdr));
+        B.hdr = reinterpret_cast<dev::BuildHdr *>(a->up_table.get());
+        B.nodes = reinterpret_cast<dev::BuildNode *>(a->up_table.get() + sizeof(dev::BuildHdr));
         TA.hdr = B.hdr;
         // (the topology tables do not depend on the capacities: a repeat keeps them.  Their flag is read after the first attempt.)
         RTK_HIP_AS(launch_build(B, topo && attempt == 0 ? &TA : nullptr, s), "launch device build");
         // the one place an update blocks the host: flags, sizes and the node table
-        RTK_HIP(hipMemcpyAsync(a->up_table_host, a->up_table, sizeof(dev::BuildHdr) + a->up_cap_nodes * sizeof(dev::BuildNode), hipMemcpyDeviceToHost, s));
+        RTK_HIP(hipMemcpyAsync(a->up_table_host.get(), a->up_table.get(), table_bytes(cap_nodes()), hipMemcpyDeviceToHost, s));
         RTK_HIP(hipStreamSynchronize(s));
-        std::memcpy(&hdr, a->up_table_host, sizeof(hdr));
+        std::memcpy(&hdr, a->up_table_host.get(), sizeof(hdr));
         const uint32_t raised = ~hdr.ok;
         if (raised & dev::kBuildNonFinite) return fail(RTK_ERR_INVALID, "vertices must be finite");
         if (raised & dev::kBuildBadIndex) return fail(RTK_ERR_INVALID, "an index is not a vertex of its mesh");
         if ((raised & (dev::kBuildRefOverflow | dev::kBuildNodeOverflow)) == 0u) break;
-        if (raised & dev::kBuildNodeOverflow) want_nodes = std::max<size_t>(2 * a->up_cap_nodes, 2 * size_t(hdr.need_nodes));
-        if (raised & dev::kBuildRefOverflow) want_refs = std::max<size_t>(2 * a->up_cap_refs, 2 * size_t(hdr.need_refs));
+        if (raised & dev::kBuildNodeOverflow) want_nodes = std::max<size_t>(2 * cap_nodes(), 2 * size_t(hdr.need_nodes));
+        if (raised & dev::kBuildRefOverflow) want_refs = std::max<size_t>(2 * cap_refs(), 2 * size_t(hdr.need_refs));
     }
     // numbering on the host (kdtree.cpp): reference order, traversal order with skip links, leaf offsets in both, FAST orders
-    const dev::BuildNode *bn = reinterpret_cast<const dev::BuildNode *>(a->up_table_host + sizeof(dev::BuildHdr));
+    const dev::BuildNode *bn = reinterpret_cast<const dev::BuildNode *>(a->up_table_host.get() + sizeof(dev::BuildHdr));
     HostTree T;
     std::vector<dev::GatherLeaf> gather;
     tree_from_build_nodes(bn, T, gather);
@@ -261,74 +207,56 @@ int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hip
     }
     for (dev::GatherLeaf &g : gather) g.pad[0] = 0u;
     // room in the spare set
-    void **sp = a->spare;
-    size_t *sc = a->spare_cap;
-    RTK_TRY(grow_dev(&sp[G_NODES], &sc[G_NODES], T.dev_nodes.size() * sizeof(DevNode)));
-    RTK_TRY(grow_dev(&sp[G_LEAVES], &sc[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode)));
-    if (a->fast_traversal) RTK_TRY(grow_dev(&sp[G_FAST], &sc[G_FAST], T.dev_leaves_fast.size() * sizeof(DevNode)));
-    RTK_TRY(grow_dev(&sp[G_TRIS], &sc[G_TRIS], n_refs * sizeof(DevTri)));
-    RTK_TRY(grow_dev(&sp[G_IDS], &sc[G_IDS], n_refs * sizeof(uint32_t)));
-    RTK_TRY(grow_dev(&sp[G_LREFS], &sc[G_LREFS], n_refs * sizeof(int32_t)));
+    RTK_MEM(sp.nodes.reserve(T.dev_nodes.size(), grow_bytes()));
+    RTK_MEM(sp.leaves.reserve(T.dev_leaves.size(), grow_bytes()));
+    if (a->fast_traversal) RTK_MEM(sp.leaves_fast.reserve(T.dev_leaves_fast.size(), grow_bytes()));
+    RTK_MEM(sp.tris.reserve(n_refs, grow_bytes()));
+    RTK_MEM(sp.tri_ids.reserve(n_refs, grow_bytes()));
+    RTK_MEM(sp.leaf_refs.reserve(n_refs, grow_bytes()));
     if (occl) {
-        RTK_TRY(grow_dev(&sp[G_ONODES], &sc[G_ONODES], onodes.size() * sizeof(DevNode)));
-        RTK_TRY(grow_dev(&sp[G_OLEAVES], &sc[G_OLEAVES], oleaves.size() * sizeof(DevNode)));
-        RTK_TRY(grow_dev(&sp[G_OTRIS], &sc[G_OTRIS], std::max<size_t>(1, n_opaque) * sizeof(DevTri)));
-        RTK_TRY(grow_dev(&sp[G_OIDS], &sc[G_OIDS], std::max<size_t>(1, n_opaque) * sizeof(uint32_t)));
+        RTK_MEM(sp.occl_nodes.reserve(onodes.size(), grow_bytes()));
+        RTK_MEM(sp.occl_leaves.reserve(oleaves.size(), grow_bytes()));
+        RTK_MEM(sp.occl_tris.reserve(std::max<size_t>(1, n_opaque), grow_bytes()));
+        RTK_MEM(sp.occl_ids.reserve(std::max<size_t>(1, n_opaque), grow_bytes()));
     }
-    size_t gcap = a->up_gather_cap * sizeof(dev::GatherLeaf);
-    RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_gather), &gcap, gather.size() * sizeof(dev::GatherLeaf)));
-    a->up_gather_cap = gcap / sizeof(dev::GatherLeaf);
+    RTK_MEM(a->up_gather.reserve(gather.size(), grow_bytes()));
     // the small tables go up through one pinned buffer (the copies are stream-ordered and the host does not wait for them)
     struct Up { const void *src; void *dst; size_t bytes; };
     const Up ups[] = {
-        {T.dev_nodes.data(), sp[G_NODES], T.dev_nodes.size() * sizeof(DevNode)},
-        {T.dev_leaves.data(), sp[G_LEAVES], T.dev_leaves.size() * sizeof(DevNode)},
-        {T.dev_leaves_fast.data(), sp[G_FAST], a->fast_traversal ? T.dev_leaves_fast.size() * sizeof(DevNode) : 0},
-        {gather.data(), a->up_gather, gather.size() * sizeof(dev::GatherLeaf)},
-        {onodes.data(), sp[G_ONODES], onodes.size() * sizeof(DevNode)},
-        {oleaves.data(), sp[G_OLEAVES], oleaves.size() * sizeof(DevNode)},
+        {T.dev_nodes.data(), sp.nodes.get(), T.dev_nodes.size() * sizeof(DevNode)},
+        {T.dev_leaves.data(), sp.leaves.get(), T.dev_leaves.size() * sizeof(DevNode)},
+        {T.dev_leaves_fast.data(), sp.leaves_fast.get(), a->fast_traversal ? T.dev_leaves_fast.size() * sizeof(DevNode) : 0},
+        {gather.data(), a->up_gather.get(), gather.size() * sizeof(dev::GatherLeaf)},
+        {onodes.data(), sp.occl_nodes.get(), onodes.size() * sizeof(DevNode)},
+        {oleaves.data(), sp.occl_leaves.get(), oleaves.size() * sizeof(DevNode)},
     };
     size_t total = 0;
     for (const Up &u : ups) total += (u.bytes + 63) & ~size_t(63);
-    RTK_TRY(grow_pinned(&a->up_stage, &a->up_stage_cap, total));
+    RTK_MEM(a->up_stage.reserve(total, grow_bytes()));
+    uint8_t *const stage = a->up_stage.get();
     size_t at = 0;
     for (const Up &u : ups) {
         if (u.bytes == 0) continue;
-        std::memcpy(a->up_stage + at, u.src, u.bytes);
-        RTK_HIP(hipMemcpyAsync(u.dst, a->up_stage + at, u.bytes, hipMemcpyHostToDevice, s));
+        std::memcpy(stage + at, u.src, u.bytes);
+        RTK_HIP(hipMemcpyAsync(u.dst, stage + at, u.bytes, hipMemcpyHostToDevice, s));
         at += (u.bytes + 63) & ~size_t(63);
     }
     dev::GatherArgs G;
-    G.leaves = a->up_gather; G.n_leaves = uint32_t(gather.size());
-    G.ref_id = a->up_ref_id; G.tris_in = a->up_tris; G.opaque = occl ? t_opaque : nullptr;
-    G.tris = static_cast<DevTri *>(sp[G_TRIS]); G.tri_ids = static_cast<uint32_t *>(sp[G_IDS]); G.leaf_refs = static_cast<int32_t *>(sp[G_LREFS]);
-    G.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); G.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]);
+    G.leaves = a->up_gather.get(); G.n_leaves = uint32_t(gather.size());
+    G.ref_id = a->up_ref_id.get(); G.tris_in = a->up_tris.get(); G.opaque = occl ? t_opaque : nullptr;
+    G.tris = sp.tris.get(); G.tri_ids = sp.tri_ids.get(); G.leaf_refs = sp.leaf_refs.get();
+    G.occl_tris = sp.occl_tris.get(); G.occl_ids = sp.occl_ids.get();
     RTK_HIP_AS(launch_gather(G, s), "launch k_build_gather");
     if (occl && n_opaque == 0) {                                        // nothing opaque: keep the pointers valid, as ensure_device does
-        if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp[G_OTRIS], sp[G_TRIS], sizeof(DevTri), hipMemcpyDeviceToDevice, s));
-        else RTK_HIP(hipMemsetAsync(sp[G_OTRIS], 0, sizeof(DevTri), s));
-        RTK_HIP(hipMemsetAsync(sp[G_OIDS], 0, sizeof(uint32_t), s));
+        if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp.occl_tris.get(), sp.tris.get(), sizeof(DevTri), hipMemcpyDeviceToDevice, s));
+        else RTK_HIP(hipMemsetAsync(sp.occl_tris.get(), 0, sizeof(DevTri), s));
+        RTK_HIP(hipMemsetAsync(sp.occl_ids.get(), 0, sizeof(uint32_t), s));
     }
-    RTK_HIP(hipEventRecord(a->geom_ready, s));
+    RTK_HIP(hipEventRecord(a->geom_ready.get(), s));
     // ---- nothing below fails: swap the sets and bring the host's picture of the accel up to date
-    void **act[kGeomBufs] = {reinterpret_cast<void **>(&a->d_nodes), reinterpret_cast<void **>(&a->d_leaves), reinterpret_cast<void **>(&a->d_leaves_fast),
-                             reinterpret_cast<void **>(&a->d_tris), reinterpret_cast<void **>(&a->d_tri_ids), reinterpret_cast<void **>(&a->d_shade),
-                             reinterpret_cast<void **>(&a->d_leaf_refs), reinterpret_cast<void **>(&a->d_occl_nodes), reinterpret_cast<void **>(&a->d_occl_leaves),
-                             reinterpret_cast<void **>(&a->d_occl_tris), reinterpret_cast<void **>(&a->d_occl_ids)};
-    for (int i = 0; i < kGeomBufs; ++i) {
-        if (i == G_FAST && !a->fast_traversal) continue;
-        if (i >= G_ONODES && !occl) continue;
-        std::swap(*act[i], a->spare[i]);
-        std::swap(a->active_cap[i], a->spare_cap[i]);
-    }
+    a->geom.swap(sp, a->fast_traversal, occl);
     if (topo) {
-        void **tact[kTopoBufs] = {reinterpret_cast<void **>(&a->up_index), reinterpret_cast<void **>(&a->up_inc_off), reinterpret_cast<void **>(&a->up_inc),
-                                  reinterpret_cast<void **>(&a->up_opaque), reinterpret_cast<void **>(&a->d_tri_uv)};
-        for (int i = 0; i < kTopoBufs; ++i) {
-            if (i == T_TRI_UV && TA.tri_uv == nullptr) continue;
-            std::swap(*tact[i], a->topo_spare[i]);
-            std::swap(a->topo_active_cap[i], a->topo_spare_cap[i]);
-        }
+        a->topo.swap(a->topo_spare, TA.tri_uv != nullptr);
         a->up_static = true;
         a->scene.n_triangles = int32_t(nt);
         a->mesh_ntris.assign(topo->mesh_ntris, topo->mesh_ntris + a->mesh_ntris.size());
@@ -391,11 +319,11 @@ int rtk::remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &material
         if (refractive(materials[i]) != refractive(a->scene.materials[i])) set_changed = true;
     }
     const bool tree = a->fast_traversal && a->knobs.fast_occluders && set_changed;
-    if (!tree && !(a->up_opaque && set_changed)) return RTK_OK;
+    if (!tree && !(a->topo.opaque.get() && set_changed)) return RTK_OK;
     RTK_TRY(ensure_update_common(a));
     dev::OcclArgs O{};
     O.materials = d_materials; O.n_materials = uint32_t(materials.size());
-    O.shade = a->d_shade; O.n_tris = uint32_t(a->scene.n_triangles);
+    O.shade = a->geom.shade.get(); O.n_tris = uint32_t(a->scene.n_triangles);
     if (tree && any) {
         // the leaves of the active tree, in dev_nodes' order: as ensure_device and update_impl walk them
         const std::vector<DevNode> &nodes = a->tree.dev_nodes;
@@ -405,16 +333,16 @@ int rtk::remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &material
         for (const dev::OcclLeaf &l : leaves)
             if (size_t(l.first) + l.count > n_refs) return fail(RTK_ERR_INVALID, "internal: a leaf runs past the accel's references");
         const size_t nl = leaves.size();
-        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->st_leaves), &a->st_leaves_cap, nl * sizeof(dev::OcclLeaf)));
-        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->st_counts), &a->st_counts_cap, nl * sizeof(uint32_t)));
-        O.leaves = a->st_leaves; O.n_leaves = uint32_t(nl); O.n_refs = uint32_t(n_refs);
-        O.tris = a->d_tris; O.tri_ids = a->d_tri_ids; O.counts = a->st_counts;
+        RTK_MEM(a->st_leaves.reserve(nl, grow_bytes()));
+        RTK_MEM(a->st_counts.reserve(nl, grow_bytes()));
+        O.leaves = a->st_leaves.get(); O.n_leaves = uint32_t(nl); O.n_refs = uint32_t(n_refs);
+        O.tris = a->geom.tris.get(); O.tri_ids = a->geom.tri_ids.get(); O.counts = a->st_counts.get();
         std::vector<uint32_t> counts(nl, 0u);
         if (nl > 0) {
-            RTK_HIP(hipMemcpyAsync(a->st_leaves, leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
+            RTK_HIP(hipMemcpyAsync(a->st_leaves.get(), leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
             RTK_HIP_AS(launch_occl_count(O, s), "launch k_occl_count");
             // the one place the call blocks after entry: one count per leaf
-            RTK_HIP(hipMemcpyAsync(counts.data(), a->st_counts, nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            RTK_HIP(hipMemcpyAsync(counts.data(), a->st_counts.get(), nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             RTK_HIP(hipStreamSynchronize(s));
         }
         // as ensure_device / update_impl: the same nodes, a leaf's a / b its run in the opaque copy, empty leaves kept as nodes
@@ -431,43 +359,37 @@ int rtk::remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &material
             if (n.b != 0u) oleaves.push_back(n);
         }
         if (oleaves.empty()) { DevNode n = onodes.empty() ? DevNode{} : onodes[0]; n.a = 0u; n.b = 0u; oleaves.push_back(n); }
-        void **sp = a->spare;
-        size_t *sc = a->spare_cap;
-        RTK_TRY(grow_dev(&sp[G_ONODES], &sc[G_ONODES], onodes.size() * sizeof(DevNode)));
-        RTK_TRY(grow_dev(&sp[G_OLEAVES], &sc[G_OLEAVES], oleaves.size() * sizeof(DevNode)));
-        RTK_TRY(grow_dev(&sp[G_OTRIS], &sc[G_OTRIS], std::max<size_t>(1, n_opaque) * sizeof(DevTri)));
-        RTK_TRY(grow_dev(&sp[G_OIDS], &sc[G_OIDS], std::max<size_t>(1, n_opaque) * sizeof(uint32_t)));
+        GeomBufs &sp = a->geom_spare;
+        RTK_MEM(sp.occl_nodes.reserve(onodes.size(), grow_bytes()));
+        RTK_MEM(sp.occl_leaves.reserve(oleaves.size(), grow_bytes()));
+        RTK_MEM(sp.occl_tris.reserve(std::max<size_t>(1, n_opaque), grow_bytes()));
+        RTK_MEM(sp.occl_ids.reserve(std::max<size_t>(1, n_opaque), grow_bytes()));
         // (pageable sources: these copies return when the data has left the host vectors)
-        if (!onodes.empty()) RTK_HIP(hipMemcpyAsync(sp[G_ONODES], onodes.data(), onodes.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
-        RTK_HIP(hipMemcpyAsync(sp[G_OLEAVES], oleaves.data(), oleaves.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
-        if (nl > 0) RTK_HIP(hipMemcpyAsync(a->st_leaves, leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
-        O.occl_tris = static_cast<DevTri *>(sp[G_OTRIS]); O.occl_ids = static_cast<uint32_t *>(sp[G_OIDS]); O.cap = uint32_t(n_opaque);
+        if (!onodes.empty()) RTK_HIP(hipMemcpyAsync(sp.occl_nodes.get(), onodes.data(), onodes.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
+        RTK_HIP(hipMemcpyAsync(sp.occl_leaves.get(), oleaves.data(), oleaves.size() * sizeof(DevNode), hipMemcpyHostToDevice, s));
+        if (nl > 0) RTK_HIP(hipMemcpyAsync(a->st_leaves.get(), leaves.data(), nl * sizeof(dev::OcclLeaf), hipMemcpyHostToDevice, s));
+        O.occl_tris = sp.occl_tris.get(); O.occl_ids = sp.occl_ids.get(); O.cap = uint32_t(n_opaque);
         if (n_opaque > 0) RTK_HIP_AS(launch_occl_gather(O, s), "launch k_occl_gather");
         else {                                                              // nothing opaque: keep the pointers valid, as ensure_device does
-            if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp[G_OTRIS], a->d_tris, sizeof(DevTri), hipMemcpyDeviceToDevice, s));
-            else RTK_HIP(hipMemsetAsync(sp[G_OTRIS], 0, sizeof(DevTri), s));
-            RTK_HIP(hipMemsetAsync(sp[G_OIDS], 0, sizeof(uint32_t), s));
+            if (n_refs > 0) RTK_HIP(hipMemcpyAsync(sp.occl_tris.get(), a->geom.tris.get(), sizeof(DevTri), hipMemcpyDeviceToDevice, s));
+            else RTK_HIP(hipMemsetAsync(sp.occl_tris.get(), 0, sizeof(DevTri), s));
+            RTK_HIP(hipMemsetAsync(sp.occl_ids.get(), 0, sizeof(uint32_t), s));
         }
-        if (a->up_opaque) { O.opaque = a->up_opaque; RTK_HIP_AS(launch_occl_flags(O, s), "launch k_occl_flags"); }
+        if (a->topo.opaque.get()) { O.opaque = a->topo.opaque.get(); RTK_HIP_AS(launch_occl_flags(O, s), "launch k_occl_flags"); }
         RTK_HIP(hipStreamSynchronize(s));                                   // (the host vectors above go out of scope)
-        RTK_HIP(hipEventRecord(a->geom_ready, s));
+        RTK_HIP(hipEventRecord(a->geom_ready.get(), s));
         // ---- nothing below fails
-        void **act[4] = {reinterpret_cast<void **>(&a->d_occl_nodes), reinterpret_cast<void **>(&a->d_occl_leaves),
-                         reinterpret_cast<void **>(&a->d_occl_tris), reinterpret_cast<void **>(&a->d_occl_ids)};
-        for (int i = G_ONODES; i <= G_OIDS; ++i) {
-            std::swap(*act[i - G_ONODES], a->spare[i]);
-            std::swap(a->active_cap[i], a->spare_cap[i]);
-        }
+        a->geom.swap_occl(sp);
         a->occl_n_leaves = uint32_t(oleaves.size());
         a->occl_on = true;
         a->geom_pending = true;
         return RTK_OK;
     }
     // the flags alone; a FAST accel that lost its last refractive material keeps the buffers for the next time
-    if (a->up_opaque) {
-        O.opaque = a->up_opaque;
+    if (a->topo.opaque.get()) {
+        O.opaque = a->topo.opaque.get();
         RTK_HIP_AS(launch_occl_flags(O, s), "launch k_occl_flags");
-        RTK_HIP(hipEventRecord(a->geom_ready, s));
+        RTK_HIP(hipEventRecord(a->geom_ready.get(), s));
         a->geom_pending = true;
     }
     if (tree) { a->occl_on = false; a->occl_n_leaves = 0u; }
@@ -496,9 +418,9 @@ int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
             if (!std::isfinite(vertices[i])) return fail(RTK_ERR_INVALID, "vertices must be finite");
         RTK_HIP(hipDeviceSynchronize());
         a->geom_pending = false;
-        if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));   // (the vertex count never changes)
-        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
-        return update_impl(a, a->up_verts, nullptr, nullptr);
+        RTK_MEM(a->up_verts.reserve(n));                                    // (once: the vertex count never changes)
+        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts.get(), vertices, n * sizeof(float), hipMemcpyHostToDevice));
+        return update_impl(a, a->up_verts.get(), nullptr, nullptr);
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }
 
@@ -537,11 +459,11 @@ int rtk_accel_update_geometry(rtk_accel *a, const float *vertices, const uint32_
         }
         RTK_HIP(hipDeviceSynchronize());
         a->geom_pending = false;
-        if (!a->up_verts) RTK_HIP(hipMalloc(reinterpret_cast<void **>(&a->up_verts), std::max<size_t>(1, n) * sizeof(float)));
-        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts, vertices, n * sizeof(float), hipMemcpyHostToDevice));
-        RTK_TRY(grow_dev(reinterpret_cast<void **>(&a->up_idx_stage), &a->up_idx_stage_cap, size_t(N.n_tris) * 3 * sizeof(uint32_t)));
-        if (N.n_tris > 0u) RTK_HIP(hipMemcpy(a->up_idx_stage, indices, size_t(N.n_tris) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
-        N.d_indices = a->up_idx_stage;
-        return update_impl(a, a->up_verts, &N, nullptr);
+        RTK_MEM(a->up_verts.reserve(n));
+        if (n > 0) RTK_HIP(hipMemcpy(a->up_verts.get(), vertices, n * sizeof(float), hipMemcpyHostToDevice));
+        RTK_MEM(a->up_idx_stage.reserve(size_t(N.n_tris) * 3, grow_bytes()));
+        if (N.n_tris > 0u) RTK_HIP(hipMemcpy(a->up_idx_stage.get(), indices, size_t(N.n_tris) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        N.d_indices = a->up_idx_stage.get();
+        return update_impl(a, a->up_verts.get(), &N, nullptr);
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }

@@ -16,6 +16,7 @@
 #include "stream.hpp"
 #include "build.hpp"
 #include "dev_mem.hpp"
+#include "frame_plan.hpp"
 
 // Environment knobs (all optional).  Read ONCE, when an accel is built: nothing on the launch path
 // calls getenv.
@@ -120,6 +121,23 @@ template <typename T> using PinBuf = Buf<T, PinnedMem>;
 using DevEvent = Event<EventSrc<hipEventDisableTiming>>;
 using TimedEvent = Event<EventSrc<hipEventDefault>>;
 
+// A workspace of the accel that calls on different streams share: its last user recorded `done` behind its last kernel, the next
+// user, on any stream, waits for that on the device before it touches the workspace.
+struct LastUse {
+    DevEvent done;
+    bool in_use = false;               // done has been recorded
+    hipError_t wait_previous(hipStream_t s) {
+        const hipError_t e = static_cast<hipError_t>(done.ensure());
+        return e == hipSuccess && in_use ? hipStreamWaitEvent(s, done.get(), 0) : e;
+    }
+    hipError_t record(hipStream_t s) {
+        hipError_t e = static_cast<hipError_t>(done.ensure());
+        if (e == hipSuccess) e = hipEventRecord(done.get(), s);
+        if (e == hipSuccess) in_use = true;
+        return e;
+    }
+};
+
 // The geometry of an accel exists twice, as two values of this struct: an update builds into the spare one and swaps it with
 // the active one at the end, so a failed update leaves the accel as it was and a steady animation allocates nothing.
 struct GeomBufs {
@@ -159,21 +177,16 @@ struct StreamBufs {
 };
 }  // namespace rtk
 
-// Per-pixel-block cost of the last frame of shape `sig`, and the launch order made from it.
+// Per-pixel-block cost of the last frame of shape `state.sig`, and the launch order made from it.
 struct rtk_cost_feedback {
     rtk::DevBuf<uint32_t> cost, order;
     rtk::DevBuf<uint8_t> bins;
-    size_t units = 0;
-    uint64_t sig[5] = {0, 0, 0, 0, 0};
-    bool valid = false;              // cost holds the costs of a frame of shape sig
-    bool order_valid = false;        // order was made from such costs
-    unsigned age = 0;                // frames rendered with the current order
+    rtk::OrderState state;           // what the tables hold (frame_plan.hpp)
     // number of workgroups in order's workgroup list, read back behind the sort that made it (pinned host word + event)
     rtk::PinBuf<uint32_t> nwgs_host;
     rtk::DevEvent nwgs_ev;
-    bool nwgs_pending = false, nwgs_known = false;
 
-    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; }
+    void forget() { state.forget(); }
 };
 
 struct rtk_accel {
@@ -210,17 +223,13 @@ struct rtk_accel {
     rtk::DevBuf<float> ws_sumbuf;
     rtk::dev::StreamWs ws = {};
     rtk::dev::StreamWs ws_lane[rtk::dev::kStreamLanes] = {};
-    int ws_lanes = 0;
-    size_t ws_pixels = 0, ws_lights = 0, ws_nodes = 0;
-    bool ws_sum = false;
+    rtk::StreamWsShape ws_shape;                                // what they have room for (frame_plan.hpp)
     hipStream_t lane_stream[rtk::dev::kStreamLanes] = {};       // the process's (api_frame.hip LaneStreams): not freed with an accel
     rtk::DevEvent lane_done[rtk::dev::kStreamLanes];
     rtk::DevEvent lane_fork;
     struct SideEvents { rtk::DevEvent ready[2], done[2]; } lane_side_ev[rtk::dev::kStreamLanes];
     rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane (the process's) and views of lane_side_ev
-    // the streaming workspace's last user (a STREAM frame or a radiance batch) recorded ws_done: the next one on any stream waits for it
-    rtk::DevEvent ws_done;
-    bool ws_in_use = false;
+    rtk::LastUse ws_last;                                       // of a STREAM frame or a radiance batch
     // ---- tp_*: two-pass workspace (api_frame.hip ensure_twopass_ws)
     rtk::DevBuf<float4> tp_prim;
     rtk::DevBuf<uint32_t> tp_bins;     // [kCostBins] counts, [1] n_listed
@@ -246,24 +255,21 @@ struct rtk_accel {
     size_t rg_limit = 0;                       // the launch limit the table on the device was cut with
     rtk::DevBuf<rtk::RegionEntry> rg_table;    // the entries of all launches of the call, one behind the other
     bool rg_table_valid = false;               // rg_table holds the plan of rg_rects
-    rtk::DevEvent rg_done;                     // recorded behind a call's last kernel: the next table upload, on any stream, waits for it
-    bool rg_in_use = false;
+    rtk::LastUse rg_last;                      // of rg_table by a call's kernels: the next table upload waits for it
     rtk::DevBuf<rtk_ray> rg_rays;              // streaming path: rays, frame pixel indices and colours of one chunk of pixels
     rtk::DevBuf<uint32_t> rg_ids;
     rtk::DevBuf<float> rg_rgb;
     rtk::DevBuf<float> rg_out;                 // staging of the host variant
-    // ---- trial_*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
+    // ---- trial*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     rtk::TimedEvent trial_ev[4];
-    uint64_t trial_sig[3] = {0, 0, 0};
-    int trial_state = 0;
+    rtk::EngineTrial trial;
     // ---- rp_*: ray repacking workspace (batched intersect: api_batch.hip, repack.hip)
     rtk::DevBuf<uint32_t> rp_bounds, rp_keys, rp_idx;
     rtk::DevBuf<uint8_t> rp_temp;
     size_t rp_temp_bytes = 0;
     rtk::PinBuf<uint32_t> rp_host;   // pinned: the probe's words as the host sees them
     rtk::DevEvent rp_probe_ev;
-    rtk::DevEvent rp_done;           // recorded behind the k_intersect that walks rp_idx: the next repack on any stream waits for it
-    bool rp_in_use = false;
+    rtk::LastUse rp_last;            // of rp_idx by the k_intersect that walks it: the next repack waits for it
     // ---- oc_*: staging of the host variant of the occlusion batch (rtk_accel_occluded, api_batch.hip): grows, never shrinks
     rtk::DevBuf<rtk_ray> oc_rays;
     rtk::DevBuf<float> oc_max_t;
@@ -350,12 +356,10 @@ inline int stream_slices_for(const HostTree &t) {     // rtk_accel.stream_slices
     return (refs > 0.0 && sq / refs < 150.0) ? 1 : 4;
 }
 
-struct FrameGeom {
-    uint32_t width, height, bucket, tiles_x, tiles_y, n_buckets, blocks_side, buckets_per_rank;
-    uint32_t skew_q;                   // kernels.hpp rank_bucket(): 0 = round robin, else tiles_x / world (diagonal deal)
-    int rank, world;
-    int sample_begin, sample_end;      // this call renders samples [sample_begin, sample_end) (rtk_render_params.sample_begin/_count)
-};
+// whether the ray trees of a frame or batch fork (refraction, diffuse GI) ...
+inline bool scene_forks(const rtk_accel *a, int diffuse_rays) { return a->has_refractive || diffuse_rays > 0; }
+// ... and whether it needs the general build of the kernels (+ refraction, diffuse GI, textures) and not the lean one
+inline bool scene_general(const rtk_accel *a, int diffuse_rays) { return scene_forks(a, diffuse_rays) || !a->scene.textures.empty(); }
 
 // api.hip
 // `s`: the stream the caller is about to issue work on.  It waits for the geometry of the last rtk_accel_update_vertices

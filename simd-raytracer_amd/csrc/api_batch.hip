@@ -49,9 +49,8 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
     if ((forced && sortable) || probe) {
         RTK_TRY(ensure_repack_ws(a, n));
         // The workspace (bounds, keys, permutation) belongs to the accel: a batch on another stream may still be walking the
-        // permutation of the previous call.  Its k_intersect recorded rp_done; this stream waits for it before it rewrites anything.
-        RTK_MEM(a->rp_done.ensure());
-        if (a->rp_in_use) RTK_HIP(hipStreamWaitEvent(s, a->rp_done.get(), 0));
+        // permutation of the previous call.  Its k_intersect recorded rp_last; this stream waits for it before it rewrites anything.
+        RTK_HIP(a->rp_last.wait_previous(s));
         hipError_t eb = hipSuccess;
         bool sort = forced;
         unsigned sort_from_bit = 0u;
@@ -74,7 +73,6 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
             dev::IntersectArgs Spec = A;
             Spec.verdict = a->rp_bounds.get();
             RTK_HIP_AS(launch_intersect(Spec, RTK_TRACE_WAVE, false, s), "launch k_intersect");
-            a->rp_in_use = true;
             // ... and so are the keys a batch to be sorted needs (k_ray_keys returns at once if it is not): the verdict's trip to the
             // host and the launches that follow it no longer leave the stream idle
             if (!a->knobs.repack_full_bounds) {
@@ -82,7 +80,7 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
                 if (eb != hipSuccess) return hip_fail(eb, "launch k_ray_keys");
                 keys_made = true;
             }
-            RTK_HIP(hipEventRecord(a->rp_done.get(), s));                         // (both read the workspace's verdict words)
+            RTK_HIP(a->rp_last.record(s));                                        // (both read the workspace's verdict words)
             RTK_HIP(hipEventSynchronize(a->rp_probe_ev.get()));                   // the verdict, not the trace
             sort = rp_host[16] != 0u;
             if (!sort) return RTK_OK;                                        // coherent as it comes: that launch was the batch
@@ -108,10 +106,7 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
         }
     }
     RTK_HIP_AS(launch_intersect(A, mode, stats, s), "launch k_intersect");
-    if (A.perm != nullptr) {
-        RTK_HIP(hipEventRecord(a->rp_done.get(), s));
-        a->rp_in_use = true;
-    }
+    if (A.perm != nullptr) RTK_HIP(a->rp_last.record(s));
     return RTK_OK;
 }
 

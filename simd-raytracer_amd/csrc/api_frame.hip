@@ -71,25 +71,22 @@ void free_stream_ws(rtk_accel *a) {
     a->ws_sumbuf.reset();
     for (int j = 0; j < dev::kStreamLanes; ++j) { a->ws_bufs[j].reset(); a->ws_lane[j] = dev::StreamWs{}; }
     a->ws = a->ws_lane[0];
-    a->ws_lanes = 0; a->ws_pixels = 0; a->ws_nodes = 0; a->ws_lights = 0; a->ws_sum = false;
+    a->ws_shape = StreamWsShape{};
 }
 
 // (Re)allocates the streaming workspace for `pixels` output pixels.  Allocation synchronises the device, so it only
 // happens when a larger frame (or more lights / multi-sample) is requested than ever before on this accel.
 int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes) {
-    if (lights == 0) lights = 1;
-    if (lanes < 1) lanes = 1;
-    if (pixels <= a->ws_pixels && nodes <= a->ws_nodes && lights <= a->ws_lights && (!need_sum || a->ws_sum) && lanes <= a->ws_lanes) return RTK_OK;
-    const size_t np = pixels > a->ws_pixels ? pixels : a->ws_pixels;
-    const size_t nn = nodes > a->ws_nodes ? nodes : a->ws_nodes;
-    const size_t nl = lights > a->ws_lights ? lights : a->ws_lights;
-    const int nlanes = lanes > a->ws_lanes ? lanes : a->ws_lanes;
-    const bool sum = need_sum || a->ws_sum;
-    if (nn > 0xFFFFFFF0ull) return fail(RTK_ERR_INVALID, "frame too large for the streaming pipeline's 32-bit node ids");
+    StreamWsShape request;
+    request.pixels = pixels; request.nodes = nodes; request.lights = lights; request.lanes = lanes; request.sum = need_sum;
+    if (a->ws_shape.covers(request)) return RTK_OK;
+    const StreamWsShape shape = a->ws_shape.grown(request);
+    if (shape.refused()) return fail(RTK_ERR_INVALID, "frame too large for the streaming pipeline's 32-bit node ids");
     RTK_HIP(hipDeviceSynchronize());
     free_stream_ws(a);
-    const size_t nh = nn / 2 + 64;                            // every shading point belongs to a distinct node
-    if (sum) RTK_MEM(a->ws_sumbuf.reserve(np * 3));
+    const size_t np = shape.pixels, nn = shape.nodes, nl = shape.lights, nh = StreamWsShape::hit_cap(nn);
+    const int nlanes = shape.lanes;
+    if (shape.sum) RTK_MEM(a->ws_sumbuf.reserve(np * 3));
     for (int j = 0; j < nlanes; ++j) {
         StreamBufs &b = a->ws_bufs[j];
         RTK_MEM(b.rays.reserve(nn));
@@ -118,7 +115,7 @@ int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, b
         a->lane_side[j].stream[0] = L->side[j][0]; a->lane_side[j].stream[1] = L->side[j][1];
     }
     a->ws = a->ws_lane[0];
-    a->ws_lanes = nlanes; a->ws_pixels = np; a->ws_nodes = nn; a->ws_lights = nl; a->ws_sum = sum;
+    a->ws_shape = shape;
     return RTK_OK;
 }
 
@@ -184,6 +181,11 @@ dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
     return A;
 }
 
+// the counters of a frame or a part of a call start at zero: the kCounterWords and k_block_prior's four behind them
+hipError_t zero_counters(rtk_accel *a, hipStream_t s) {
+    return hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s);
+}
+
 // the accel's own camera: the scene's at rtk_accel_build, then whatever rtk_accel_set_camera stored there
 rtk_view accel_camera(const rtk_accel *a) {
     rtk_view v;
@@ -241,13 +243,8 @@ StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffus
 }
 
 // the queues belong to the accel: whoever used them last (a STREAM frame, a batch on another stream) finishes first, on the device
-int claim_stream_ws(rtk_accel *a, hipStream_t s) {
-    RTK_MEM(a->ws_done.ensure());
-    if (a->ws_in_use) RTK_HIP(hipStreamWaitEvent(s, a->ws_done.get(), 0));
-    a->ws_in_use = true;
-    return RTK_OK;
-}
-int release_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(hipEventRecord(a->ws_done.get(), s)); return RTK_OK; }
+int claim_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(a->ws_last.wait_previous(s)); return RTK_OK; }
+int release_stream_ws(rtk_accel *a, hipStream_t s) { RTK_HIP(a->ws_last.record(s)); return RTK_OK; }
 
 // fork: lane 0 is the caller's stream, the other lanes wait for everything enqueued on it so far
 int fork_lanes(rtk_accel *a, int lanes, hipStream_t s) {
@@ -262,44 +259,37 @@ int join_lanes(rtk_accel *a, int lanes, hipStream_t s) {
 }
 
 // fresh queues: their first use is not what a frame costs -- time the pipeline on the next frame instead
-void trial_abandon(rtk_accel *a, hipEvent_t trial[2]) { trial[0] = trial[1] = nullptr; a->trial_state = 0; }
+void trial_abandon(rtk_accel *a, hipEvent_t trial[2]) { trial[0] = trial[1] = nullptr; a->trial.abandon(); }
 
 // RTK_TRACE_AUTO for frames: fork-free scenes go through the GROUP4 megakernel; on scenes whose ray
 // trees fork (refraction, diffuse GI) which engine wins depends on how much of the frame forks, so both are timed on the first
-// frames of a shape: frame 1 pipeline, frames 2-3 megakernel (the second one with its cost-feedback order), then the verdict as
-// soon as the events have completed (hipEventQuery, never a host wait).  `trial`: {start, end} to record around the engine, or null.
+// frames of a shape (frame_plan.hpp EngineTrial), then the verdict as soon as the events have completed (hipEventQuery, never a
+// host wait).  `trial`: {start, end} to record around the engine, or null.
 int choose_engine(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, bool forks, bool &stream, hipEvent_t trial[2]) {
     stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
-    if (p->trace_mode == RTK_TRACE_AUTO && forks && !p->collect_stats) {
-        const uint64_t tsig[3] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height), (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
-                                  (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays)};
-        if (std::memcmp(tsig, a->trial_sig, sizeof(tsig)) != 0) { std::memcpy(a->trial_sig, tsig, sizeof(tsig)); a->trial_state = 0; }
-        if (a->knobs.auto_trials) {
-            for (TimedEvent &e : a->trial_ev) RTK_MEM(e.ensure());
-            if (a->trial_state == 3) {                                      // both timed: is the verdict in?
-                float t_stream = 0.f, t_mega = 0.f;
-                if (hipEventQuery(a->trial_ev[1].get()) == hipSuccess && hipEventQuery(a->trial_ev[3].get()) == hipSuccess &&
-                    hipEventElapsedTime(&t_stream, a->trial_ev[0].get(), a->trial_ev[1].get()) == hipSuccess &&
-                    hipEventElapsedTime(&t_mega, a->trial_ev[2].get(), a->trial_ev[3].get()) == hipSuccess)
-                    a->trial_state = t_mega < t_stream ? 5 : 4;
-                else (void)hipGetLastError();                               // not ready yet: clear the sticky "not ready"
-            }
-            switch (a->trial_state) {
-                case 0: stream = true; trial[0] = a->trial_ev[0].get(); trial[1] = a->trial_ev[1].get(); a->trial_state = 1; break;
-                case 1: stream = false; a->trial_state = 2; break;          // first megakernel frame: records the block costs
-                case 2: stream = false; trial[0] = a->trial_ev[2].get(); trial[1] = a->trial_ev[3].get(); a->trial_state = 3; break;
-                case 5: stream = false; break;
-                default: stream = true; break;                              // 3 (waiting for the events), 4 (pipeline won)
-            }
+    if (!EngineTrial::applies(p->trace_mode, forks, p->collect_stats != 0)) return RTK_OK;
+    uint64_t tsig[3];
+    shape_sig(g, p->spp, p->max_ray_depth, p->diffuse_rays, tsig);
+    if (a->knobs.auto_trials) {
+        for (TimedEvent &e : a->trial_ev) RTK_MEM(e.ensure());
+        if (a->trial.waiting(tsig)) {                                       // both timed: is the verdict in?
+            float t_stream = 0.f, t_mega = 0.f;
+            if (hipEventQuery(a->trial_ev[1].get()) == hipSuccess && hipEventQuery(a->trial_ev[3].get()) == hipSuccess &&
+                hipEventElapsedTime(&t_stream, a->trial_ev[0].get(), a->trial_ev[1].get()) == hipSuccess &&
+                hipEventElapsedTime(&t_mega, a->trial_ev[2].get(), a->trial_ev[3].get()) == hipSuccess)
+                a->trial.verdict(t_stream, t_mega);
+            else (void)hipGetLastError();                                   // not ready yet: clear the sticky "not ready"
         }
     }
+    const EngineTrial::Step step = a->trial.next(tsig, a->knobs.auto_trials);
+    stream = step.stream;
+    if (step.record != EngineTrial::kNoRecord) { trial[0] = a->trial_ev[step.record].get(); trial[1] = a->trial_ev[step.record + 1].get(); }
     return RTK_OK;
 }
 
 int render_twopass(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general, hipStream_t s) {
     if (p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
-    const size_t tiles = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
-    RTK_TRY(ensure_twopass_ws(a, out_pixels(g), tiles));
+    RTK_TRY(ensure_twopass_ws(a, out_pixels(g), g.blocks()));
     A.prim = a->tp_prim.get(); A.bin_count = a->tp_bins.get(); A.n_listed = a->tp_bins.get() + kCostBins; A.bin_list = a->tp_bin_list.get();
     A.tile_order = a->tp_order.get(); A.tile_cap = uint32_t(a->tp_tiles);
     RTK_HIP_AS(launch_twopass(A, p->collect_stats != 0, general, s), "launch two-pass frame");
@@ -310,15 +300,14 @@ int render_twopass(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g,
 int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const dev::RenderArgs &A, bool forks, bool general,
                   hipEvent_t trial[2], hipStream_t s) {
     StreamSetup u = stream_args(a, A, p->diffuse_rays, forks);
-    const size_t n_root = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side * 64;
+    const size_t n_root = g.blocks() * 64;
     const size_t nodes_per_sample = n_root * u.factor + 4096;
     const FramePlan plan = plan_frame_batches(g.sample_end - g.sample_begin, nodes_per_sample, u.node_bytes, u.budget,
                                               a->knobs.stream_lanes, a->knobs.stream_batch);
     const int batch = plan.batch, lanes = plan.lanes;
-    const size_t ws_nodes_before = a->ws_nodes;
-    const int ws_lanes_before = a->ws_lanes;
+    const StreamWsShape ws_before = a->ws_shape;
     RTK_TRY(ensure_stream_ws(a, out_pixels(g), nodes_per_sample * size_t(batch), a->scene.lights.size(), p->spp > 1, lanes));
-    if (trial[0] && (a->ws_nodes != ws_nodes_before || a->ws_lanes != ws_lanes_before)) trial_abandon(a, trial);
+    if (trial[0] && (a->ws_shape.nodes != ws_before.nodes || a->ws_shape.lanes != ws_before.lanes)) trial_abandon(a, trial);
     if (trial[0]) RTK_HIP(hipEventRecord(trial[0], s));
     dev::StreamArgs &S = u.S;
     S.ws = a->ws; S.n_root = uint32_t(n_root); S.n_level0 = uint32_t(n_root);
@@ -368,19 +357,48 @@ int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, 
 
 // (capacity, never shrunk)
 int ensure_feedback_ws(rtk_accel *a, rtk_cost_feedback &fb, const FrameGeom &g, size_t units) {
-    if (fb.units >= units) return RTK_OK;
-    // (the first allocation of the frames' tables also covers the scene's own frame size, so that a small frame
-    // rendered first -- a warm-up -- does not leave three allocations, ~0.1 ms, in front of the first full-size frame)
-    size_t cap = units;
-    const uint32_t bk = g.bucket, bs = g.blocks_side;
+    if (fb.state.units >= units) return RTK_OK;
+    const uint32_t bk = g.bucket;
     const uint64_t tx = (uint64_t(a->scene.width > 0 ? a->scene.width : 0) + bk - 1) / bk, ty = (uint64_t(a->scene.height > 0 ? a->scene.height : 0) + bk - 1) / bk;
-    const uint64_t native = tx * ty * bs * bs;
-    if (&fb == &a->fb && fb.units == 0 && native > cap && native <= (1ull << 24)) cap = size_t(native);
-    fb.units = 0; fb.valid = false; fb.order_valid = false;
+    const size_t cap = fb.state.capacity(units, &fb == &a->fb, g.blocks_of(tx * ty));
     RTK_MEM(fb.cost.reserve(cap));
     RTK_MEM(fb.order.reserve(2 * cap + 4 + 8));                       // order, header, workgroup list, prior's counters
     RTK_MEM(fb.bins.reserve(cap));
-    fb.units = cap;
+    fb.state.units = cap;
+    return RTK_OK;
+}
+
+// The launch order of a megakernel launch of `units` units: what fb.state (frame_plan.hpp OrderState) says this frame's is made
+// from is launched here, in front of the frame, and handed to the kernel in A.
+int order_launch(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, int frame_mode,
+                 size_t units, hipStream_t s) {
+    uint64_t sig[5];
+    shape_sig(g, p->spp, p->max_ray_depth, p->diffuse_rays, sig);
+    sig[3] = (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode);
+    sig[4] = A.regions ? ((1ull << 63) | (uint64_t(A.n_regions) << 32) | uint64_t(A.n_units))   // (its list is compared by the caller)
+                       : (A.views ? uint64_t(A.n_views) : 0ull);                                // (0: a frame; a views launch of one view is not one)
+    RTK_TRY(ensure_feedback_ws(a, fb, g, units));
+    uint32_t *const order = fb.order.get(), *const order_hdr = order + units, *const wg_list = order + units + 4;
+    const OrderState::Step step = fb.state.step(sig, frame_mode, p->collect_stats != 0, A.regions != nullptr,
+                                                {a->knobs.first_frame_prior, a->knobs.resort_every});
+    // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at.  A one-shot
+    // render is exactly this frame: the reference CLI renders one, src/main.cpp:13-25)
+    if (step.prior)
+        RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), order, wg_list, order_hdr,
+                                      reinterpret_cast<uint32_t *>(a->d_counters.get() + kCounterWords), 4u, s), "launch k_block_prior");
+    if (step.resort) {
+        // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
+        RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), order, wg_list, order_hdr, uint32_t(units),
+                                        frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
+                   "launch k_order_by_cost");
+        // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
+        RTK_MEM(fb.nwgs_host.reserve(1));
+        RTK_MEM(fb.nwgs_ev.ensure());
+        RTK_HIP(hipMemcpyAsync(fb.nwgs_host.get(), order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        RTK_HIP(hipEventRecord(fb.nwgs_ev.get(), s));
+    }
+    if (step.use_order) { A.order_in = order; A.order_hdr = order_hdr; A.wg_list = wg_list; }
+    A.cost_out = fb.cost.get();
     return RTK_OK;
 }
 
@@ -392,67 +410,19 @@ int ensure_feedback_ws(rtk_accel *a, rtk_cost_feedback &fb, const FrameGeom &g, 
 // together; `fb` is then that launch's own set of tables.
 int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general,
                       hipStream_t s) {
-    const size_t per_view = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;
     // (a regions launch, rtk_render_regions, comes with its units counted: the blocks of its rectangles)
-    const size_t units = A.regions ? size_t(A.n_units) : (A.views ? per_view * A.n_views : per_view);
+    const size_t units = A.regions ? size_t(A.n_units) : (A.views ? g.blocks() * A.n_views : g.blocks());
     A.n_units = uint32_t(units);
-    // RTK_TRACE_AUTO for frames: four waves per pixel block when there are enough blocks to fill the chip several times over,
-    // eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
-    // Measured on config 2 (tools/rank_times.py): 32,400 blocks 0.44 ms (GROUP4) vs 0.87 (GROUP8); 4,050 blocks 0.43 vs 0.32.
-    // (A views launch counts the blocks of all its views: many small views get the four-wave workgroups.)
-    const int frame_mode = p->trace_mode != RTK_TRACE_AUTO ? p->trace_mode : (units < a->knobs.group8_below ? RTK_TRACE_GROUP8 : RTK_TRACE_GROUP4);
+    const int frame_mode = OrderState::frame_mode(p->trace_mode, units, a->knobs.group8_below);
     if (a->knobs.cost_feedback && units > 0 && units <= 0x7FFFFFFFull) {
-        const uint64_t sig[5] = {(uint64_t(uint32_t(g.width)) << 32) | uint32_t(g.height),
-                                 (uint64_t(uint32_t(g.rank)) << 32) | uint32_t(g.world),
-                                 (uint64_t(uint32_t(p->spp)) << 32) | (uint64_t(uint32_t(p->max_ray_depth)) << 16) | uint32_t(p->diffuse_rays),
-                                 (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode),
-                                 A.regions ? ((1ull << 63) | (uint64_t(A.n_regions) << 32) | uint64_t(A.n_units))   // (its list is compared by the caller)
-                                           : (A.views ? uint64_t(A.n_views) : 0ull)};   // (0: a frame; a views launch of one view is not one)
-        RTK_TRY(ensure_feedback_ws(a, fb, g, units));
-        uint32_t *const order = fb.order.get(), *const order_hdr = order + units, *const wg_list = order + units + 4;
-        auto use_order = [&] { A.order_in = order; A.order_hdr = order_hdr; A.wg_list = wg_list; };
-        const bool same_shape = fb.valid && std::memcmp(sig, fb.sig, sizeof(sig)) == 0;
-        if (!same_shape) fb.order_valid = false;
-        // The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in for them
-        // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at).
-        // A one-shot render is exactly this frame (the reference CLI renders one, src/main.cpp:13-25).
-        // (the first launch of a new rectangle list runs in the natural order: k_block_prior maps units through the buckets)
-        const bool prior = !same_shape && a->knobs.first_frame_prior && frame_mode == RTK_TRACE_GROUP4 && p->collect_stats == 0 && !A.regions;
-        if (prior) {
-            RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), order, wg_list, order_hdr,
-                                          reinterpret_cast<uint32_t *>(a->d_counters.get() + kCounterWords), 4u, s), "launch k_block_prior");
-            use_order();
-        }
-        if (same_shape) {
-            // The order is refreshed from the newest costs every few frames only: the sort is one small workgroup whose
-            // ~28 us sit in front of the frame, and an order that is a few frames old is as good (costs move slowly).
-            if (!fb.order_valid || fb.age >= a->knobs.resort_every) {
-                // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
-                RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), order, wg_list, order_hdr, uint32_t(units),
-                                                frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
-                           "launch k_order_by_cost");
-                fb.order_valid = true;
-                fb.age = 0;
-                // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
-                RTK_MEM(fb.nwgs_host.reserve(1));
-                RTK_MEM(fb.nwgs_ev.ensure());
-                fb.nwgs_known = false;
-                RTK_HIP(hipMemcpyAsync(fb.nwgs_host.get(), order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                RTK_HIP(hipEventRecord(fb.nwgs_ev.get(), s));
-                fb.nwgs_pending = true;
-            }
-            fb.age += 1;
-            use_order();
-        }
-        A.cost_out = fb.cost.get();
-        std::memcpy(fb.sig, sig, sizeof(sig));
-        fb.valid = true;
+        const int rc = order_launch(a, fb, p, g, A, frame_mode, units, s);
+        if (rc != RTK_OK) { fb.forget(); return rc; }                     // (the state ran ahead of the launches)
     }
     unsigned n_wgs = 0;
-    if (A.wg_list != nullptr && A.order_in == fb.order.get() && fb.order_valid) {
-        if (fb.nwgs_pending && hipEventQuery(fb.nwgs_ev.get()) == hipSuccess) { fb.nwgs_pending = false; fb.nwgs_known = true; }
-        else if (fb.nwgs_pending) (void)hipGetLastError();            // not ready: clear the sticky status
-        if (fb.nwgs_known && !fb.nwgs_pending) n_wgs = *fb.nwgs_host.get();
+    if (A.wg_list != nullptr) {
+        bool ready = false;
+        if (fb.state.awaits_count() && !(ready = hipEventQuery(fb.nwgs_ev.get()) == hipSuccess)) (void)hipGetLastError();   // not ready: clear the sticky status
+        n_wgs = fb.state.workgroups(ready, fb.nwgs_host.get());
     }
     RTK_HIP_AS(launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs), "launch k_render");
     return RTK_OK;
@@ -477,11 +447,10 @@ dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const
 // of the launch arguments, so frames already enqueued keep theirs.
 int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out, hipStream_t s) {
     dev::RenderArgs A = frame_args(a, p, g, cam, d_out);
-    const bool forks = a->has_refractive || p->diffuse_rays > 0;
     // the megakernel comes in two builds: the lean one (diffuse / reflective / constant materials only) and the general one
     // (template FORKS: + refraction, diffuse GI, textures), so that the lean one does not carry the general one's registers
-    const bool general = forks || !a->scene.textures.empty();
-    RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+    const bool forks = scene_forks(a, p->diffuse_rays), general = scene_general(a, p->diffuse_rays);
+    RTK_HIP(zero_counters(a, s));
     // buckets past the end of the frame (padding so that every rank has equal length) stay zero
     if (g.world > 1 && g.sample_begin == 0) RTK_HIP(hipMemsetAsync(d_out, 0, out_pixels(g) * 3 * sizeof(float), s));
     bool stream = false;
@@ -518,7 +487,7 @@ int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d_out, h
 bool views_one_launch(const rtk_accel *a, const rtk_render_params *p) {
     if (p->collect_stats != 0) return false;
     if (p->trace_mode == RTK_TRACE_GROUP4 || p->trace_mode == RTK_TRACE_GROUP8 || p->trace_mode == RTK_TRACE_GROUP16) return true;
-    return p->trace_mode == RTK_TRACE_AUTO && !(a->has_refractive || p->diffuse_rays > 0);
+    return p->trace_mode == RTK_TRACE_AUTO && !scene_forks(a, p->diffuse_rays);
 }
 
 int views_check(const rtk_accel *a, const rtk_render_params *p, const void *views, int32_t n_views, const void *out, FrameGeom &g) {
@@ -542,7 +511,7 @@ struct CallCounters {
         RTK_HIP(hipMemsetAsync(a->d_views_counters.get(), 0, kCounterWords * sizeof(unsigned long long), s));
         return RTK_OK;
     }
-    int zero_part() { RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s)); return RTK_OK; }   // (a frame zeroes its own)
+    int zero_part() { RTK_HIP(zero_counters(a, s)); return RTK_OK; }   // (a frame zeroes its own)
     int after_part() { if (many) RTK_HIP_AS(launch_counters_fold(a->d_counters.get(), a->d_views_counters.get(), s), "launch k_counters_fold"); return RTK_OK; }
     int end() {
         if (many) RTK_HIP(hipMemcpyAsync(a->d_counters.get(), a->d_views_counters.get(), kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
@@ -557,12 +526,12 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
     const size_t n = size_t(n_views);
     size_t n_parts = n;
     if (views_one_launch(a, p)) {
-        const size_t per_view = size_t(g.buckets_per_rank) * g.blocks_side * g.blocks_side;       // <= 2^26: a launch of one view fits 31 bits
-        const size_t limit = a->knobs.views_launch_units;
-        const size_t per_launch = per_view >= limit ? 1 : limit / per_view;
-        n_parts = (n + per_launch - 1) / per_launch;
+        const size_t per_view = g.blocks();                                                       // <= 2^26: a launch of one view fits 31 bits
+        const ViewsLaunches cut = views_launches(n, per_view, a->knobs.views_launch_units);
+        const size_t per_launch = cut.per_launch;
+        n_parts = cut.n_parts;
         if (a->fb_views.size() < n_parts) a->fb_views.resize(n_parts);
-        const bool general = a->has_refractive || p->diffuse_rays > 0 || !a->scene.textures.empty();
+        const bool general = scene_general(a, p->diffuse_rays);
         CallCounters cc{a, n_parts > 1, s};
         RTK_TRY(cc.begin());
         for (size_t c = 0; c < n_parts; ++c) {
@@ -623,7 +592,7 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
     A.gi_div_f = static_cast<float>(p->diffuse_rays + 1);
     A.shadow_bias = p->shadow_bias; A.reflection_bias = p->reflection_bias; A.refraction_bias = p->refraction_bias;
     A.world = 1;
-    const bool forks = a->has_refractive || p->diffuse_rays > 0;
+    const bool forks = scene_forks(a, p->diffuse_rays);
     StreamSetup u = stream_args(a, A, p->diffuse_rays, forks);
     const RadiancePlan plan = plan_radiance_chunks(n, u.factor, u.node_bytes, u.budget, a->knobs.stream_lanes);
     const int lanes = plan.lanes;
@@ -706,12 +675,11 @@ int regions_table(rtk_accel *a, const FrameGeom &g, const rtk_rect *rects, size_
     for (rtk_cost_feedback &f : a->fb_regions) f.forget();
     a->rg_plan = plan_regions(rects, n, layout, g.width, limit);
     const size_t n_entries = a->rg_plan.entries.size();
-    RTK_MEM(a->rg_done.ensure());
     if (a->rg_table.capacity() < n_entries) {
         RTK_HIP(hipDeviceSynchronize());
         RTK_MEM(a->rg_table.reserve(n_entries, grow_table()));
-    } else if (a->rg_in_use) {
-        RTK_HIP(hipStreamWaitEvent(s, a->rg_done.get(), 0));                // a call on another stream may still be reading the old table
+    } else {
+        RTK_HIP(a->rg_last.wait_previous(s));                               // a call on another stream may still be reading the old table
     }
     RTK_HIP(hipMemcpyAsync(a->rg_table.get(), a->rg_plan.entries.data(), n_entries * sizeof(RegionEntry), hipMemcpyHostToDevice, s));
     a->rg_rects.assign(rects, rects + n);
@@ -725,8 +693,7 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
                         float *d_out, hipStream_t s) {
     RTK_TRY(regions_table(a, g, rects, size_t(n_rects), layout, s));
     const RegionsPlan &P = a->rg_plan;
-    const bool forks = a->has_refractive || p->diffuse_rays > 0;
-    const bool general = forks || !a->scene.textures.empty();
+    const bool forks = scene_forks(a, p->diffuse_rays), general = scene_general(a, p->diffuse_rays);
     const bool stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
     dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_out);
     if (!stream) {
@@ -761,7 +728,7 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
         rp.max_ray_depth = p->max_ray_depth; rp.diffuse_rays = p->diffuse_rays; rp.seed = p->seed; rp.sample = 0;
         rp.shadow_bias = p->shadow_bias; rp.reflection_bias = p->reflection_bias; rp.refraction_bias = p->refraction_bias;
         rp.cull = 1; rp.trace_mode = RTK_TRACE_STREAM;
-        RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s));
+        RTK_HIP(zero_counters(a, s));
         for (const RegionLaunch &L : P.launches) {
             A.regions = a->rg_table.get() + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
             for (uint64_t first = 0; first < L.n_pixels; first += chunk) {
@@ -776,8 +743,7 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
             }
         }
     }
-    RTK_HIP(hipEventRecord(a->rg_done.get(), s));
-    a->rg_in_use = true;
+    RTK_HIP(a->rg_last.record(s));
     a->last_stream = s;
     a->last_stats = false;
     a->last_primary = P.total_pixels * uint64_t(g.sample_end - g.sample_begin);

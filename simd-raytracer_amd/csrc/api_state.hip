@@ -135,7 +135,7 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
         a->fb.forget();
         for (rtk_cost_feedback &f : a->fb_views) f.forget();
         for (rtk_cost_feedback &f : a->fb_regions) f.forget();
-        a->trial_state = 0;
+        a->trial.abandon();
         return RTK_OK;
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }

@@ -287,7 +287,7 @@ int update_impl(rtk_accel *a, const float *d_verts, const NewTopology *topo, hip
     a->fb.forget();
     for (rtk_cost_feedback &f : a->fb_views) f.forget();
     for (rtk_cost_feedback &f : a->fb_regions) f.forget();
-    a->trial_state = 0;
+    a->trial.abandon();
     return RTK_OK;
 }
 

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import CONFIG_SCENES, SCENE2, SCENE5, SCENE8
+from small_scenes import two_quad_scene
+from update_checks import _rtk_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -389,6 +391,23 @@ def test_cost_feedback_reorders_blocks_but_not_results(rtk, ora, mode):
         torch.cuda.synchronize()
         outs.append(buf.cpu().numpy())
     assert np.array_equal(_bits(outs[0]), _bits(outs[1])) and np.array_equal(_bits(outs[0]), _bits(outs[2]))
+
+
+def test_launch_decisions_past_the_second_resort_change_no_frame(rtk, ora):
+    """The decisions of csrc/frame_plan.hpp that the frames above never reach, with the default knobs: 20 GROUP4 frames of one
+    shape (prior, sort at 2, the read-back workgroup count shortening the launch from 4 on, the re-sort at 18 and the count
+    of the new list), one frame of another shape, three more of the first (prior, sort, reuse).  44x28 is one bucket of 64
+    units with ragged blocks at both edges.  Every frame is the oracle's, bits and rays."""
+    flat = two_quad_scene(ora)
+    acc = rtk.KdTreeSimdAccel(_rtk_scene(rtk, flat))
+    oacc = ora.Accel(ora.Scene(flat), ora.ACCEL_KD_SIMD)
+    shapes = {(w, h): oacc.render(w, h, 1, 5, 0) for w, h in ((44, 28), (24, 20))}
+    assert len(np.unique(_bits(shapes[(44, 28)][0]).reshape(-1, 3), axis=0)) > 8          # floor, mirror and background
+    for i, (w, h) in enumerate([(44, 28)] * 20 + [(24, 20)] + [(44, 28)] * 3):
+        rgb, cn = acc.render_frame(rtk.RenderConfig(width=w, height=h, max_ray_depth=5, trace_mode=FRAME_MODES["group4"]))
+        ref, ocn = shapes[(w, h)]
+        assert cn["rays"] == ocn["rays"], i
+        assert rgb.shape == ref.shape and np.array_equal(_bits(rgb), _bits(ref)), i
 
 
 @pytest.mark.parametrize("mode", ["group4", "stream", "lane"])

@@ -17,6 +17,7 @@
 #include "build.hpp"
 #include "dev_mem.hpp"
 #include "frame_plan.hpp"
+#include "update_plan.hpp"
 
 // Environment knobs (all optional).  Read ONCE, when an accel is built: nothing on the launch path
 // calls getenv.
@@ -136,6 +137,37 @@ struct LastUse {
         if (e == hipSuccess) in_use = true;
         return e;
     }
+};
+
+// What a call that changes a resident accel on its caller's stream (an update, a regather, set_lights_device) leaves for every
+// later call, on whatever stream: the event behind its last kernel or copy, and whether anybody still has to wait for it.
+class GeomFence {
+    DevEvent ready_;
+    bool pending_ = false;
+public:
+    // entry of a call that rewrites what earlier work, on whatever stream, may still read: the device is idle afterwards.  The
+    // event is made here, the first time, so that its creation fails before the call has written anything, in place or beside.
+    hipError_t quiesce() {
+        hipError_t e = static_cast<hipError_t>(ready_.ensure());
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) pending_ = false;
+        return e;
+    }
+    // behind the last piece of work on `s` of a call that began with quiesce(), and before the call swaps anything in
+    hipError_t publish(hipStream_t s) {
+        const hipError_t e = hipEventRecord(ready_.get(), s);
+        if (e == hipSuccess) pending_ = true;
+        return e;
+    }
+    // `s` is about to read the accel: nothing to do once the event has been seen complete, else `s` waits for it on the device
+    hipError_t wait(hipStream_t s) {
+        if (!pending_) return hipSuccess;
+        if (hipEventQuery(ready_.get()) == hipSuccess) { pending_ = false; return hipSuccess; }
+        (void)hipGetLastError();                                            // (hipErrorNotReady is no error of the caller's)
+        return hipStreamWaitEvent(s, ready_.get(), 0);
+    }
+    // the host is about to read what the last publisher wrote
+    hipError_t sync_host() const { return ready_.get() ? hipEventSynchronize(ready_.get()) : hipSuccess; }
 };
 
 // The geometry of an accel exists twice, as two values of this struct: an update builds into the spare one and swaps it with
@@ -303,8 +335,7 @@ struct rtk_accel {
     rtk::PinBuf<uint8_t> up_table_host;        // its pinned host copy
     rtk::DevBuf<rtk::dev::GatherLeaf> up_gather;
     rtk::PinBuf<uint8_t> up_stage;             // pinned: the small tables on their way up
-    rtk::DevEvent geom_ready;                  // recorded behind an update's last kernel: later work on any stream waits for it
-    bool geom_pending = false;
+    rtk::GeomFence geom_fence;                 // published behind an update's last kernel: later work on any stream waits for it
     // ---- st_*: rtk_accel_set_lights / _set_materials (api_state.hip; the regather: api_update.hip, occluders.hip)
     bool lights_on_device = false;             // rtk_accel_set_lights_device: scene.lights has the COUNT, the values are in d_lights
     rtk::DevBuf<rtk::DevMaterial> st_materials;    // the spare material table: written, read by the regather, then swapped with d_materials
@@ -366,8 +397,17 @@ inline bool scene_general(const rtk_accel *a, int diffuse_rays) { return scene_f
 // (which was built on that call's stream) unless that has completed already.
 int ensure_device(rtk_accel *a, hipStream_t s = nullptr);
 dev::TreeView tree_view(const rtk_accel *a);
+// What the frames learnt about the scene as it was says nothing about the scene as it is now: the launch orders of frames, views
+// and regions start over, and so does RTK_TRACE_AUTO's engine trial.  `keep`: what the caller's change leaves valid.
+enum : unsigned { kKeepViewOrders = 1u, kKeepTrial = 2u };
+inline void forget_orders(rtk_accel *a, unsigned keep = 0u) {
+    a->fb.forget();
+    if (!(keep & kKeepViewOrders)) for (rtk_cost_feedback &f : a->fb_views) f.forget();
+    for (rtk_cost_feedback &f : a->fb_regions) f.forget();
+    if (!(keep & kKeepTrial)) a->trial.abandon();
+}
+
 // api_update.hip
-int ensure_update_common(rtk_accel *a);
 // What follows from a new material table on a RESIDENT accel whose device is idle: the per-triangle opaque flags the updates read,
 // and -- when the set of refractive materials changed -- the opaque-only occlusion tree of a RTK_TRAVERSAL_FAST accel, re-made
 // from the active tree into the spare buffers and swapped in.  `d_materials`: the new table on the device; a->scene.materials

@@ -16,10 +16,7 @@ void set_error(const std::string &msg) { g_last_error = msg; }
 int ensure_device(rtk_accel *a, hipStream_t s) {
     if (a->on_device) {
         RTK_HIP(hipSetDevice(a->device));
-        if (a->geom_pending) {
-            if (hipEventQuery(a->geom_ready.get()) == hipSuccess) a->geom_pending = false;
-            else { (void)hipGetLastError(); RTK_HIP(hipStreamWaitEvent(s, a->geom_ready.get(), 0)); }
-        }
+        RTK_HIP(a->geom_fence.wait(s));
         return RTK_OK;
     }
     int count = 0;
@@ -40,30 +37,13 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
     RTK_TRY(upload(a->tree.dev_tri_ids, G.tri_ids));
     RTK_TRY(upload(a->tree.dev_shade, G.shade));
     if (a->fast_traversal && a->has_refractive && a->knobs.fast_occluders) {
-        // occlusion through transmissive surfaces as ONE query against what is not transmissive (rtk.h, RTK_TRAVERSAL_FAST): the same
-        // nodes, their leaves without the transmissive triangles; leaves left empty drop out of the leaf list
-        const HostTree &t = a->tree;
-        std::vector<DevNode> nodes = t.dev_nodes, leaves;
-        std::vector<DevTri> tris;
-        std::vector<uint32_t> ids;
-        for (DevNode &n : nodes) {
-            if (n.b == DEV_INNER) continue;
-            const uint32_t first = uint32_t(tris.size());
-            for (uint32_t r = n.a; r < n.a + n.b; ++r) {
-                const uint32_t m = t.dev_shade[t.dev_tri_ids[r]].material;
-                if (m < a->scene.materials.size() && a->scene.materials[m].kind == RTK_MAT_REFRACTIVE) continue;
-                tris.push_back(t.dev_tris[r]); ids.push_back(t.dev_tri_ids[r]);
-            }
-            n.a = first; n.b = uint32_t(tris.size()) - first;
-            if (n.b != 0u) leaves.push_back(n);
-        }
-        if (tris.empty()) { tris.push_back(t.dev_tris.empty() ? DevTri{} : t.dev_tris[0]); ids.push_back(0u); }      // (nothing opaque: keep the pointers valid)
-        if (leaves.empty()) { DevNode n = nodes.empty() ? DevNode{} : nodes[0]; n.a = 0u; n.b = 0u; leaves.push_back(n); }
-        RTK_TRY(upload(nodes, G.occl_nodes));
-        RTK_TRY(upload(leaves, G.occl_leaves));
-        RTK_TRY(upload(tris, G.occl_tris));
-        RTK_TRY(upload(ids, G.occl_ids));
-        a->occl_n_leaves = uint32_t(leaves.size());
+        HostOccluders o;                                                    // the second tree of RTK_TRAVERSAL_FAST (update_plan.hpp)
+        if (const char *why = host_occluders(a->tree, a->scene.materials, o)) return fail(RTK_ERR_INVALID, why);
+        RTK_TRY(upload(o.tree.nodes, G.occl_nodes));
+        RTK_TRY(upload(o.tree.leaves, G.occl_leaves));
+        RTK_TRY(upload(o.tris, G.occl_tris));
+        RTK_TRY(upload(o.ids, G.occl_ids));
+        a->occl_n_leaves = uint32_t(o.tree.leaves.size());
         a->occl_on = true;
     }
     RTK_TRY(upload(a->scene.materials, a->d_materials));
@@ -270,7 +250,7 @@ int rtk_accel_build(const rtk_scene *scene, const rtk_accel_params *params, rtk_
         if (!(a->params.eps >= 1.17549435e-38f && a->params.eps < 1.0f)) {
             delete a; return fail(RTK_ERR_INVALID, "eps must be in [FLT_MIN, 1)");
         }
-        for (const DevMaterial &m : a->scene.materials) if (m.kind == RTK_MAT_REFRACTIVE) a->has_refractive = true;
+        a->has_refractive = any_refractive(a->scene.materials);
         for (const HostMesh &m : a->scene.meshes) { a->mesh_nverts.push_back(int32_t(m.vertices.size())); a->mesh_ntris.push_back(int32_t(m.indices.size() / 3)); }
         a->knobs = rtk_knobs::from_env();
         a->stream_slices_auto = stream_slices_for(a->tree);
@@ -321,7 +301,7 @@ int rtk_accel_tree_dump(const rtk_accel *a, float *nodes_box, int32_t *nodes_lin
         // the device build wrote them (build.hip, k_build_gather): fetched when someone asks
         if (a->n_leaf_refs_dev > 0) {
             RTK_HIP(hipSetDevice(a->device));
-            RTK_HIP(hipEventSynchronize(a->geom_ready.get()));
+            RTK_HIP(a->geom_fence.sync_host());
             RTK_HIP(hipMemcpy(leaf_refs, a->geom.leaf_refs.get(), size_t(a->n_leaf_refs_dev) * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
     } else if (leaf_refs && !a->tree.leaf_refs.empty())

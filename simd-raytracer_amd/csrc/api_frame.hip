@@ -888,10 +888,8 @@ int rtk_accel_set_camera(rtk_accel *a, const rtk_view *view) {
     // frame, and the third takes 0.20 ms against 0.30 under a kept order, which is served until its next re-sort (rtk.h;
     // RTK_CAMERA_KEEPS_ORDER=1 keeps it).  RTK_TRACE_AUTO's
     // engine verdict stays: started over at every move, the trial of a camera in motion would never end.
-    if (!a->knobs.camera_keeps_order) {
-        a->fb.forget();
-        for (rtk_cost_feedback &f : a->fb_regions) f.forget();       // (rectangles are seen from the accel's camera; views bring their own)
-    }
+    // (rectangles are seen from the accel's camera; views bring their own)
+    if (!a->knobs.camera_keeps_order) forget_orders(a, kKeepViewOrders | kKeepTrial);
     return RTK_OK;
 }
 

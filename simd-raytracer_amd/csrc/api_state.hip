@@ -24,9 +24,7 @@ int reserve_lights(rtk_accel *a, size_t n) {
 // every block's cost scales with the number of lights; their positions leave the silhouettes where they are (rtk.h)
 void lights_changed(rtk_accel *a, size_t n_before) {
     if (a->scene.lights.size() == n_before) return;
-    a->fb.forget();
-    for (rtk_cost_feedback &f : a->fb_views) f.forget();
-    for (rtk_cost_feedback &f : a->fb_regions) f.forget();
+    forget_orders(a, kKeepTrial);
 }
 
 }  // namespace
@@ -58,8 +56,7 @@ int rtk_accel_set_lights(rtk_accel *a, const rtk_light *lights, int32_t n) {
         if (a->on_device) {
             RTK_HIP(hipSetDevice(a->device));
             // entry: nothing issued earlier on this accel, on whatever stream, may still read the table
-            RTK_HIP(hipDeviceSynchronize());
-            a->geom_pending = false;
+            RTK_HIP(a->geom_fence.quiesce());
             RTK_TRY(reserve_lights(a, size_t(n)));
             if (n > 0) RTK_HIP(hipMemcpy(a->d_lights.get(), table.data(), size_t(n) * sizeof(DevLight), hipMemcpyHostToDevice));
         }
@@ -78,14 +75,11 @@ int rtk_accel_set_lights_device(rtk_accel *a, const rtk_light *d_lights, int32_t
     try {
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
         RTK_TRY(ensure_device(a));
-        RTK_HIP(hipDeviceSynchronize());
-        a->geom_pending = false;
-        RTK_TRY(ensure_update_common(a));
+        RTK_HIP(a->geom_fence.quiesce());
         RTK_TRY(reserve_lights(a, size_t(n)));
         std::vector<DevLight> count_only(static_cast<size_t>(n), DevLight{{0.f, 0.f, 0.f}, 0.f});
         if (n > 0) RTK_HIP(hipMemcpyAsync(a->d_lights.get(), d_lights, size_t(n) * sizeof(DevLight), hipMemcpyDeviceToDevice, s));
-        RTK_HIP(hipEventRecord(a->geom_ready.get(), s));
-        a->geom_pending = true;
+        RTK_HIP(a->geom_fence.publish(s));
         const size_t before = a->scene.lights.size();
         a->scene.lights.swap(count_only);              // the COUNT every launch path reads; the values live in d_lights
         a->lights_on_device = true;
@@ -108,7 +102,6 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
         if (n < 0 || size_t(n) != a->scene.materials.size()) return fail(RTK_ERR_INVALID, "the number of materials is fixed when the scene is made");
         // scene.cpp, scene_from_desc
         std::vector<DevMaterial> table(static_cast<size_t>(n));
-        bool any_refractive = false;
         for (size_t i = 0; i < table.size(); ++i) {
             DevMaterial &m = table[i];
             std::memcpy(&m, &materials[i], sizeof(m));
@@ -117,12 +110,10 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
                 if (m.texture < 0 || size_t(m.texture) >= a->scene.textures.size()) return fail(RTK_ERR_INVALID, "texture material refers to a texture that does not exist");
             } else m.texture = -1;
             m.pad = 0u;
-            any_refractive = any_refractive || m.kind == RTK_MAT_REFRACTIVE;
         }
         if (a->on_device) {
             RTK_HIP(hipSetDevice(a->device));
-            RTK_HIP(hipDeviceSynchronize());
-            a->geom_pending = false;
+            RTK_HIP(a->geom_fence.quiesce());
             // the new table goes into the spare one, what follows from it is built beside what is active, and both are swapped in at the end
             RTK_MEM(a->st_materials.reserve(table.size()));             // (once: the number of materials is fixed)
             if (!table.empty()) RTK_HIP(hipMemcpy(a->st_materials.get(), table.data(), table.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
@@ -130,12 +121,9 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
             a->d_materials.swap(a->st_materials);
         }
         a->scene.materials.swap(table);
-        a->has_refractive = any_refractive;
+        a->has_refractive = any_refractive(a->scene.materials);
         // a scene that starts or stops forking runs other kernels over other block costs, and needs a new verdict
-        a->fb.forget();
-        for (rtk_cost_feedback &f : a->fb_views) f.forget();
-        for (rtk_cost_feedback &f : a->fb_regions) f.forget();
-        a->trial.abandon();
+        forget_orders(a);
         return RTK_OK;
     } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
 }

@@ -21,8 +21,6 @@ struct BuildHdr {
     uint32_t pad2[12];
 };
 static_assert(sizeof(BuildHdr) == 128, "BuildHdr must be 128 bytes");
-constexpr uint32_t kBuildNonFinite = 1u, kBuildCoordsBig = 2u, kBuildRefOverflow = 4u, kBuildNodeOverflow = 8u;
-constexpr uint32_t kBuildBadIndex = 16u;     // topology.hip: an index that is not a vertex of its own mesh
 
 struct BuildArgs {
     const float *verts;             // [n_verts][3], the new positions
@@ -82,13 +80,8 @@ struct GatherArgs {
     uint32_t *occl_ids;
 };
 
-// rtk_accel_set_materials (occluders.hip): the opaque-only occlusion tree again, from the ACTIVE tree and a new material table.
-struct OcclLeaf {
-    uint32_t first, count;          // the leaf's run in the active tris / tri_ids
-    uint32_t dst;                   // its first slot in the opaque-only copy (the gather's; the count kernel does not read it)
-    uint32_t pad;
-};
-static_assert(sizeof(OcclLeaf) == 16, "OcclLeaf must be 16 bytes");
+// rtk_accel_set_materials (occluders.hip): the opaque-only occlusion tree again, from the ACTIVE tree and a new material table
+// (OcclLeaf: build_nodes.hpp).
 
 struct OcclArgs {
     const DevMaterial *materials;

@@ -30,6 +30,18 @@ struct GatherLeaf {
     uint32_t pad[3];
 };
 
+// One leaf of the ACTIVE tree when rtk_accel_set_materials re-makes the opaque-only occlusion tree from it (occluders.hip).
+struct OcclLeaf {
+    uint32_t first, count;          // the leaf's run in the active tris / tri_ids
+    uint32_t dst;                   // its first slot in the opaque-only copy (the gather's; the count kernel does not read it)
+    uint32_t pad;
+};
+static_assert(sizeof(OcclLeaf) == 16, "OcclLeaf must be 16 bytes");
+
+// The flags of BuildHdr::ok (build.hpp): a kernel CLEARS a bit to raise one.
+constexpr uint32_t kBuildNonFinite = 1u, kBuildCoordsBig = 2u, kBuildRefOverflow = 4u, kBuildNodeOverflow = 8u;
+constexpr uint32_t kBuildBadIndex = 16u;     // topology.hip: an index that is not a vertex of its own mesh
+
 }  // namespace dev
 
 // kdtree.cpp: numbering and flattening of a device-built tree (nodes, depth, dev_nodes, dev_leaves of `out`)

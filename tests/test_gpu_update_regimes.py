@@ -25,8 +25,9 @@ MISS = 0xFFFFFFFF
 
 
 def _first_caps(n_nodes, n_tris, max_depth):
-    """(cap_nodes, cap_refs) of an accel's FIRST update, from the tree it holds then: api_update.hip, update_vertices_impl, `max_nodes`,
-    `want_nodes`, `want_refs` and their clamps at the head of the retry loop.  Later updates keep what the last one ended with."""
+    """(cap_nodes, cap_refs) of an accel's FIRST update, from the tree it holds then: csrc/update_plan.hpp, BuildCaps, the first
+    request() of one made without kept capacities (tests/cpp/update_plan_check.cpp pins the same numbers on the host).  Later
+    updates keep what the last one ended with."""
     max_nodes = (1 << (max_depth + 1)) - 1
     want_nodes = min(max(1024, 4 * n_nodes), max_nodes)
     want_refs = max(4096, 2 * n_tris * (min(max_depth, 12) + 2), n_tris)

@@ -8,9 +8,15 @@
                      fails for every ray;
 * `interval_misses`  the interval-arithmetic culling of generic bundles (sound by monotone rounding alone).
 
+Next to them stand the pieces that feed and surround the culling: `tri_values` (t, u, v of the exact test), `slab_hits`
+(the ray / box test), `bundle_image` (what emit_bundle writes to LDS for a set of member rays), `box_may_hit`
+(bundle_may_hit_box) and `leaf_winner` (the running strict `<` of a leaf).
+
 The model exists so that the soundness property "culled => no ray of the bundle is accepted" can be hammered on the CPU with
 millions of random and adversarial cases (tests/test_bundle_cull_model.py).  It is test infrastructure: the product's
-culling lives in simd-raytracer_amd/csrc/trace.hip.hpp and is checked end to end by the GPU parity tests.
+culling lives in simd-raytracer_amd/csrc/trace.hip.hpp.  tests/test_gpu_cull_probe.py runs that device code itself, one wave
+at a time through tests/cpp/cull_probe.hip, and pins this model to it: bundle images, pencil_misses and the exact test bit for
+bit, interval_misses within the error of the hardware reciprocal, and the soundness property on the device's own decisions.
 """
 import numpy as np
 
@@ -19,22 +25,37 @@ EPS24 = f32(2.0 ** -24)
 K_T = f32(2.0 ** -20)          # rounding-error margin per unit of |operand products| (derived bound: 6.1 * 2^-24 twice)
 K_DET = f32(2.0 ** -21)        # relative slack on the determinant in the u <= 1 and u + v <= 1 tests (derived: 4 * 2^-24)
 ABS_SLACK = f32(1e-30)
+FLT_MAX = f32(3.402823466e+38)
+
+# trace.hip.hpp: flags of a bundle, the coordinate limit, and the layout of a bundle's LDS image (kBundleFloats floats)
+BUNDLE_OK, BUNDLE_ALL_CULL, BUNDLE_INVX, BUNDLE_INVY, BUNDLE_INVZ, BUNDLE_PENCIL = 1, 2, 4, 8, 16, 32
+BUNDLE_LIMIT = f32(1.0e9)
+BUNDLE_FLOATS = 40
+I_OL, I_OH, I_DL, I_DH = slice(0, 3), slice(3, 6), slice(6, 9), slice(9, 12)
+I_INV = slice(12, 18)          # 1/dhx, 1/dlx, 1/dhy, 1/dly, 1/dhz, 1/dlz
+I_FLAGS, I_DD1 = 18, 19
+I_APEX = slice(20, 23)         # [23] = 0
+I_DC, I_RD, I_OC, I_RO, I_DM = slice(24, 27), slice(27, 30), slice(30, 33), slice(33, 36), slice(36, 39)
+I_D1 = 39
 
 
 def _f(x):
     return np.asarray(x, dtype=f32)
 
 
-def tri_accepts(o, d, v0, e1, e2, cull, eps=f32(1e-6)):
-    """[rays, tris] bool: the exact per-ray acceptance (without the running `t < best.t`).  o, d: [R, 3]; v0, e1, e2: [K, 3]."""
+def tri_values(o, d, v0, e1, e2, cull, eps=f32(1e-6)):
+    """([rays, tris] bool, t, u, v): the exact per-ray test (without the running `t < best.t`) and the floats it computes.
+    o, d: [R, 3]; v0, e1, e2: [K, 3]; cull: one bool or one per ray."""
     o = _f(o)[:, None, :]; d = _f(d)[:, None, :]
     v0 = _f(v0)[None]; e1 = _f(e1)[None]; e2 = _f(e2)[None]
+    eps = f32(eps)
+    cull = np.broadcast_to(np.asarray(cull, bool).reshape(-1, 1), (o.shape[0], 1))
     with np.errstate(all="ignore"):
         pvx = d[..., 1] * e2[..., 2] - d[..., 2] * e2[..., 1]
         pvy = d[..., 2] * e2[..., 0] - d[..., 0] * e2[..., 2]
         pvz = d[..., 0] * e2[..., 1] - d[..., 1] * e2[..., 0]
         det = (e1[..., 0] * pvx + e1[..., 1] * pvy) + e1[..., 2] * pvz
-        m = (eps <= det) if cull else (eps <= np.abs(det))
+        m = np.where(cull, eps <= det, eps <= np.abs(det))
         inv = f32(1.0) / det
         tvx = o[..., 0] - v0[..., 0]; tvy = o[..., 1] - v0[..., 1]; tvz = o[..., 2] - v0[..., 2]
         u = ((tvx * pvx + tvy * pvy) + tvz * pvz) * inv
@@ -46,7 +67,43 @@ def tri_accepts(o, d, v0, e1, e2, cull, eps=f32(1e-6)):
         m &= (f32(0) <= v) & (u + v <= f32(1))
         t = ((e2[..., 0] * qx + e2[..., 1] * qy) + e2[..., 2] * qz) * inv
         m &= eps < t
-    return m
+    return m, t, u, v
+
+
+def tri_accepts(o, d, v0, e1, e2, cull, eps=f32(1e-6)):
+    """[rays, tris] bool: the exact per-ray acceptance (without the running `t < best.t`).  o, d: [R, 3]; v0, e1, e2: [K, 3]."""
+    return tri_values(o, d, v0, e1, e2, cull, eps)[0]
+
+
+def leaf_winner(o, d, v0, e1, e2, cull, eps, best_t=None):
+    """(t, u, v, k) per ray after the triangles of a leaf in leaf order: a running strict `<` from `best_t` (FLT_MAX when
+    None), so the earliest triangle with the smallest t wins.  k = -1 and t = best_t where nothing was accepted."""
+    m, t, u, v = tri_values(o, d, v0, e1, e2, cull, eps)
+    R = m.shape[0]
+    bt = np.full(R, FLT_MAX, f32) if best_t is None else _f(best_t).copy()
+    bu = np.zeros(R, f32); bv = np.zeros(R, f32); bk = np.full(R, -1, np.int64)
+    for k in range(m.shape[1]):
+        w = m[:, k] & (t[:, k] < bt)
+        bt[w] = t[w, k]; bu[w] = u[w, k]; bv[w] = v[w, k]; bk[w] = k
+    return bt, bu, bv, bk
+
+
+def slab_hits(o, d, lo, hi):
+    """([rays, boxes] bool, t_min): slab() of trace.hip.hpp (aabb3::intersect), inv = 1/d in float32, compare-select so that
+    NaNs (0 * inf) take the device's path.  o, d: [R, 3]; lo, hi: [K, 3]."""
+    o = _f(o)[:, None, :]; d = _f(d)[:, None, :]; lo = _f(lo)[None]; hi = _f(hi)[None]
+    with np.errstate(all="ignore"):
+        inv = f32(1.0) / d
+        t_min = np.zeros((o.shape[0], lo.shape[1]), f32)
+        t_max = np.full_like(t_min, FLT_MAX)
+        miss = np.zeros(t_min.shape, bool)
+        for a in range(3):
+            p = (lo[..., a] - o[..., a]) * inv[..., a]; c = (hi[..., a] - o[..., a]) * inv[..., a]
+            t1 = np.where(c < p, c, p); t2 = np.where(c < p, p, c)
+            t_min = np.where(t_min < t1, t1, t_min)
+            t_max = np.where(t2 < t_max, t2, t_max)
+            miss |= t_max < t_min
+    return ~miss, t_min
 
 
 def _cross(a, b):
@@ -65,8 +122,9 @@ def _across(a, b):        # "absolute cross product": upper bound of |x x y| for
     return [a[1] * b[2] + a[2] * b[1], a[2] * b[0] + a[0] * b[2], a[0] * b[1] + a[1] * b[0]]
 
 
-def pencil_delta(o, d, C):
-    """Upper bound of the distance between the apex C and each ray's line (float32, as the device computes it)."""
+def _delta_lanes(o, d, C):
+    """pencil_delta_lane of every ray: an upper bound of the distance between the apex C and the ray's line; inf where the
+    direction is too short to say."""
     o = _f(o); d = _f(d); C = _f(C)
     with np.errstate(all="ignore"):
         c = [C[a] - o[:, a] for a in range(3)]
@@ -76,6 +134,12 @@ def pencil_delta(o, d, C):
         w1 = (np.abs(w[0]) + np.abs(w[1])) + np.abs(w[2])
         c1 = (np.abs(c[0]) + np.abs(c[1])) + np.abs(c[2])
         dl = w1 + f32(2.0 ** -19) * c1
+    return dl, dd
+
+
+def pencil_delta(o, d, C):
+    """Upper bound of the distance between the apex C and each ray's line (float32, as the device computes it)."""
+    dl, dd = _delta_lanes(o, d, C)
     ok = bool(np.all(dd >= f32(1e-30)) and np.all(np.isfinite(dl)))
     return (f32(np.max(dl)) * f32(1.00001) if ok else f32(np.inf)), ok
 
@@ -85,19 +149,72 @@ def bundle_boxes(o, d):
     return o.min(0), o.max(0), d.min(0), d.max(0)
 
 
-def pencil_misses(C, delta, ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6)):
-    """[K] bool: True = no ray of the pencil bundle can be accepted for this triangle.  Mirrors pencil_misses() of trace.hip.hpp."""
-    C = _f(C); ol = _f(ol); oh = _f(oh); dl = _f(dl); dh = _f(dh); delta = f32(delta)
+def image_from_boxes(ol, oh, dl, dh, all_cull, C, delta, pencil):
+    """The LDS image emit_bundle writes for a bundle with these boxes: the boxes, the six bounds of fl(1/d), the flags, the
+    apex, delta |d|_1 and the centre / radius form (radii inflated so that centre +- radius covers the box in exact
+    arithmetic).  `delta` is the bundle's (already carrying its factor 1.00001), `pencil` whether BUNDLE_PENCIL is set."""
+    ol = _f(ol); oh = _f(oh); dl = _f(dl); dh = _f(dh); C = _f(C); delta = f32(delta)
+    img = np.zeros(BUNDLE_FLOATS, f32)
+    with np.errstate(all="ignore"):
+        img[I_OL] = ol; img[I_OH] = oh; img[I_DL] = dl; img[I_DH] = dh
+        flags = BUNDLE_OK | (BUNDLE_ALL_CULL if all_cull else 0) | (BUNDLE_PENCIL if pencil else 0)
+        for a, bit in enumerate((BUNDLE_INVX, BUNDLE_INVY, BUNDLE_INVZ)):
+            if (f32(1e-30) < dl[a]) or (dh[a] < f32(-1e-30)):
+                flags |= bit
+            img[12 + 2 * a] = f32(1.0) / dh[a]; img[13 + 2 * a] = f32(1.0) / dl[a]
+        img[I_FLAGS] = np.array([flags], np.uint32).view(f32)[0]
+        dc = (dl + dh) * f32(0.5)
+        rd = (dh - dl) * f32(0.5) * f32(1.000001) + f32(2.0 ** -22) * (np.abs(dl) + np.abs(dh))
+        oc = (ol + oh) * f32(0.5)
+        ro = (oh - ol) * f32(0.5) * f32(1.000001) + f32(2.0 ** -22) * (np.abs(ol) + np.abs(oh))
+        Dm = np.abs(dc) + rd
+        D1 = (Dm[0] + Dm[1]) + Dm[2]
+        img[I_DD1] = (delta * D1) * f32(1.00001)
+        img[I_APEX] = C
+        img[I_DC] = dc; img[I_RD] = rd; img[I_OC] = oc; img[I_RO] = ro; img[I_DM] = Dm; img[I_D1] = D1
+    return img
+
+
+def image_flags(img):
+    """The flags word of one image ([40]) or of a batch of them ([40, N], one column per triangle row)."""
+    return np.ascontiguousarray(_f(img)[I_FLAGS]).view(np.uint32)
+
+
+def bundle_image(o, d, cull, hint=None, hinted=False):
+    """What emit_bundle writes for the member rays o, d ([M, 3]; cull: one bool per ray): None when a component of some ray
+    is NaN, infinite or above 1e9 (the bundle is not OK, the trace goes without culling).  `hint` is the apex make_bundles
+    passes along (that of the first lane of the class) and `hinted` whether the class carries kClsHasApex; a bundle whose
+    origins all coincide finds its apex by itself."""
+    o = _f(o); d = _f(d)
+    cull = np.broadcast_to(np.asarray(cull, bool).reshape(-1), (o.shape[0],))
+    with np.errstate(all="ignore"):
+        if not (np.all(np.abs(o) <= BUNDLE_LIMIT) and np.all(np.abs(d) <= BUNDLE_LIMIT)):
+            return None
+        ol, oh, dl, dh = bundle_boxes(o, d)
+        C = np.zeros(3, f32) if hint is None else _f(hint).copy()
+        pencil = bool(hinted)
+        if np.all(ol == oh):
+            C = ol.copy(); pencil = True
+        delta = f32(0.0)
+        if pencil:
+            lanes, dd = _delta_lanes(o, d, C)
+            lanes = np.where(dd >= f32(1e-30), lanes, f32(np.inf))
+            bad = ~(lanes < BUNDLE_LIMIT)
+            delta = f32(np.fmax.reduce(np.append(lanes, f32(0.0)))) * f32(1.00001)      # v_max drops a NaN
+            pencil = bool(not bad.any() and np.all(np.abs(C) <= BUNDLE_LIMIT))
+    return image_from_boxes(ol, oh, dl, dh, bool(cull.all()), C, delta, pencil)
+
+
+def pencil_image_misses(img, v0, e1, e2, eps=f32(1e-6)):
+    """[K] bool: True = no ray of the pencil bundle with LDS image `img` can be accepted for this triangle.  Mirrors
+    pencil_misses() of trace.hip.hpp, which reads the same slots (load_pencil).  `img` may also be [40, K]: one bundle per triangle."""
+    img = _f(img); eps = f32(eps)
     v0 = _f(v0); e1 = _f(e1); e2 = _f(e2)
     V0 = [v0[:, a] for a in range(3)]; E1 = [e1[:, a] for a in range(3)]; E2 = [e2[:, a] for a in range(3)]
+    C = img[I_APEX]; dc = list(img[I_DC]); rd = list(img[I_RD]); oc = list(img[I_OC]); ro = list(img[I_RO])
+    D1 = img[I_D1]; dD1 = img[I_DD1]
+    all_cull = (image_flags(img) & BUNDLE_ALL_CULL) != 0
     with np.errstate(all="ignore"):
-        # centre / radius of the direction and origin boxes, radii inflated so that centre +- radius covers the box in exact arithmetic
-        dc = [(dl[a] + dh[a]) * f32(0.5) for a in range(3)]
-        rd = [(dh[a] - dl[a]) * f32(0.5) * f32(1.000001) + f32(2.0 ** -22) * (np.abs(dl[a]) + np.abs(dh[a])) for a in range(3)]
-        oc = [(ol[a] + oh[a]) * f32(0.5) for a in range(3)]
-        ro = [(oh[a] - ol[a]) * f32(0.5) * f32(1.000001) + f32(2.0 ** -22) * (np.abs(ol[a]) + np.abs(oh[a])) for a in range(3)]
-        Dm = [np.abs(dc[a]) + rd[a] for a in range(3)]
-        D1 = (Dm[0] + Dm[1]) + Dm[2]
         cv = [C[a] - V0[a] for a in range(3)]
         A = _cross(E2, cv)              # un = d . A     (+ a term bounded by delta |d| |e2|)
         Bv = _cross(cv, E1)             # vn = d . Bv    (+ a term bounded by delta |d| |e1|)
@@ -112,7 +229,6 @@ def pencil_misses(C, delta, ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6))
         # the T's of the error analysis, bounded through norms: sum_a x_a (y_b z_c + y_c z_b) <= |x|_1 |y|_1 max|z|
         TV1 = (TVm[0] + TVm[1]) + TVm[2]
         TS = TV1 + ((TC[0] + TC[1]) + TC[2])
-        dD1 = (delta * D1) * f32(1.00001)
         M_un = K_T * ((TS * D1) * E2m) + dD1 * E21 + ABS_SLACK
         M_vn = K_T * ((TS * D1) * E1m) + dD1 * E11 + ABS_SLACK
         M_det = K_T * ((E11 * D1) * E2m) + ABS_SLACK
@@ -144,6 +260,11 @@ def pencil_misses(C, delta, ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6))
         return none | (out & ~(pos & neg) & (dH < f32(1e30)))
 
 
+def pencil_misses(C, delta, ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6)):
+    """[K] bool: pencil_image_misses for the bundle with these boxes, apex and delta."""
+    return pencil_image_misses(image_from_boxes(ol, oh, dl, dh, all_cull, C, delta, True), v0, e1, e2, eps)
+
+
 class Iv:
     def __init__(self, lo, hi):
         self.lo, self.hi = lo, hi
@@ -167,9 +288,19 @@ def _iv_add(a, b):
     return Iv(a.lo + b.lo, a.hi + b.hi)
 
 
-def interval_misses(ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6)):
-    """[K] bool: the interval-arithmetic culling of generic bundles (bundle_misses() of trace.hip.hpp)."""
-    ol = _f(ol); oh = _f(oh); dl = _f(dl); dh = _f(dh)
+def _float_steps(x, n, towards):
+    for _ in range(n):
+        x = np.nextafter(x, f32(towards))
+    return x
+
+
+def interval_misses(ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6), rcp_steps=0):
+    """[K] bool: the interval-arithmetic culling of generic bundles (bundle_misses() of trace.hip.hpp).  The boxes are [3], or
+    [3, K] with all_cull [K]: one bundle per triangle.
+    rcp_steps = n moves the two reciprocals 1/d_h and 1/d_l by n float steps outwards (n > 0: a wider interval, which can only
+    un-cull) or inwards (n < 0) before their factors 0.999999 / 1.000001: the device takes them from v_rcp_f32, within 1 ulp
+    of 1/x, where this model divides."""
+    ol = _f(ol); oh = _f(oh); dl = _f(dl); dh = _f(dh); eps = f32(eps)
     v0 = _f(v0); e1 = _f(e1); e2 = _f(e2)
     one = np.ones(v0.shape[0], f32)
     with np.errstate(all="ignore"):
@@ -193,9 +324,39 @@ def interval_misses(ol, oh, dl, dh, all_cull, v0, e1, e2, eps=f32(1e-6)):
         vn = Iv(np.where(neg, -vn.hi, vn.lo), np.where(neg, -vn.lo, vn.hi))
         tn_hi = np.where(neg, -tn.lo, tn.hi)
         d_l = np.maximum(d_l, eps)
-        il = f32(1.0) / d_h * f32(0.999999); ih = f32(1.0) / d_l * f32(1.000001)
+        rl = f32(1.0) / d_h; rh = f32(1.0) / d_l
+        if rcp_steps:
+            rl = _float_steps(rl, abs(rcp_steps), -np.inf if rcp_steps > 0 else np.inf)
+            rh = _float_steps(rh, abs(rcp_steps), np.inf if rcp_steps > 0 else -np.inf)
+        il = rl * f32(0.999999); ih = rh * f32(1.000001)
         u_hi = np.maximum(un.hi * il, un.hi * ih); u_lo = np.minimum(un.lo * il, un.lo * ih)
         v_hi = np.maximum(vn.hi * il, vn.hi * ih); v_lo = np.minimum(vn.lo * il, vn.lo * ih)
         t_hi = np.maximum(tn_hi * il, tn_hi * ih)
         out = (u_hi < 0) | (f32(1) < u_lo) | (v_hi < 0) | (f32(1) < u_lo + v_lo) | (t_hi <= eps)
         return none | (out & ~(pos & neg) & (d_h < f32(1e30)))
+
+
+def box_may_hit(img, lo, hi):
+    """[K] bool: bundle_may_hit_box() for the bundle with LDS image `img` (boxes, BUNDLE_INV* flags and the six bounds of 1/d)
+    against the boxes lo, hi ([K, 3]).  False = no ray of the bundle can pass slab() for this box.  v_min / v_max drop a NaN
+    operand, hence fmin / fmax."""
+    img = _f(img); lo = _f(lo); hi = _f(hi)
+    flags = image_flags(img)
+    t_min_lo = np.zeros(lo.shape[0], f32); t_max_hi = np.full(lo.shape[0], FLT_MAX, f32)
+    miss = np.zeros(lo.shape[0], bool)
+
+    def mul(al, ah, bl, bh):
+        c = [al * bl, al * bh, ah * bl, ah * bh]
+        return np.fmin(np.fmin(c[0], c[1]), np.fmin(c[2], c[3])), np.fmax(np.fmax(c[0], c[1]), np.fmax(c[2], c[3]))
+
+    with np.errstate(all="ignore"):
+        for a, bit in enumerate((BUNDLE_INVX, BUNDLE_INVY, BUNDLE_INVZ)):
+            if not flags & bit:
+                continue
+            o_l = img[I_OL][a]; o_h = img[I_OH][a]; il = img[12 + 2 * a]; ih = img[13 + 2 * a]
+            a_lo, a_hi = mul(lo[:, a] - o_h, lo[:, a] - o_l, il, ih)
+            c_lo, c_hi = mul(hi[:, a] - o_h, hi[:, a] - o_l, il, ih)
+            t_min_lo = np.fmax(t_min_lo, np.fmin(a_lo, c_lo))
+            t_max_hi = np.fmin(t_max_hi, np.fmax(a_hi, c_hi))
+            miss |= t_max_hi < t_min_lo
+    return ~miss

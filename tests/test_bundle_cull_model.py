@@ -4,43 +4,11 @@ is never accepted by the exact per-ray test for ANY ray of the bundle -- hammere
 import numpy as np
 import pytest
 
+import cull_cases as cc
 import cull_model as cm
+from cull_cases import bundle as _bundle, triangles as _triangles
 
 f32 = np.float32
-
-
-def _bundle(rng, kind):
-    C = (rng.normal(size=3) * rng.choice([1.0, 10.0, 60.0])).astype(f32)
-    dc = rng.normal(size=3); dc /= np.linalg.norm(dc)
-    width = 10.0 ** rng.uniform(-4, -0.5)
-    d = dc[None] + width * rng.uniform(-1, 1, size=(64, 3))
-    if kind != "raw":
-        d /= np.linalg.norm(d, axis=1, keepdims=True)
-    d = d.astype(f32)
-    if kind == "camera":
-        o = np.broadcast_to(C, (64, 3)).astype(f32).copy()
-    else:                                                   # rays that end in C (shadow rays towards a light), plus some noise
-        s = rng.uniform(0.5, 50.0, size=(64, 1))
-        noise = rng.choice([0.0, 1e-6, 1e-3]) * rng.normal(size=(64, 3))
-        o = (C[None].astype(np.float64) - s * d.astype(np.float64) + noise).astype(f32)
-    return C, o, d
-
-
-def _triangles(rng, o, d, n):
-    """Triangles placed around points ON the bundle's rays, so that rays pass near (or exactly through) edges and vertices."""
-    r = rng.integers(0, 64, size=n)
-    t = rng.uniform(0.05, 40.0, size=(n, 1)) * rng.choice([1.0, -0.2], size=(n, 1), p=[0.9, 0.1])
-    X = o[r].astype(np.float64) + t * d[r].astype(np.float64)
-    size = 10.0 ** rng.uniform(-3, 1, size=(n, 1))
-    a = rng.normal(size=(n, 3)) * size; b = rng.normal(size=(n, 3)) * size
-    mode = rng.integers(0, 5, size=n)
-    bu = rng.uniform(-1.5, 2.5, size=(n, 1)); bv = rng.uniform(-1.5, 2.5, size=(n, 1))
-    bu[mode == 1] = 0.0; bv[mode == 2] = 0.0                 # X on an edge
-    bu[mode == 3] = 0.0; bv[mode == 3] = 0.0                 # X on the vertex v0
-    v0 = X - bu * a - bv * b
-    deg = rng.random(n) < 0.03
-    b[deg] = a[deg] * rng.uniform(-2, 2, size=(deg.sum(), 1))   # degenerate (zero area)
-    return v0.astype(f32), a.astype(f32), b.astype(f32)
 
 
 @pytest.mark.parametrize("kind", ["camera", "shadow", "raw"])
@@ -81,3 +49,58 @@ def test_wrong_apex_only_loosens_the_culling():
             hit = cm.tri_accepts(o, d, v0, e1, e2, cull).any(0)
             mp = cm.pencil_misses(wrong, delta, ol, oh, dl, dh, cull, v0, e1, e2)
             assert not (mp & hit).any(), (it, cull)
+
+
+@pytest.mark.parametrize("kind", cc.KINDS)
+def test_culled_triangles_are_never_hit_over_scales_and_epsilons(kind):
+    """The same property over the coordinate range the culling claims (just under kBundleLimit down to 1e-3) and the epsilons a
+    scene may set; per cell the set must have both hits and culled triangles, or it would prove nothing."""
+    cells = [(t, e, 1.0) for t, e in cc.GRID] + ([(None, 1e-6, 1e-3), (None, 1e-6, 1e3)] if kind == "raw" else [])
+    for target, eps, dscale in cells:
+        hits = culled = 0
+        for it, s in enumerate(cc.grid_sets(kind)):
+            C, o, d, v0, e1, e2 = cc.rescale(*s, target, dscale)
+            ol, oh, dl, dh = cm.bundle_boxes(o, d)
+            delta, ok = cm.pencil_delta(o, d, C)
+            for cull in (True, False):
+                hit = cm.tri_accepts(o, d, v0, e1, e2, cull, eps).any(0)
+                mi = cm.interval_misses(ol, oh, dl, dh, cull, v0, e1, e2, eps)
+                assert not (mi & hit).any(), (kind, target, eps, dscale, it, cull, "interval", np.nonzero(mi & hit)[0][:5])
+                mp = np.zeros_like(mi)
+                if ok:
+                    mp = cm.pencil_misses(C, delta, ol, oh, dl, dh, cull, v0, e1, e2, eps)
+                    assert not (mp & hit).any(), (kind, target, eps, dscale, it, cull, "pencil", np.nonzero(mp & hit)[0][:5])
+                hits += int(hit.sum()); culled += int((mi | mp).sum())
+        assert hits > 0 and culled > 0, (kind, target, eps, dscale, hits, culled)
+
+
+def _zero_axis(rng, d, it):
+    """Every third bundle gets a zero direction component: in all its rays, or in some of them."""
+    d = d.copy()
+    if it % 3 == 1:
+        d[:, rng.integers(0, 3)] = 0.0
+    elif it % 3 == 2:
+        d[rng.random(64) < 0.3, rng.integers(0, 3)] = 0.0
+    return d
+
+
+@pytest.mark.parametrize("kind", cc.KINDS)
+def test_culled_boxes_are_never_hit(kind):
+    """bundle_may_hit_box against slab(): a box the bundle test drops is missed by every ray of the bundle.  Boxes around
+    points on the rays, flat boxes, faces through an origin, rays with a zero direction component (that axis gives no bound)."""
+    rng = np.random.default_rng({"camera": 21, "shadow": 22, "raw": 23}[kind])
+    dropped = missed = hit_n = 0
+    for it in range(150):
+        C, o, d = _bundle(rng, kind)
+        d = _zero_axis(rng, d, it)
+        lo, hi = cc.boxes(rng, o, d, 256)
+        img = cm.bundle_image(o, d, True)
+        flags = cm.image_flags(img)
+        for a, bit in enumerate((cm.BUNDLE_INVX, cm.BUNDLE_INVY, cm.BUNDLE_INVZ)):
+            if (d[:, a] == 0).any():
+                assert not flags & bit, (kind, it, a)
+        hit = cm.slab_hits(o, d, lo, hi)[0].any(0)
+        may = cm.box_may_hit(img, lo, hi)
+        assert not (~may & hit).any(), (kind, it, np.nonzero(~may & hit)[0][:5])
+        dropped += int((~may).sum()); missed += int((~hit).sum()); hit_n += int(hit.sum())
+    assert hit_n > 0 and dropped > 0, (hit_n, missed, dropped)          # (not vacuous: boxes are hit, boxes are dropped)

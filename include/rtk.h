@@ -59,8 +59,8 @@ enum {
     RTK_TRACE_GROUP16 = 5, /* frames only: same with 16 waves (one 1024-thread workgroup per 8x8 pixel block) */
     RTK_TRACE_STREAM = 6, /* frames only: the ray tree level by level — per-depth path / shadow / combine kernels over
                              compacted ray queues (stream.hip) */
-    RTK_TRACE_TWOPASS = 7, /* frames only, spp == 1: camera-ray pass, then the GROUP4 shading pass over the pixel blocks
-                             sorted by estimated cost, most expensive first */
+    RTK_TRACE_TWOPASS = 7, /* frames only, spp == 1: rendered by the GROUP4 engine; kept so that callers compile (it named a
+                             camera-ray pass followed by a cost-sorted shading pass, which GROUP4's cost feedback superseded) */
     RTK_TRACE_REPACK = 8  /* batched intersect only: the rays are first sorted by the cell of their origin and direction
                              (repack.hip: Morton key over the dimensions that vary, rocPRIM radix sort), then traced in that
                              order -- wave-cooperatively when the sort makes tight waves, with the per-lane fallback otherwise;

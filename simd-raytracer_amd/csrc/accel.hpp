@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "abi_guard.hpp"
 #include "kernels.hpp"
 #include "stream.hpp"
 #include "build.hpp"
@@ -245,7 +246,7 @@ struct rtk_accel {
     rtk::DevBuf<rtk::DevLight> d_lights;           // its capacity is the rows it has room for: grows with head room, never shrinks
     rtk::DevBuf<rtk::DevTexture> d_textures;
     rtk::DevBuf<uint8_t> d_tex_pixels;
-    rtk::DevBuf<unsigned long long> d_counters;    // 8 x u64 in rtk_counters order + kRayCounterShards ray-count shards
+    rtk::DevBuf<unsigned long long> d_counters;    // [kCounterAllocWords] counters.hpp
     uint32_t occl_n_leaves = 0;
     bool occl_on = false;
     // ---- ws_* / lane_*: streaming-pipeline workspace (api_frame.hip ensure_stream_ws; grown on demand)
@@ -262,11 +263,6 @@ struct rtk_accel {
     struct SideEvents { rtk::DevEvent ready[2], done[2]; } lane_side_ev[rtk::dev::kStreamLanes];
     rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane (the process's) and views of lane_side_ev
     rtk::LastUse ws_last;                                       // of a STREAM frame or a radiance batch
-    // ---- tp_*: two-pass workspace (api_frame.hip ensure_twopass_ws)
-    rtk::DevBuf<float4> tp_prim;
-    rtk::DevBuf<uint32_t> tp_bins;     // [kCostBins] counts, [1] n_listed
-    rtk::DevBuf<uint32_t> tp_bin_list, tp_order;
-    size_t tp_pixels = 0, tp_tiles = 0;
     // ---- fb / fb_views: cost feedback (megakernel frames, api_frame.hip render_megakernel).  Frames have one set of tables;
     // rtk_render_views has one per launch of a call (a call is cut into launches of whole views), so that a caller who
     // alternates frames and views calls keeps the order of both.
@@ -307,7 +303,7 @@ struct rtk_accel {
     rtk::DevBuf<float> oc_max_t;
     rtk::DevBuf<uint8_t> oc_out;
     // ---- rad_*: batched radiance (rtk_accel_radiance, api_frame.hip)
-    // one kCounterWords block per lane for a chunk's pipeline, then {rays, chunks redone} of the call
+    // one counter block per lane for a chunk's pipeline, then {rays, chunks redone} of the call (counters.hpp)
     rtk::DevBuf<unsigned long long> d_rad_counters;
     // staging of the host variant: grows, never shrinks
     rtk::DevBuf<rtk_ray> rad_rays;

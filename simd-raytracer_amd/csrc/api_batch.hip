@@ -111,48 +111,51 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
 }
 
 int rtk_accel_intersect_device(rtk_accel *a, const rtk_ray *d_rays, size_t n, int cull, int mode, rtk_hit *d_out, void *stream) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
-    return intersect_device_impl(a, d_rays, n, cull, mode, d_out, static_cast<hipStream_t>(stream), false);
+    return abi_guard([&]() -> int {
+        if (!a) return fail(RTK_ERR_INVALID, "null accel");
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return intersect_device_impl(a, d_rays, n, cull, mode, d_out, static_cast<hipStream_t>(stream), false);
+    });
 }
 
 int rtk_accel_intersect_stats(rtk_accel *a, const rtk_ray *d_rays, size_t n, int cull, int mode, rtk_hit *d_out,
                               rtk_counters *counters) {
-    if (!a || !counters) return fail(RTK_ERR_INVALID, "null accel or counters");
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a));
-    RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, kCounterWords * sizeof(unsigned long long), nullptr));
-    RTK_TRY(intersect_device_impl(a, d_rays, n, cull, mode, d_out, nullptr, true));
-    unsigned long long h[8];
-    RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
-    counters->rays = h[0]; counters->primary = 0; counters->hits = h[2]; counters->nodes = h[3]; counters->boxpass = h[4];
-    counters->leaves = h[5]; counters->tris = h[6]; counters->packets16 = h[7];
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !counters) return fail(RTK_ERR_INVALID, "null accel or counters");
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, kCounterWords * sizeof(unsigned long long), nullptr));
+        RTK_TRY(intersect_device_impl(a, d_rays, n, cull, mode, d_out, nullptr, true));
+        unsigned long long h[kRayShardWord];
+        RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
+        counters_from_block(h, true, counters);
+        return RTK_OK;
+    });
 }
 
 int rtk_accel_intersect(rtk_accel *a, const rtk_ray *rays, size_t n, int cull, int mode, rtk_hit *out) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    if (n > 0 && (!rays || !out)) return fail(RTK_ERR_INVALID, "null ray or hit buffer");
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a));
-    if (n == 0) return RTK_OK;
-    DevBuf<rtk_ray> d_rays;                      // (the call's own: freed when it returns)
-    DevBuf<rtk_hit> d_out;
-    RTK_MEM(d_rays.reserve(n));
-    RTK_HIP_AS(static_cast<hipError_t>(d_out.reserve(n)), "hipMalloc hits");
-    RTK_HIP_AS(hipMemcpy(d_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice), "intersect copy");
-    RTK_TRY(intersect_device_impl(a, d_rays.get(), n, cull, mode, d_out.get(), nullptr, false));
-    RTK_HIP_AS(hipMemcpy(out, d_out.get(), n * sizeof(rtk_hit), hipMemcpyDeviceToHost), "intersect copy");
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a) return fail(RTK_ERR_INVALID, "null accel");
+        if (n > 0 && (!rays || !out)) return fail(RTK_ERR_INVALID, "null ray or hit buffer");
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        if (n == 0) return RTK_OK;
+        DevBuf<rtk_ray> d_rays;                      // (the call's own: freed when it returns)
+        DevBuf<rtk_hit> d_out;
+        RTK_MEM(d_rays.reserve(n));
+        RTK_HIP_AS(static_cast<hipError_t>(d_out.reserve(n)), "hipMalloc hits");
+        RTK_HIP_AS(hipMemcpy(d_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice), "intersect copy");
+        RTK_TRY(intersect_device_impl(a, d_rays.get(), n, cull, mode, d_out.get(), nullptr, false));
+        RTK_HIP_AS(hipMemcpy(out, d_out.get(), n * sizeof(rtk_hit), hipMemcpyDeviceToHost), "intersect copy");
+        return RTK_OK;
+    });
 }
 
 // ---------------------------------------------------------------- batched occlusion
 
-// Word of the counter buffer the host variant counts its closest-hit queries in: the last of the four words behind the frame
-// counters (the first-frame prior's six 32-bit cursors fill the first three), so the counters of the most recent frame
-// (rtk_render_last_counters) stay as that frame left them.
-static constexpr int kOccludedCountWord = kCounterWords + 3;
+// (the host variant counts its closest-hit queries in kOccludedCountWord, behind the frame counters: those of the most recent
+// frame, rtk_render_last_counters, stay as that frame left them)
 
 static int occluded_check(const rtk_accel *a, const void *rays, const void *max_t, size_t n, float shadow_bias, int mode, const void *out) {
     if (!a) return fail(RTK_ERR_INVALID, "null accel");
@@ -179,34 +182,38 @@ static int occluded_launch(rtk_accel *a, const rtk_ray *d_rays, const float *d_m
 
 int rtk_accel_occluded_device(rtk_accel *a, const rtk_ray *d_rays, const float *d_max_t, size_t n, float shadow_bias, int mode,
                               uint8_t *d_out, void *stream) {
-    RTK_TRY(occluded_check(a, d_rays, d_max_t, n, shadow_bias, mode, d_out));
-    if (n == 0) return RTK_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
-    return occluded_launch(a, d_rays, d_max_t, n, shadow_bias, mode, d_out, static_cast<hipStream_t>(stream), false);
+    return abi_guard([&]() -> int {
+        RTK_TRY(occluded_check(a, d_rays, d_max_t, n, shadow_bias, mode, d_out));
+        if (n == 0) return RTK_OK;
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return occluded_launch(a, d_rays, d_max_t, n, shadow_bias, mode, d_out, static_cast<hipStream_t>(stream), false);
+    });
 }
 
 int rtk_accel_occluded(rtk_accel *a, const rtk_ray *rays, const float *max_t, size_t n, float shadow_bias, int mode, uint8_t *out,
                        uint64_t *n_intersections) {
-    RTK_TRY(occluded_check(a, rays, max_t, n, shadow_bias, mode, out));
-    if (n == 0) {
-        if (n_intersections) *n_intersections = 0;
+    return abi_guard([&]() -> int {
+        RTK_TRY(occluded_check(a, rays, max_t, n, shadow_bias, mode, out));
+        if (n == 0) {
+            if (n_intersections) *n_intersections = 0;
+            return RTK_OK;
+        }
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        RTK_MEM(a->oc_rays.reserve(n));
+        RTK_MEM(a->oc_max_t.reserve(n));
+        RTK_MEM(a->oc_out.reserve(n));
+        RTK_HIP(hipMemcpy(a->oc_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+        RTK_HIP(hipMemcpy(a->oc_max_t.get(), max_t, n * sizeof(float), hipMemcpyHostToDevice));
+        if (n_intersections) RTK_HIP(hipMemsetAsync(a->d_counters.get() + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
+        RTK_TRY(occluded_launch(a, a->oc_rays.get(), a->oc_max_t.get(), n, shadow_bias, mode, a->oc_out.get(), nullptr, n_intersections != nullptr));
+        RTK_HIP(hipMemcpy(out, a->oc_out.get(), n, hipMemcpyDeviceToHost));
+        if (n_intersections) {
+            unsigned long long h = 0;
+            RTK_HIP(hipMemcpy(&h, a->d_counters.get() + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
+            *n_intersections = h;
+        }
         return RTK_OK;
-    }
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a));
-    RTK_MEM(a->oc_rays.reserve(n));
-    RTK_MEM(a->oc_max_t.reserve(n));
-    RTK_MEM(a->oc_out.reserve(n));
-    RTK_HIP(hipMemcpy(a->oc_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-    RTK_HIP(hipMemcpy(a->oc_max_t.get(), max_t, n * sizeof(float), hipMemcpyHostToDevice));
-    if (n_intersections) RTK_HIP(hipMemsetAsync(a->d_counters.get() + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
-    RTK_TRY(occluded_launch(a, a->oc_rays.get(), a->oc_max_t.get(), n, shadow_bias, mode, a->oc_out.get(), nullptr, n_intersections != nullptr));
-    RTK_HIP(hipMemcpy(out, a->oc_out.get(), n, hipMemcpyDeviceToHost));
-    if (n_intersections) {
-        unsigned long long h = 0;
-        RTK_HIP(hipMemcpy(&h, a->d_counters.get() + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
-        *n_intersections = h;
-    }
-    return RTK_OK;
+    });
 }

@@ -121,19 +121,6 @@ int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, b
 
 namespace {
 
-int ensure_twopass_ws(rtk_accel *a, size_t pixels, size_t tiles) {
-    if (pixels <= a->tp_pixels && tiles <= a->tp_tiles) return RTK_OK;
-    const size_t np = pixels > a->tp_pixels ? pixels : a->tp_pixels, nt = tiles > a->tp_tiles ? tiles : a->tp_tiles;
-    RTK_HIP(hipDeviceSynchronize());
-    a->tp_pixels = 0; a->tp_tiles = 0;
-    RTK_MEM(a->tp_prim.reserve(np));
-    RTK_MEM(a->tp_bins.reserve(kCostBins + 1));
-    RTK_MEM(a->tp_bin_list.reserve(size_t(kCostBins) * nt));
-    RTK_MEM(a->tp_order.reserve(nt));
-    a->tp_pixels = np; a->tp_tiles = nt;
-    return RTK_OK;
-}
-
 // output pixels of this rank: the whole frame, or its buckets (padded so that every rank has equal length) of a sharded one
 size_t out_pixels(const FrameGeom &g) {
     return g.world > 1 ? size_t(g.buckets_per_rank) * g.bucket * g.bucket : size_t(g.width) * g.height;
@@ -181,9 +168,16 @@ dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
     return A;
 }
 
-// the counters of a frame or a part of a call start at zero: the kCounterWords and k_block_prior's four behind them
+// the counters of a frame or a part of a call start at zero, with the tail behind them (counters.hpp)
 hipError_t zero_counters(rtk_accel *a, hipStream_t s) {
-    return hipMemsetAsync(a->d_counters.get(), 0, (kCounterWords + 4) * sizeof(unsigned long long), s);
+    return hipMemsetAsync(a->d_counters.get(), 0, kCounterAllocWords * sizeof(unsigned long long), s);
+}
+
+// what rtk_render_last_counters and rtk_render_last_critical_path go by
+void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary) {
+    a->last_stream = s;
+    a->last_stats = stats;
+    a->last_primary = primary;
 }
 
 // the accel's own camera: the scene's at rtk_accel_build, then whatever rtk_accel_set_camera stored there
@@ -287,15 +281,6 @@ int choose_engine(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, 
     return RTK_OK;
 }
 
-int render_twopass(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, bool general, hipStream_t s) {
-    if (p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
-    RTK_TRY(ensure_twopass_ws(a, out_pixels(g), g.blocks()));
-    A.prim = a->tp_prim.get(); A.bin_count = a->tp_bins.get(); A.n_listed = a->tp_bins.get() + kCostBins; A.bin_list = a->tp_bin_list.get();
-    A.tile_order = a->tp_order.get(); A.tile_cap = uint32_t(a->tp_tiles);
-    RTK_HIP_AS(launch_twopass(A, p->collect_stats != 0, general, s), "launch two-pass frame");
-    return RTK_OK;
-}
-
 // `trial[0]` is recorded here, behind the workspace allocation, which is not what a frame costs.
 int render_stream(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const dev::RenderArgs &A, bool forks, bool general,
                   hipEvent_t trial[2], hipStream_t s) {
@@ -385,7 +370,7 @@ int order_launch(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_params *p
     // render is exactly this frame: the reference CLI renders one, src/main.cpp:13-25)
     if (step.prior)
         RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), order, wg_list, order_hdr,
-                                      reinterpret_cast<uint32_t *>(a->d_counters.get() + kCounterWords), 4u, s), "launch k_block_prior");
+                                      reinterpret_cast<uint32_t *>(a->d_counters.get() + kPriorScratchWord), 4u, s), "launch k_block_prior");
     if (step.resort) {
         // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
         RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), order, wg_list, order_hdr, uint32_t(units),
@@ -458,13 +443,12 @@ int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
     RTK_TRY(choose_engine(a, p, g, forks, stream, trial));
     // (the streaming pipeline starts its trial itself, behind its workspace allocation)
     if (trial[0] && !stream) RTK_HIP(hipEventRecord(trial[0], s));
-    if (p->trace_mode == RTK_TRACE_TWOPASS) RTK_TRY(render_twopass(a, p, g, A, general, s));
-    else if (stream) RTK_TRY(render_stream(a, p, g, A, forks, general, trial, s));
+    // (the retired two-pass engine's mode keeps its refusal; its frames are GROUP4's: frame_plan.hpp OrderState::frame_mode)
+    if (p->trace_mode == RTK_TRACE_TWOPASS && p->spp != 1) return fail(RTK_ERR_UNSUPPORTED, "RTK_TRACE_TWOPASS needs spp == 1");
+    if (stream) RTK_TRY(render_stream(a, p, g, A, forks, general, trial, s));
     else RTK_TRY(render_megakernel(a, a->fb, p, g, A, general, s));
     if (trial[1]) RTK_HIP(hipEventRecord(trial[1], s));
-    a->last_stream = s;
-    a->last_stats = p->collect_stats != 0;
-    a->last_primary = primary_rays_of_rank(g);
+    record_last(a, s, p->collect_stats != 0, primary_rays_of_rank(g));
     return RTK_OK;
 }
 
@@ -519,31 +503,40 @@ struct CallCounters {
     }
 };
 
+// The parts of a call that the megakernel takes as launches of many units (views, rectangles): each with cost tables of its own
+// (`tables`, grown to the part count) and folded into the call's totals.  `part_args(c)`: the launch arguments of part c.
+template <typename PartArgs>
+int render_parts(rtk_accel *a, std::vector<rtk_cost_feedback> &tables, size_t n_parts, const rtk_render_params *p, const FrameGeom &g,
+                 hipStream_t s, PartArgs part_args) {
+    if (tables.size() < n_parts) tables.resize(n_parts);
+    const bool general = scene_general(a, p->diffuse_rays);
+    CallCounters cc{a, n_parts > 1, s};
+    RTK_TRY(cc.begin());
+    for (size_t c = 0; c < n_parts; ++c) {
+        dev::RenderArgs A = part_args(c);
+        RTK_TRY(cc.zero_part());
+        RTK_TRY(render_megakernel(a, tables[c], p, g, A, general, s));
+        RTK_TRY(cc.after_part());
+    }
+    return cc.end();
+}
+
 // `h_views`: the views in host memory, or null when the caller has them on the device only (`d_views`, always set).
 int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view *h_views, const rtk_view *d_views,
                       int32_t n_views, float *d_out, hipStream_t s) {
     const size_t stride = size_t(g.width) * g.height * 3;
     const size_t n = size_t(n_views);
-    size_t n_parts = n;
     if (views_one_launch(a, p)) {
         const size_t per_view = g.blocks();                                                       // <= 2^26: a launch of one view fits 31 bits
         const ViewsLaunches cut = views_launches(n, per_view, a->knobs.views_launch_units);
         const size_t per_launch = cut.per_launch;
-        n_parts = cut.n_parts;
-        if (a->fb_views.size() < n_parts) a->fb_views.resize(n_parts);
-        const bool general = scene_general(a, p->diffuse_rays);
-        CallCounters cc{a, n_parts > 1, s};
-        RTK_TRY(cc.begin());
-        for (size_t c = 0; c < n_parts; ++c) {
+        RTK_TRY(render_parts(a, a->fb_views, cut.n_parts, p, g, s, [&](size_t c) {
             const size_t first = c * per_launch, cnt = n - first < per_launch ? n - first : per_launch;
             dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_out + first * stride);     // (the camera in the arguments is not read)
             A.views = reinterpret_cast<const float *>(d_views + first);
             A.n_views = uint32_t(cnt); A.units_per_view = uint32_t(per_view); A.view_stride = stride;
-            RTK_TRY(cc.zero_part());
-            RTK_TRY(render_megakernel(a, a->fb_views[c], p, g, A, general, s));
-            RTK_TRY(cc.after_part());
-        }
-        RTK_TRY(cc.end());
+            return A;
+        }));
     } else {
         std::vector<rtk_view> back;
         if (!h_views) {                          // the engines of this path take the camera in their launch arguments: fetch the views
@@ -552,7 +545,7 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
             RTK_HIP(hipStreamSynchronize(s));
             h_views = back.data();
         }
-        CallCounters cc{a, n_parts > 1, s};
+        CallCounters cc{a, n > 1, s};
         RTK_TRY(cc.begin());
         for (size_t v = 0; v < n; ++v) {
             RTK_TRY(render_frame_impl(a, p, g, h_views[v], d_out + v * stride, s));
@@ -560,9 +553,7 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
         }
         RTK_TRY(cc.end());
     }
-    a->last_stream = s;
-    a->last_stats = p->collect_stats != 0;
-    a->last_primary = primary_rays_of_rank(g) * uint64_t(n);
+    record_last(a, s, p->collect_stats != 0, primary_rays_of_rank(g) * uint64_t(n));
     return RTK_OK;
 }
 
@@ -598,11 +589,10 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
     const int lanes = plan.lanes;
     if (n_chunks_out) *n_chunks_out = uint32_t(plan.n_chunks);
     RTK_TRY(ensure_stream_ws(a, 0, plan.nodes, a->scene.lights.size(), false, lanes));
-    const size_t lane_words = size_t(dev::kStreamLanes) * kCounterWords;
-    RTK_MEM(a->d_rad_counters.reserve(lane_words + 2));
-    unsigned long long *const total = a->d_rad_counters.get() + lane_words;
+    RTK_MEM(a->d_rad_counters.reserve(radiance_total_word(dev::kStreamLanes) + kRadianceTotalWords));
+    unsigned long long *const total = a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes);
     RTK_TRY(claim_stream_ws(a, s));
-    RTK_HIP(hipMemsetAsync(total, 0, 2 * sizeof(unsigned long long), s));
+    RTK_HIP(hipMemsetAsync(total, 0, kRadianceTotalWords * sizeof(unsigned long long), s));
     dev::StreamArgs &S = u.S;
     S.n_lanes = 1;                                       // overflow words: a chunk is judged on its own lane's alone (k_combine, depth 0)
     S.user_sample = uint32_t(p->sample); S.user_cull = p->cull ? 1u : 0u;
@@ -618,7 +608,7 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
         S.user_n = uint32_t(cn); S.user_id0 = uint32_t(first);
         S.n_root = uint32_t((cn + 63) / 64 * 64); S.n_level0 = S.n_root;
         S.r.out = d_rgb + first * 3;
-        S.r.counters = a->d_rad_counters.get() + size_t(j) * kCounterWords;
+        S.r.counters = a->d_rad_counters.get() + radiance_lane_word(j);
         // ctrl: a chunk zeroes its lane's and its counter block on the lane's stream (the overflow word included: it is the chunk's)
         RTK_HIP(hipMemsetAsync(S.ws.ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), ls));
         RTK_HIP(hipMemsetAsync(S.r.counters, 0, kCounterWords * sizeof(unsigned long long), ls));
@@ -693,24 +683,17 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
                         float *d_out, hipStream_t s) {
     RTK_TRY(regions_table(a, g, rects, size_t(n_rects), layout, s));
     const RegionsPlan &P = a->rg_plan;
-    const bool forks = scene_forks(a, p->diffuse_rays), general = scene_general(a, p->diffuse_rays);
+    const bool forks = scene_forks(a, p->diffuse_rays);
     const bool stream = p->trace_mode == RTK_TRACE_STREAM || (p->trace_mode == RTK_TRACE_AUTO && forks);
     dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_out);
     if (!stream) {
         // the megakernel: one launch per RegionLaunch, each with cost tables of its own; several are folded into the call's totals
-        const size_t n_parts = P.launches.size();
-        if (a->fb_regions.size() < n_parts) a->fb_regions.resize(n_parts);
-        CallCounters cc{a, n_parts > 1, s};
-        RTK_TRY(cc.begin());
-        for (size_t c = 0; c < n_parts; ++c) {
+        RTK_TRY(render_parts(a, a->fb_regions, P.launches.size(), p, g, s, [&](size_t c) {
             const RegionLaunch &L = P.launches[c];
-            A.regions = a->rg_table.get() + L.first_entry; A.n_regions = L.n_entries; A.n_units = L.n_units;
-            A.order_in = nullptr; A.order_hdr = nullptr; A.wg_list = nullptr; A.cost_out = nullptr;
-            RTK_TRY(cc.zero_part());
-            RTK_TRY(render_megakernel(a, a->fb_regions[c], p, g, A, general, s));
-            RTK_TRY(cc.after_part());
-        }
-        RTK_TRY(cc.end());
+            dev::RenderArgs R = A;
+            R.regions = a->rg_table.get() + L.first_entry; R.n_regions = L.n_entries; R.n_units = L.n_units;
+            return R;
+        }));
     } else {
         // sample by sample and chunk by chunk: camera rays + frame pixel indices, the radiance pipeline, the sums.  All of a
         // pixel's launches are on `s` (the pipeline forks onto its lanes and joins `s` again), so its sum stays in sample order.
@@ -737,16 +720,14 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
                     RTK_HIP_AS(launch_region_rays(A, smp, first, cn, a->rg_rays.get(), a->rg_ids.get(), s), "launch k_region_rays");
                     rp.sample = smp;
                     RTK_TRY(radiance_device_impl(a, a->rg_rays.get(), a->rg_ids.get(), cn, &rp, a->rg_rgb.get(), s, nullptr));
-                    RTK_HIP_AS(launch_add_word(a->d_counters.get(), a->d_rad_counters.get() + size_t(dev::kStreamLanes) * kCounterWords, s), "launch k_add_word");
+                    RTK_HIP_AS(launch_add_word(a->d_counters.get(), a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes) + kRadianceRays, s), "launch k_add_word");
                     RTK_HIP_AS(launch_region_accumulate(A, first, cn, a->rg_rgb.get(), smp == 0, p->spp != 1 && smp + 1 == p->spp, s), "launch k_region_accumulate");
                 }
             }
         }
     }
     RTK_HIP(a->rg_last.record(s));
-    a->last_stream = s;
-    a->last_stats = false;
-    a->last_primary = P.total_pixels * uint64_t(g.sample_end - g.sample_begin);
+    record_last(a, s, false, P.total_pixels * uint64_t(g.sample_end - g.sample_begin));
     return RTK_OK;
 }
 
@@ -758,191 +739,214 @@ using namespace rtk;
 extern "C" {
 
 int rtk_render_output_floats(const rtk_accel *a, const rtk_render_params *p, size_t *n_floats) {
-    if (!n_floats) return fail(RTK_ERR_INVALID, "null n_floats");
-    FrameGeom g;
-    RTK_TRY(frame_geom(a, p, g));
-    *n_floats = out_pixels(g) * 3;
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!n_floats) return fail(RTK_ERR_INVALID, "null n_floats");
+        FrameGeom g;
+        RTK_TRY(frame_geom(a, p, g));
+        *n_floats = out_pixels(g) * 3;
+        return RTK_OK;
+    });
 }
 
 int rtk_render_frame_device(rtk_accel *a, const rtk_render_params *p, float *d_out, void *stream) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
-    return render_device_impl(a, p, d_out, static_cast<hipStream_t>(stream));
+    return abi_guard([&]() -> int {
+        if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return render_device_impl(a, p, d_out, static_cast<hipStream_t>(stream));
+    });
 }
 
 int rtk_render_last_counters(rtk_accel *a, rtk_counters *c) {
-    if (!a || !c) return fail(RTK_ERR_INVALID, "null accel or counters");
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
-    RTK_HIP(hipSetDevice(a->device));
-    RTK_HIP(hipStreamSynchronize(a->last_stream));
-    unsigned long long h[kCounterWords];
-    RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
-    std::memset(c, 0, sizeof(*c));
-    for (int i = 0; i < kRayCounterShards; ++i) h[0] += h[8 + i];      // the frame kernel shards its ray counter
-    c->rays = h[0]; c->primary = a->last_primary;
-    if (a->last_stats) { c->hits = h[2]; c->nodes = h[3]; c->boxpass = h[4]; c->leaves = h[5]; c->tris = h[6]; c->packets16 = h[7]; }
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !c) return fail(RTK_ERR_INVALID, "null accel or counters");
+        std::lock_guard<std::mutex> lock(a->mu);
+        if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
+        RTK_HIP(hipSetDevice(a->device));
+        RTK_HIP(hipStreamSynchronize(a->last_stream));
+        unsigned long long h[kCounterWords];
+        RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
+        counters_from_block(h, a->last_stats, c);
+        for (int i = 0; i < kRayCounterShards; ++i) c->rays += h[kRayShardWord + i];      // the frame kernel shards its ray counter
+        c->primary = a->last_primary;
+        return RTK_OK;
+    });
 }
 
 int rtk_render_last_critical_path(rtk_accel *a, double *ms) {
-    if (!a || !ms) return fail(RTK_ERR_INVALID, "null accel or ms");
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
-    RTK_HIP(hipSetDevice(a->device));
-    RTK_HIP(hipStreamSynchronize(a->last_stream));
-    unsigned long long shard[kRayCounterShards], ticks = 0;
-    RTK_HIP(hipMemcpy(shard, a->d_counters.get() + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
-    for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
-    *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !ms) return fail(RTK_ERR_INVALID, "null accel or ms");
+        std::lock_guard<std::mutex> lock(a->mu);
+        if (!a->on_device) return fail(RTK_ERR_INVALID, "no frame has been rendered on this accel");
+        RTK_HIP(hipSetDevice(a->device));
+        RTK_HIP(hipStreamSynchronize(a->last_stream));
+        unsigned long long shard[kRayCounterShards], ticks = 0;
+        RTK_HIP(hipMemcpy(shard, a->d_counters.get() + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
+        for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
+        *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
+        return RTK_OK;
+    });
 }
 
 int rtk_render_frame(rtk_accel *a, const rtk_render_params *p, float *rgb, rtk_counters *counters) {
-    if (!a || !p || !rgb) return fail(RTK_ERR_INVALID, "null accel, params or rgb");
-    if (p->world_size > 1) return fail(RTK_ERR_INVALID, "rtk_render_frame renders whole frames; use rtk_render_frame_device for sharded output");
-    size_t nf = 0;
-    RTK_TRY(rtk_render_output_floats(a, p, &nf));
-    {
-        std::lock_guard<std::mutex> lock(a->mu);
-        RTK_TRY(ensure_device(a));
-        DevBuf<float> d_out;                     // (the call's own: freed when the block is left)
-        RTK_MEM(d_out.reserve(nf));
-        // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
-        if (p->sample_begin > 0) RTK_HIP_AS(hipMemcpy(d_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice), "upload of the running sums");
-        RTK_TRY(render_device_impl(a, p, d_out.get(), nullptr));
-        RTK_HIP_AS(hipMemcpy(rgb, d_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost), "frame copy");
-    }
-    if (counters) return rtk_render_last_counters(a, counters);
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !p || !rgb) return fail(RTK_ERR_INVALID, "null accel, params or rgb");
+        if (p->world_size > 1) return fail(RTK_ERR_INVALID, "rtk_render_frame renders whole frames; use rtk_render_frame_device for sharded output");
+        size_t nf = 0;
+        RTK_TRY(rtk_render_output_floats(a, p, &nf));
+        {
+            std::lock_guard<std::mutex> lock(a->mu);
+            RTK_TRY(ensure_device(a));
+            DevBuf<float> d_out;                     // (the call's own: freed when the block is left)
+            RTK_MEM(d_out.reserve(nf));
+            // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
+            if (p->sample_begin > 0) RTK_HIP_AS(hipMemcpy(d_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice), "upload of the running sums");
+            RTK_TRY(render_device_impl(a, p, d_out.get(), nullptr));
+            RTK_HIP_AS(hipMemcpy(rgb, d_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost), "frame copy");
+        }
+        if (counters) return rtk_render_last_counters(a, counters);
+        return RTK_OK;
+    });
 }
 
 int rtk_tiles_assemble_device(const rtk_accel *a, const rtk_render_params *p, const float *d_gathered, float *d_rgb, void *stream) {
-    FrameGeom g;
-    RTK_TRY(frame_geom(a, p, g));
-    if (!d_gathered || !d_rgb) return fail(RTK_ERR_INVALID, "null buffer");
-    dev::AssembleArgs A;
-    A.gathered = d_gathered; A.rgb = d_rgb; A.width = g.width; A.height = g.height; A.bucket = g.bucket;
-    A.tiles_x = g.tiles_x; A.world = uint32_t(g.world); A.buckets_per_rank = g.buckets_per_rank; A.skew_q = g.skew_q;
-    RTK_HIP_AS(launch_assemble(A, static_cast<hipStream_t>(stream)), "launch k_assemble");
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        FrameGeom g;
+        RTK_TRY(frame_geom(a, p, g));
+        if (!d_gathered || !d_rgb) return fail(RTK_ERR_INVALID, "null buffer");
+        dev::AssembleArgs A;
+        A.gathered = d_gathered; A.rgb = d_rgb; A.width = g.width; A.height = g.height; A.bucket = g.bucket;
+        A.tiles_x = g.tiles_x; A.world = uint32_t(g.world); A.buckets_per_rank = g.buckets_per_rank; A.skew_q = g.skew_q;
+        RTK_HIP_AS(launch_assemble(A, static_cast<hipStream_t>(stream)), "launch k_assemble");
+        return RTK_OK;
+    });
 }
 
 // ---------------------------------------------------------------- batched radiance
 
 int rtk_accel_radiance_device(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
                               float *d_rgb, void *stream) {
-    RTK_TRY(radiance_check(a, d_rays, d_ids, n, p, d_rgb));
-    if (n == 0) return RTK_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
-    return radiance_device_impl(a, d_rays, d_ids, n, p, d_rgb, static_cast<hipStream_t>(stream), nullptr);
+    return abi_guard([&]() -> int {
+        RTK_TRY(radiance_check(a, d_rays, d_ids, n, p, d_rgb));
+        if (n == 0) return RTK_OK;
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return radiance_device_impl(a, d_rays, d_ids, n, p, d_rgb, static_cast<hipStream_t>(stream), nullptr);
+    });
 }
 
 int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, size_t n, const rtk_radiance_params *p, float *rgb,
                        rtk_counters *counters) {
-    RTK_TRY(radiance_check(a, rays, ids, n, p, rgb));
-    if (n == 0) {
-        if (counters) std::memset(counters, 0, sizeof(*counters));
+    return abi_guard([&]() -> int {
+        RTK_TRY(radiance_check(a, rays, ids, n, p, rgb));
+        if (n == 0) {
+            if (counters) std::memset(counters, 0, sizeof(*counters));
+            return RTK_OK;
+        }
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        RTK_MEM(a->rad_rays.reserve(n));
+        RTK_MEM(a->rad_ids.reserve(n));
+        RTK_MEM(a->rad_rgb.reserve(n * 3));
+        RTK_HIP(hipMemcpy(a->rad_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
+        if (ids) RTK_HIP(hipMemcpy(a->rad_ids.get(), ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        uint32_t n_chunks = 0;
+        RTK_TRY(radiance_device_impl(a, a->rad_rays.get(), ids ? a->rad_ids.get() : nullptr, n, p, a->rad_rgb.get(), nullptr, &n_chunks));
+        RTK_HIP(hipMemcpy(rgb, a->rad_rgb.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        unsigned long long h[kRadianceTotalWords] = {};
+        RTK_HIP(hipMemcpy(h, a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes), sizeof(h), hipMemcpyDeviceToHost));
+        if (counters) {
+            std::memset(counters, 0, sizeof(*counters));
+            counters->rays = h[kRadianceRays]; counters->primary = n;
+        }
+        if (a->knobs.stream_debug)
+            std::fprintf(stderr, "[rtk radiance] rays %zu chunks %u redone %llu node_cap %u\n", n, n_chunks, h[kRadianceRedone], a->ws.node_cap);
         return RTK_OK;
-    }
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a));
-    RTK_MEM(a->rad_rays.reserve(n));
-    RTK_MEM(a->rad_ids.reserve(n));
-    RTK_MEM(a->rad_rgb.reserve(n * 3));
-    RTK_HIP(hipMemcpy(a->rad_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-    if (ids) RTK_HIP(hipMemcpy(a->rad_ids.get(), ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    uint32_t n_chunks = 0;
-    RTK_TRY(radiance_device_impl(a, a->rad_rays.get(), ids ? a->rad_ids.get() : nullptr, n, p, a->rad_rgb.get(), nullptr, &n_chunks));
-    RTK_HIP(hipMemcpy(rgb, a->rad_rgb.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    unsigned long long h[2] = {0, 0};
-    RTK_HIP(hipMemcpy(h, a->d_rad_counters.get() + size_t(dev::kStreamLanes) * kCounterWords, sizeof(h), hipMemcpyDeviceToHost));
-    if (counters) {
-        std::memset(counters, 0, sizeof(*counters));
-        counters->rays = h[0]; counters->primary = n;
-    }
-    if (a->knobs.stream_debug)
-        std::fprintf(stderr, "[rtk radiance] rays %zu chunks %u redone %llu node_cap %u\n", n, n_chunks, h[1], a->ws.node_cap);
-    return RTK_OK;
+    });
 }
 
 // ---------------------------------------------------------------- camera and views
 
 int rtk_accel_get_camera(const rtk_accel *a, rtk_view *out) {
-    if (!a || !out) return fail(RTK_ERR_INVALID, "null accel or view");
-    std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
-    *out = accel_camera(a);
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !out) return fail(RTK_ERR_INVALID, "null accel or view");
+        std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
+        *out = accel_camera(a);
+        return RTK_OK;
+    });
 }
 
 int rtk_accel_set_camera(rtk_accel *a, const rtk_view *view) {
-    if (!a || !view) return fail(RTK_ERR_INVALID, "null accel or view");
-    std::lock_guard<std::mutex> lock(a->mu);
-    std::memcpy(a->scene.cam_pos, view->position, sizeof(a->scene.cam_pos));
-    std::memcpy(a->scene.cam_mat, view->matrix, sizeof(a->scene.cam_mat));
-    // The launch order learnt under the previous camera changes no result, only the order.  It starts over (the first-frame prior,
-    // then the new camera's costs), as after an update of the geometry: measured, neither choice wins every run on the first
-    // frame, and the third takes 0.20 ms against 0.30 under a kept order, which is served until its next re-sort (rtk.h;
-    // RTK_CAMERA_KEEPS_ORDER=1 keeps it).  RTK_TRACE_AUTO's
-    // engine verdict stays: started over at every move, the trial of a camera in motion would never end.
-    // (rectangles are seen from the accel's camera; views bring their own)
-    if (!a->knobs.camera_keeps_order) forget_orders(a, kKeepViewOrders | kKeepTrial);
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !view) return fail(RTK_ERR_INVALID, "null accel or view");
+        std::lock_guard<std::mutex> lock(a->mu);
+        std::memcpy(a->scene.cam_pos, view->position, sizeof(a->scene.cam_pos));
+        std::memcpy(a->scene.cam_mat, view->matrix, sizeof(a->scene.cam_mat));
+        // The launch order learnt under the previous camera changes no result, only the order.  It starts over (the first-frame prior,
+        // then the new camera's costs), as after an update of the geometry: measured, neither choice wins every run on the first
+        // frame, and the third takes 0.20 ms against 0.30 under a kept order, which is served until its next re-sort (rtk.h;
+        // RTK_CAMERA_KEEPS_ORDER=1 keeps it).  RTK_TRACE_AUTO's
+        // engine verdict stays: started over at every move, the trial of a camera in motion would never end.
+        // (rectangles are seen from the accel's camera; views bring their own)
+        if (!a->knobs.camera_keeps_order) forget_orders(a, kKeepViewOrders | kKeepTrial);
+        return RTK_OK;
+    });
 }
 
 int rtk_render_views_device(rtk_accel *a, const rtk_render_params *p, const rtk_view *d_views, int32_t n_views, float *d_out, void *stream) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    FrameGeom g;
-    RTK_TRY(views_check(a, p, d_views, n_views, d_out, g));
-    if (n_views == 0) return RTK_OK;
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
-    return render_views_impl(a, p, g, nullptr, d_views, n_views, d_out, static_cast<hipStream_t>(stream));
+    return abi_guard([&]() -> int {
+        if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+        FrameGeom g;
+        RTK_TRY(views_check(a, p, d_views, n_views, d_out, g));
+        if (n_views == 0) return RTK_OK;
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
+        return render_views_impl(a, p, g, nullptr, d_views, n_views, d_out, static_cast<hipStream_t>(stream));
+    });
 }
 
 int rtk_render_views(rtk_accel *a, const rtk_render_params *p, const rtk_view *views, int32_t n_views, float *rgb, rtk_counters *counters) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    FrameGeom g;
-    RTK_TRY(views_check(a, p, views, n_views, rgb, g));
-    if (n_views == 0) return RTK_OK;
-    {
-        std::lock_guard<std::mutex> lock(a->mu);
-        RTK_TRY(ensure_device(a));
-        const size_t n = size_t(n_views), nf = n * g.width * g.height * 3;
-        RTK_MEM(a->views_tab.reserve(n));
-        RTK_MEM(a->views_out.reserve(nf));
-        RTK_HIP(hipMemcpy(a->views_tab.get(), views, n * sizeof(rtk_view), hipMemcpyHostToDevice));
-        // a later pass of progressive views continues the running per-pixel sums the previous pass left in `rgb`
-        if (p->sample_begin > 0) RTK_HIP(hipMemcpy(a->views_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
-        RTK_TRY(render_views_impl(a, p, g, views, a->views_tab.get(), n_views, a->views_out.get(), nullptr));
-        RTK_HIP(hipMemcpy(rgb, a->views_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    if (counters) return rtk_render_last_counters(a, counters);
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
+        FrameGeom g;
+        RTK_TRY(views_check(a, p, views, n_views, rgb, g));
+        if (n_views == 0) return RTK_OK;
+        {
+            std::lock_guard<std::mutex> lock(a->mu);
+            RTK_TRY(ensure_device(a));
+            const size_t n = size_t(n_views), nf = n * g.width * g.height * 3;
+            RTK_MEM(a->views_tab.reserve(n));
+            RTK_MEM(a->views_out.reserve(nf));
+            RTK_HIP(hipMemcpy(a->views_tab.get(), views, n * sizeof(rtk_view), hipMemcpyHostToDevice));
+            // a later pass of progressive views continues the running per-pixel sums the previous pass left in `rgb`
+            if (p->sample_begin > 0) RTK_HIP(hipMemcpy(a->views_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
+            RTK_TRY(render_views_impl(a, p, g, views, a->views_tab.get(), n_views, a->views_out.get(), nullptr));
+            RTK_HIP(hipMemcpy(rgb, a->views_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        if (counters) return rtk_render_last_counters(a, counters);
+        return RTK_OK;
+    });
 }
 
 // ---------------------------------------------------------------- regions
 
 int rtk_render_regions_device(rtk_accel *a, const rtk_render_params *p, const rtk_rect *rects, int32_t n_rects, int layout, float *d_out,
                               void *stream) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
         FrameGeom g;
         RTK_TRY(regions_check(a, p, rects, n_rects, layout, d_out, g));
         if (n_rects == 0 || regions_pixels(rects, n_rects) == 0) return RTK_OK;
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a, static_cast<hipStream_t>(stream)));
         return render_regions_impl(a, p, g, rects, n_rects, layout, d_out, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_render_regions(rtk_accel *a, const rtk_render_params *p, const rtk_rect *rects, int32_t n_rects, int layout, float *rgb,
                        rtk_counters *counters) {
-    if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !p) return fail(RTK_ERR_INVALID, "null accel or params");
         FrameGeom g;
         RTK_TRY(regions_check(a, p, rects, n_rects, layout, rgb, g));
         const uint64_t pixels = n_rects > 0 ? regions_pixels(rects, n_rects) : 0;
@@ -961,39 +965,43 @@ int rtk_render_regions(rtk_accel *a, const rtk_render_params *p, const rtk_rect 
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 // ---------------------------------------------------------------- camera rays
 
 int rtk_camera_rays_device(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *d_rays, void *stream) {
-    if (!a || !p || !d_rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
-    std::lock_guard<std::mutex> lock(a->mu);
-    RTK_TRY(ensure_device(a));
-    FrameGeom g;
-    RTK_TRY(frame_geom(a, p, g));
-    if (sample < 0 || sample >= p->spp) return fail(RTK_ERR_INVALID, "sample must be in [0, spp)");
-    dev::RenderArgs A;
-    std::memset(&A, 0, sizeof(A));
-    camera_args(accel_camera(a), p, g, A);
-    RTK_HIP_AS(launch_camera_rays(A, sample, d_rays, static_cast<hipStream_t>(stream)), "launch k_camera_rays");
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !p || !d_rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
+        std::lock_guard<std::mutex> lock(a->mu);
+        RTK_TRY(ensure_device(a));
+        FrameGeom g;
+        RTK_TRY(frame_geom(a, p, g));
+        if (sample < 0 || sample >= p->spp) return fail(RTK_ERR_INVALID, "sample must be in [0, spp)");
+        dev::RenderArgs A;
+        std::memset(&A, 0, sizeof(A));
+        camera_args(accel_camera(a), p, g, A);
+        RTK_HIP_AS(launch_camera_rays(A, sample, d_rays, static_cast<hipStream_t>(stream)), "launch k_camera_rays");
+        return RTK_OK;
+    });
 }
 
 int rtk_camera_rays(rtk_accel *a, const rtk_render_params *p, int32_t sample, rtk_ray *rays) {
-    if (!a || !p || !rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
-    FrameGeom g;
-    RTK_TRY(frame_geom(a, p, g));
-    const size_t n = size_t(g.width) * g.height;
-    DevBuf<rtk_ray> d;
-    {
-        std::lock_guard<std::mutex> lock(a->mu);
-        RTK_TRY(ensure_device(a));
-        RTK_MEM(d.reserve(n));
-    }
-    RTK_TRY(rtk_camera_rays_device(a, p, sample, d.get(), nullptr));
-    RTK_HIP_AS(hipMemcpy(rays, d.get(), n * sizeof(rtk_ray), hipMemcpyDeviceToHost), "camera ray copy");
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !p || !rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
+        FrameGeom g;
+        RTK_TRY(frame_geom(a, p, g));
+        const size_t n = size_t(g.width) * g.height;
+        DevBuf<rtk_ray> d;
+        {
+            std::lock_guard<std::mutex> lock(a->mu);
+            RTK_TRY(ensure_device(a));
+            RTK_MEM(d.reserve(n));
+        }
+        RTK_TRY(rtk_camera_rays_device(a, p, sample, d.get(), nullptr));
+        RTK_HIP_AS(hipMemcpy(rays, d.get(), n * sizeof(rtk_ray), hipMemcpyDeviceToHost), "camera ray copy");
+        return RTK_OK;
+    });
 }
 
 }  // extern "C"

@@ -32,25 +32,27 @@ void lights_changed(rtk_accel *a, size_t n_before) {
 extern "C" {
 
 int rtk_accel_get_lights(const rtk_accel *a, rtk_light *out, int32_t cap, int32_t *n) {
-    if (!a || !n) return fail(RTK_ERR_INVALID, "null accel or count");
-    std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
-    const size_t have = a->scene.lights.size();
-    *n = int32_t(have);
-    const size_t take = (out && cap > 0) ? std::min(have, size_t(cap)) : 0;
-    if (take == 0) return RTK_OK;
-    if (a->lights_on_device) {
-        RTK_HIP(hipSetDevice(a->device));
-        RTK_HIP(hipDeviceSynchronize());
-        RTK_HIP(hipMemcpy(out, a->d_lights.get(), take * sizeof(rtk_light), hipMemcpyDeviceToHost));
-    } else std::memcpy(out, a->scene.lights.data(), take * sizeof(rtk_light));
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !n) return fail(RTK_ERR_INVALID, "null accel or count");
+        std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
+        const size_t have = a->scene.lights.size();
+        *n = int32_t(have);
+        const size_t take = (out && cap > 0) ? std::min(have, size_t(cap)) : 0;
+        if (take == 0) return RTK_OK;
+        if (a->lights_on_device) {
+            RTK_HIP(hipSetDevice(a->device));
+            RTK_HIP(hipDeviceSynchronize());
+            RTK_HIP(hipMemcpy(out, a->d_lights.get(), take * sizeof(rtk_light), hipMemcpyDeviceToHost));
+        } else std::memcpy(out, a->scene.lights.data(), take * sizeof(rtk_light));
+        return RTK_OK;
+    });
 }
 
 int rtk_accel_set_lights(rtk_accel *a, const rtk_light *lights, int32_t n) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    if (n < 0 || (n > 0 && !lights)) return fail(RTK_ERR_INVALID, "negative light count or null lights");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a) return fail(RTK_ERR_INVALID, "null accel");
+        if (n < 0 || (n > 0 && !lights)) return fail(RTK_ERR_INVALID, "negative light count or null lights");
+        std::lock_guard<std::mutex> lock(a->mu);
         std::vector<DevLight> table(static_cast<size_t>(n));
         if (n > 0) std::memcpy(table.data(), lights, size_t(n) * sizeof(DevLight));
         if (a->on_device) {
@@ -65,14 +67,14 @@ int rtk_accel_set_lights(rtk_accel *a, const rtk_light *lights, int32_t n) {
         a->lights_on_device = false;
         lights_changed(a, before);
         return RTK_OK;
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_accel_set_lights_device(rtk_accel *a, const rtk_light *d_lights, int32_t n, void *hip_stream) {
-    if (!a) return fail(RTK_ERR_INVALID, "null accel");
-    if (n < 0 || (n > 0 && !d_lights)) return fail(RTK_ERR_INVALID, "negative light count or null lights");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a) return fail(RTK_ERR_INVALID, "null accel");
+        if (n < 0 || (n > 0 && !d_lights)) return fail(RTK_ERR_INVALID, "negative light count or null lights");
+        std::lock_guard<std::mutex> lock(a->mu);
         hipStream_t s = static_cast<hipStream_t>(hip_stream);
         RTK_TRY(ensure_device(a));
         RTK_HIP(a->geom_fence.quiesce());
@@ -85,20 +87,22 @@ int rtk_accel_set_lights_device(rtk_accel *a, const rtk_light *d_lights, int32_t
         a->lights_on_device = true;
         lights_changed(a, before);
         return RTK_OK;
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_accel_get_materials(const rtk_accel *a, rtk_material *out) {
-    if (!a || !out) return fail(RTK_ERR_INVALID, "null accel or materials");
-    std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
-    if (!a->scene.materials.empty()) std::memcpy(out, a->scene.materials.data(), a->scene.materials.size() * sizeof(rtk_material));
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !out) return fail(RTK_ERR_INVALID, "null accel or materials");
+        std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
+        if (!a->scene.materials.empty()) std::memcpy(out, a->scene.materials.data(), a->scene.materials.size() * sizeof(rtk_material));
+        return RTK_OK;
+    });
 }
 
 int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t n) {
-    if (!a || !materials) return fail(RTK_ERR_INVALID, "null accel or materials");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !materials) return fail(RTK_ERR_INVALID, "null accel or materials");
+        std::lock_guard<std::mutex> lock(a->mu);
         if (n < 0 || size_t(n) != a->scene.materials.size()) return fail(RTK_ERR_INVALID, "the number of materials is fixed when the scene is made");
         // scene.cpp, scene_from_desc
         std::vector<DevMaterial> table(static_cast<size_t>(n));
@@ -125,21 +129,25 @@ int rtk_accel_set_materials(rtk_accel *a, const rtk_material *materials, int32_t
         // a scene that starts or stops forking runs other kernels over other block costs, and needs a new verdict
         forget_orders(a);
         return RTK_OK;
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_accel_get_background(const rtk_accel *a, float rgb[3]) {
-    if (!a || !rgb) return fail(RTK_ERR_INVALID, "null accel or colour");
-    std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
-    std::memcpy(rgb, a->scene.background, sizeof(a->scene.background));
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !rgb) return fail(RTK_ERR_INVALID, "null accel or colour");
+        std::lock_guard<std::mutex> lock(const_cast<rtk_accel *>(a)->mu);
+        std::memcpy(rgb, a->scene.background, sizeof(a->scene.background));
+        return RTK_OK;
+    });
 }
 
 int rtk_accel_set_background(rtk_accel *a, const float rgb[3]) {
-    if (!a || !rgb) return fail(RTK_ERR_INVALID, "null accel or colour");
-    std::lock_guard<std::mutex> lock(a->mu);
-    std::memcpy(a->scene.background, rgb, sizeof(a->scene.background));
-    return RTK_OK;
+    return abi_guard([&]() -> int {
+        if (!a || !rgb) return fail(RTK_ERR_INVALID, "null accel or colour");
+        std::lock_guard<std::mutex> lock(a->mu);
+        std::memcpy(a->scene.background, rgb, sizeof(a->scene.background));
+        return RTK_OK;
+    });
 }
 
 }  // extern "C"

@@ -385,20 +385,20 @@ int rtk::remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &material
 }
 
 int rtk_accel_update_vertices_device(rtk_accel *a, const float *d_vertices, void *hip_stream) {
-    if (!a || !d_vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !d_vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
+        std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
         // entry: nothing issued earlier on this accel, on whatever stream, may still read a buffer the update rewrites
         RTK_HIP(a->geom_fence.quiesce());
         return update_impl(a, d_vertices, nullptr, static_cast<hipStream_t>(hip_stream));
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
-    if (!a || !vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !vertices) return fail(RTK_ERR_INVALID, "null accel or vertices");
+        std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
         const size_t n = size_t(a->scene.n_vertices) * 3;
         for (size_t i = 0; i < n; ++i)
@@ -407,27 +407,27 @@ int rtk_accel_update_vertices(rtk_accel *a, const float *vertices) {
         RTK_MEM(a->up_verts.reserve(n));                                    // (once: the vertex count never changes)
         if (n > 0) RTK_HIP(hipMemcpy(a->up_verts.get(), vertices, n * sizeof(float), hipMemcpyHostToDevice));
         return update_impl(a, a->up_verts.get(), nullptr, nullptr);
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 int rtk_accel_update_geometry_device(rtk_accel *a, const float *d_vertices, const uint32_t *d_indices, const int32_t *mesh_ntris, void *hip_stream) {
-    if (!a || !d_vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !d_vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
+        std::lock_guard<std::mutex> lock(a->mu);
         if (!d_indices && any_triangles(a, mesh_ntris)) return fail(RTK_ERR_INVALID, "null indices");
         RTK_TRY(ensure_device(a));
         NewTopology N{d_indices, mesh_ntris, 0u};
         RTK_TRY(check_counts(a, mesh_ntris, N.n_tris));
         RTK_HIP(a->geom_fence.quiesce());
         return update_impl(a, d_vertices, &N, static_cast<hipStream_t>(hip_stream));
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }
 
 // validate + stage + the device path
 int rtk_accel_update_geometry(rtk_accel *a, const float *vertices, const uint32_t *indices, const int32_t *mesh_ntris) {
-    if (!a || !vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
-    std::lock_guard<std::mutex> lock(a->mu);
-    try {
+    return abi_guard([&]() -> int {
+        if (!a || !vertices || !mesh_ntris) return fail(RTK_ERR_INVALID, "null accel, vertices or mesh_ntris");
+        std::lock_guard<std::mutex> lock(a->mu);
         if (!indices && any_triangles(a, mesh_ntris)) return fail(RTK_ERR_INVALID, "null indices");
         RTK_TRY(ensure_device(a));
         NewTopology N{nullptr, mesh_ntris, 0u};
@@ -449,5 +449,5 @@ int rtk_accel_update_geometry(rtk_accel *a, const float *vertices, const uint32_
         if (N.n_tris > 0u) RTK_HIP(hipMemcpy(a->up_idx_stage.get(), indices, size_t(N.n_tris) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
         N.d_indices = a->up_idx_stage.get();
         return update_impl(a, a->up_verts.get(), &N, nullptr);
-    } catch (const std::exception &e) { return fail(RTK_ERR_INVALID, e.what()); }
+    });
 }

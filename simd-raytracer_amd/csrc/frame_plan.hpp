@@ -77,7 +77,9 @@ struct OrderState {
     // over, eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
     // Measured on config 2 (tools/rank_times.py): 32,400 blocks 0.44 ms (GROUP4) vs 0.87 (GROUP8); 4,050 blocks 0.43 vs 0.32.
     // (A views launch counts the blocks of all its views: many small views get the four-wave workgroups.)
+    // RTK_TRACE_TWOPASS named an engine that the cost feedback superseded: its frames are GROUP4's.
     static int frame_mode(int trace_mode, size_t n_units, size_t group8_below) {
+        if (trace_mode == RTK_TRACE_TWOPASS) return RTK_TRACE_GROUP4;
         return trace_mode != RTK_TRACE_AUTO ? trace_mode : (n_units < group8_below ? RTK_TRACE_GROUP8 : RTK_TRACE_GROUP4);
     }
 

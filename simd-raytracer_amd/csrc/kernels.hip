@@ -186,14 +186,11 @@ struct Frame {            // 15 dwords, lives in scratch; touched only at refrac
     uint32_t key;         // RNG key of the ray whose hit this frame shades
 };
 
-template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool PRIMED = false, bool VIEWS = false, bool REGIONS = false>
+template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool VIEWS = false, bool REGIONS = false>
 // GROUP4 without per-ray statistics is built for RTK_G4_WAVES (5) waves per SIMD = 96 VGPRs: a fifth resident workgroup per CU.
 // The lean build (FORKS = false) fits with its cold state parked in LDS (`park_lds`); 4 waves / 128 VGPRs and 6 / 80 are slower.
 __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : SLICES == 8 ? 2 : (SLICES == 4 && !STATS ? RTK_G4_WAVES : 4)) void k_render(RenderArgs A) {
-    // PRIMED (second pass of a two-pass frame): pixel blocks come from tile_order (most expensive first) and the
-    // camera ray's hit is read from A.prim instead of being traced again
     FrameProbe phases = FrameProbe::enter();                     // diagnostic build only (phases.hip.hpp); empty in the product
-    if (PRIMED && blockIdx.x >= *A.n_listed) return;
     if (A.only_if != nullptr && *A.only_if == 0u) return;        // fallback launch behind the streaming pipeline: nothing overflowed
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
@@ -215,9 +212,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     // leaves as the whole block's, so it cost as much as the block.)
     uint32_t gwave;
     bool light = false;
-    if (PRIMED) {
-        gwave = A.tile_order[blockIdx.x];
-    } else if (SLICES > 1 && A.order_in != nullptr) {
+    if (SLICES > 1 && A.order_in != nullptr) {
         const uint32_t n_wgs = A.order_hdr[0], n_total = A.order_hdr[1];
         if (blockIdx.x >= n_wgs) return;
         const uint32_t desc = A.wg_list[blockIdx.x];                        // k_order_by_cost: workgroups by expected duration
@@ -360,7 +355,6 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     Stats st = {0, 0, 0, 0, 0, 0};
     Cand cand;
     cand.t = kFltMax; cand.u = cand.v = 0.f; cand.k = kMiss;
-    bool primed = false;
     // apex hint of the ray in flight (trace.hip.hpp "Pencil bundles"): camera rays leave the camera; their reflections off a
     // plane leave the camera's mirror image.  A hint only: wrong or noisy, it loosens the culling and changes no result.
     V3 mirror_apex = black;
@@ -395,7 +389,6 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 else ray = camera_ray(A, p.px, p.py, rkey);
                 mirror_apex = ray.o;
                 cull = true; depth = 0; pend = PEND_CHILD_BG; fsp = 0;
-                primed = PRIMED;
                 state = ST_TRACE;
             } else if (state == ST_SHADE) {                                 // color_hit, render.hpp:133-308
                 if (depth == A.max_depth) { ret = background; state = ST_RETURN; continue; }   // :138-139
@@ -572,7 +565,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
                 elsewhere = burst & sh_lane & (burst_my_part != 0u);
             }
         }
-        const bool quiet = kRootFirst && !burst && !(PRIMED && wave_any(primed)) && !wave_any(in_root);
+        const bool quiet = kRootFirst && !burst && !wave_any(in_root);
         if (quiet) {
             cand.t = kFltMax; cand.u = cand.v = 0.f; cand.k = kMiss;
             burst_done = false;
@@ -587,57 +580,45 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
         park[9 * 64] = ncos.x; park[10 * 64] = ncos.y; park[11 * 64] = ncos.z;
         park[12 * 64] = P.x; park[13 * 64] = P.y; park[14 * 64] = P.z;
         park[15 * 64] = mirror_apex.x; park[16 * 64] = mirror_apex.y; park[17 * 64] = mirror_apex.z;
-        if (PRIMED && wave_any(primed)) {
-            // first iteration of the pass: every pending ray is a camera ray whose hit the first pass already found
-            if (need) {
-                const Pixel p = my_pixel();
-                const float4 pc = A.prim[A.out_index(local_bucket, p.lx, p.ly, p.px, p.py)];
-                cand.t = pc.x; cand.u = pc.y; cand.v = pc.z; cand.k = __float_as_uint(pc.w);
-            }
-            nrays_wave -= (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(need));   // counted by the first pass
-            primed = false;
-            burst_done = false;
-        } else {
-            phases.trace_begins();
-            // shadow rays of scenes without transmissive materials only ask "is the closest hit nearer than the light":
-            // they may stop at the first hit that says yes (trace(), `exit_t`; A.shadow_exit is set by the host).
-            const float exit_t = (A.shadow_exit && pend == PEND_SHADOW) ? shadow_max_t : -1.0f;
-            // ray class for the bundle culling: shadow rays by light, everything else by depth (camera rays = 0)
-            // (shadow rays end in their light: the lines of a class pass through that point, the "apex" of a pencil bundle)
-            uint32_t cls = (uint32_t)depth;
-            V3 apex = black;
-            if (pend == PEND_CHILD_BG) { cls |= kClsHasApex; apex = mirror_apex; }      // camera rays and chains of reflections
-            if (pend == PEND_SHADOW) {
-                const DevLight *L = A.lights + light_k;
-                cls = kClsHasApex | (0x100u + (uint32_t)light_k + 0x40u * (uint32_t)depth);   // (different depths: different surfaces)
-                apex = mk(L->pos[0], L->pos[1], L->pos[2]);
-            }
-            if (burst) {
-                const uint32_t lane = fresh_lane();
-                group_sh->ray_o[lane] = make_float4(P.x, P.y, P.z, ncos.x);
-                group_sh->ray_d[lane] = make_float4(ncos.y, ncos.z, reach, 0.f);
-                if (lane == 0u) {
-                    group_sh->pass_mask = burst_mask; group_sh->first = burst_k; group_sh->count = burst_plog | ((burst_nl << burst_plog) << 8);
-                    group_sh->pad[0] = 1u;                                  // next job to hand out (job 0 is traced right here)
-                    // (an opaque constant: folded, it becomes one lane of a three-register tuple {first, count, kind} that is
-                    // set up in the kernel's prologue and spilled to scratch until it is needed here)
-                    uint32_t extra = GROUP_EXTRA;
-                    asm volatile("" : "+v"(extra));
-                    group_sh->kind = extra;
-                }
-                __syncthreads();                                            // B1: the helpers start on their lights
-                sx.min_tris = 0xFFFFFFFFu;                                  // (they are busy: the owner's own leaves stay whole)
-            }
-            cand = trace<MODE, STATS, kStage, SLICES, kRootFirst>(A.tree, lds_nodes, ray, cull, in_root & !elsewhere, st, sx, kAutoMinLanes, exit_t, cls, apex);   // (in_root: no unlit lane)
-            phases.trace_returned();
-            if (burst) {
-                __syncthreads();                                            // B2: their answers are in LDS
-                sx.min_tris = A.slice_min_tris;
-            }
-            phases.trace_done(sx.probe(), burst, SLICES > 1, burst_plog, in_root);
-            burst_done = burst; burst_lanes = burst_mask; burst_plog_done = burst_plog; burst_part0 = burst_my_part;
-            burst_nl_done = burst_nl;
+        phases.trace_begins();
+        // shadow rays of scenes without transmissive materials only ask "is the closest hit nearer than the light":
+        // they may stop at the first hit that says yes (trace(), `exit_t`; A.shadow_exit is set by the host).
+        const float exit_t = (A.shadow_exit && pend == PEND_SHADOW) ? shadow_max_t : -1.0f;
+        // ray class for the bundle culling: shadow rays by light, everything else by depth (camera rays = 0)
+        // (shadow rays end in their light: the lines of a class pass through that point, the "apex" of a pencil bundle)
+        uint32_t cls = (uint32_t)depth;
+        V3 apex = black;
+        if (pend == PEND_CHILD_BG) { cls |= kClsHasApex; apex = mirror_apex; }      // camera rays and chains of reflections
+        if (pend == PEND_SHADOW) {
+            const DevLight *L = A.lights + light_k;
+            cls = kClsHasApex | (0x100u + (uint32_t)light_k + 0x40u * (uint32_t)depth);   // (different depths: different surfaces)
+            apex = mk(L->pos[0], L->pos[1], L->pos[2]);
         }
+        if (burst) {
+            const uint32_t lane = fresh_lane();
+            group_sh->ray_o[lane] = make_float4(P.x, P.y, P.z, ncos.x);
+            group_sh->ray_d[lane] = make_float4(ncos.y, ncos.z, reach, 0.f);
+            if (lane == 0u) {
+                group_sh->pass_mask = burst_mask; group_sh->first = burst_k; group_sh->count = burst_plog | ((burst_nl << burst_plog) << 8);
+                group_sh->pad[0] = 1u;                                  // next job to hand out (job 0 is traced right here)
+                // (an opaque constant: folded, it becomes one lane of a three-register tuple {first, count, kind} that is
+                // set up in the kernel's prologue and spilled to scratch until it is needed here)
+                uint32_t extra = GROUP_EXTRA;
+                asm volatile("" : "+v"(extra));
+                group_sh->kind = extra;
+            }
+            __syncthreads();                                            // B1: the helpers start on their lights
+            sx.min_tris = 0xFFFFFFFFu;                                  // (they are busy: the owner's own leaves stay whole)
+        }
+        cand = trace<MODE, STATS, kStage, SLICES, kRootFirst>(A.tree, lds_nodes, ray, cull, in_root & !elsewhere, st, sx, kAutoMinLanes, exit_t, cls, apex);   // (in_root: no unlit lane)
+        phases.trace_returned();
+        if (burst) {
+            __syncthreads();                                            // B2: their answers are in LDS
+            sx.min_tris = A.slice_min_tris;
+        }
+        phases.trace_done(sx.probe(), burst, SLICES > 1, burst_plog, in_root);
+        burst_done = burst; burst_lanes = burst_mask; burst_plog_done = burst_plog; burst_part0 = burst_my_part;
+        burst_nl_done = burst_nl;
 
         float *const unpark = &park_lds[park_slot][0][fresh_lane()];
         pixel_sum = mk(unpark[0 * 64], unpark[1 * 64], unpark[2 * 64]);
@@ -731,80 +712,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const uint32_t total = nrays_wave;
     if (STATS && writer) flush_stats(st, 0u, A.counters);
     // one no-return atomic per pixel block, spread over 64 words (a single word saturates near 88 atomics/us)
-    if (lane == 0u && writer) atomicAdd(A.counters + 8 + (gwave % (uint32_t)kRayCounterShards), (unsigned long long)total);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Two-pass frames, first pass: camera rays only.  One workgroup per 8x8 pixel block (owner wave + helpers, as in
-// k_render).  Stores each pixel's candidate, writes the background for blocks no ray hits, and files every other
-// block under a log-scale estimate of the work its shading will need, so that the second pass can start the most
-// expensive blocks first (longest-processing-time-first: the frame no longer ends waiting for a few heavy blocks
-// that happened to be dispatched last).
-template <bool STATS, int SLICES>
-__global__ __launch_bounds__(64 * SLICES, 8) void k_primary(RenderArgs A) {
-    __shared__ GroupStorage<(SLICES > 1 ? SLICES : 1)> group_st;
-    GroupShared *const group_sh = group_st.get();
-    const uint32_t slice = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((threadIdx.x >> 6) + blockIdx.x) % (uint32_t)SLICES));
-    if (slice != 0u) { group_helper_loop<SLICES>(A.tree, group_sh, slice); return; }
-    SliceCtx sx = {group_sh, A.slice_min_tris, 0u, true, 0u, group_sh->bundles};
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gwave = blockIdx.x;
-    // (block_map() / block_pixel() written out, as in k_render)
-    const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint32_t local_bucket = gwave / bpb, sub = gwave % bpb;
-    const uint32_t bucket = rank_bucket((uint32_t)A.rank, local_bucket, (uint32_t)A.world, A.skew_q);
-    const uint32_t bx = (bucket % A.tiles_x) * A.bucket, by = (bucket / A.tiles_x) * A.bucket;
-    const uint32_t lx = (sub % A.blocks_per_bucket_side) * 8u + (lane & 7u);
-    const uint32_t ly = (sub / A.blocks_per_bucket_side) * 8u + (lane >> 3);
-    const uint32_t px = bx + lx, py = by + ly;
-    const bool valid = (bucket < A.n_buckets) & (lx < A.bucket) & (ly < A.bucket) & (px < A.width) & (py < A.height);
-    const Ray ray = camera_ray(A, px, py, root_key(pcg_hash(A.seed), py * A.width + px, 0u));
-    Stats st = {0, 0, 0, 0, 0, 0};
-    const Cand c = trace<RTK_TRACE_WAVE, STATS, false, SLICES>(A.tree, nullptr, ray, true, valid, st, sx);
-    group_post_exit(group_sh);
-
-    const size_t pix = A.out_index(local_bucket, lx, ly, px, py);
-    const bool hit = valid & (c.k != kMiss);
-    const unsigned long long hit_mask = __builtin_amdgcn_ballot_w64(hit);
-    if (hit_mask == 0ull) {                                        // nothing to shade: the block is finished here
-        if (valid) {
-            float *o = A.out + pix * 3;                             // (0 + background) / 1, render.hpp:68-72 with spp == 1
-            o[0] = (0.0f + A.background[0]) / 1.0f; o[1] = (0.0f + A.background[1]) / 1.0f; o[2] = (0.0f + A.background[2]) / 1.0f;
-        }
-    } else {
-        if (valid) A.prim[pix] = make_float4(c.t, c.u, c.v, __uint_as_float(c.k));
-        // cost estimate: (trace rounds the block's shading will need) x (work of this block's primary trace)
-        int kind = -1;
-        if (hit) kind = A.materials[A.tree.shade[A.tree.tri_ids[c.k]].material].kind;
-        const bool any_diffuse = wave_any(kind == RTK_MAT_DIFFUSE), any_mirror = wave_any(kind == RTK_MAT_REFLECTIVE),
-                   any_glass = wave_any(kind == RTK_MAT_REFRACTIVE);
-        const uint32_t lights = (uint32_t)A.n_lights + (uint32_t)A.diffuse_rays * 4u;
-        uint32_t rounds = 1u;
-        if (any_diffuse) rounds += lights;
-        if (any_mirror) rounds += 1u + lights;
-        if (any_glass) rounds += 4u * (1u + lights);
-        const float cost = (float)rounds * (float)(sx.work + 16u) * (float)__popcll(hit_mask);
-        uint32_t bin = (uint32_t)(__builtin_log2f(cost) * 2.0f);
-        bin = bin > (uint32_t)(kCostBins - 1) ? (uint32_t)(kCostBins - 1) : bin;
-        if (lane == 0u) {
-            const uint32_t slot = atomicAdd(A.bin_count + bin, 1u);
-            A.bin_list[(size_t)bin * A.tile_cap + slot] = gwave;
-        }
-    }
-    const uint32_t total = wave_sum(valid ? 1u : 0u);
-    if (STATS) flush_stats(st, 0u, A.counters);
-    if (lane == 0u && total != 0u) atomicAdd(A.counters + 8 + (gwave % (uint32_t)kRayCounterShards), (unsigned long long)total);
-}
-
-// Two-pass frames, between the passes: concatenates the cost bins, most expensive first.  One workgroup per bin.
-__global__ __launch_bounds__(256) void k_tile_order(RenderArgs A) {
-    const uint32_t bin = (uint32_t)(kCostBins - 1) - blockIdx.x;
-    uint32_t offset = 0;
-    for (uint32_t b = bin + 1u; b < (uint32_t)kCostBins; ++b) offset += A.bin_count[b];
-    const uint32_t n = A.bin_count[bin];
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) A.tile_order[offset + i] = A.bin_list[(size_t)bin * A.tile_cap + i];
-    if (bin == 0u && threadIdx.x == 0u) *A.n_listed = offset + n;
+    if (lane == 0u && writer) atomicAdd(A.counters + kRayShardWord + (gwave % (uint32_t)kRayCounterShards), (unsigned long long)total);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -905,43 +813,61 @@ hipError_t launch_intersect_m(const dev::IntersectArgs &A, bool lds, size_t lds_
     // only the per-lane walk reads the node array from LDS: the wave-cooperative one fetches nodes and leaves through the scalar
     // cache (staging the array for it copied 6 KB per 256 rays for nothing)
     constexpr bool kNeedsNodes = (MODE == RTK_TRACE_LANE || MODE == RTK_TRACE_AUTO);
-    if (lds && kNeedsNodes) hipLaunchKernelGGL((dev::k_intersect<MODE, STATS, true>), dim3(blocks), dim3(256), lds_bytes, s, A);
-    else hipLaunchKernelGGL((dev::k_intersect<MODE, STATS, false>), dim3(blocks), dim3(256), 0, s, A);
+    if constexpr (kNeedsNodes) {
+        if (lds) { hipLaunchKernelGGL((dev::k_intersect<MODE, STATS, true>), dim3(blocks), dim3(256), lds_bytes, s, A); return hipGetLastError(); }
+    }
+    hipLaunchKernelGGL((dev::k_intersect<MODE, STATS, false>), dim3(blocks), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 
-template <int MODE, bool STATS, bool FORKS, int SLICES>
+// (units, mode) -> kernel: VIEWS / REGIONS say what a unit of the launch is (a frame's pixel block; a (view, block) or a
+// (rectangle, block) pair of the one-launch calls).  The LDS_NODES build exists only for the modes that walk per lane.
+template <int MODE, bool STATS, bool FORKS, int SLICES, bool VIEWS = false, bool REGIONS = false>
 hipError_t launch_render_m(const dev::RenderArgs &A, unsigned blocks, bool lds, size_t lds_bytes, hipStream_t s) {
     const unsigned threads = SLICES > 1 ? 64u * SLICES : 256u;
     constexpr bool kNeedsNodes = (MODE == RTK_TRACE_LANE || MODE == RTK_TRACE_AUTO);
-    if (lds && kNeedsNodes) hipLaunchKernelGGL((dev::k_render<MODE, STATS, FORKS, true, SLICES>), dim3(blocks), dim3(threads), lds_bytes, s, A);
-    else hipLaunchKernelGGL((dev::k_render<MODE, STATS, FORKS, false, SLICES>), dim3(blocks), dim3(threads), 0, s, A);
+    if constexpr (kNeedsNodes) {
+        if (lds) { hipLaunchKernelGGL((dev::k_render<MODE, STATS, FORKS, true, SLICES, VIEWS, REGIONS>), dim3(blocks), dim3(threads), lds_bytes, s, A); return hipGetLastError(); }
+    }
+    hipLaunchKernelGGL((dev::k_render<MODE, STATS, FORKS, false, SLICES, VIEWS, REGIONS>), dim3(blocks), dim3(threads), 0, s, A);
     return hipGetLastError();
 }
 
-// rtk_render_views as one launch: the GROUP modes without per-ray statistics
-template <int SLICES>
-hipError_t launch_render_views_m(const dev::RenderArgs &A, unsigned blocks, bool forks, hipStream_t s) {
-    if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, true, false, SLICES, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
-    else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, SLICES, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
-    return hipGetLastError();
-}
-
-// rtk_render_regions as one launch: the same set
-template <int SLICES>
-hipError_t launch_render_regions_m(const dev::RenderArgs &A, unsigned blocks, bool forks, hipStream_t s) {
-    if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, true, false, SLICES, false, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
-    else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, SLICES, false, false, true>), dim3(blocks), dim3(64u * SLICES), 0, s, A);
-    return hipGetLastError();
-}
-
-template <int MODE, int SLICES>
+// the builds of one (mode, waves per unit): per-ray statistics exist for a frame's own pixel blocks only
+template <int MODE, int SLICES, bool VIEWS, bool REGIONS>
 hipError_t launch_render_mode(const dev::RenderArgs &A, unsigned blocks, bool stats, bool forks, bool lds, size_t lds_bytes,
                               hipStream_t s) {
-    if (stats) return forks ? launch_render_m<MODE, true, true, SLICES>(A, blocks, lds, lds_bytes, s)
-                            : launch_render_m<MODE, true, false, SLICES>(A, blocks, lds, lds_bytes, s);
-    return forks ? launch_render_m<MODE, false, true, SLICES>(A, blocks, lds, lds_bytes, s)
-                 : launch_render_m<MODE, false, false, SLICES>(A, blocks, lds, lds_bytes, s);
+    if constexpr (!VIEWS && !REGIONS) {
+        if (stats) return forks ? launch_render_m<MODE, true, true, SLICES>(A, blocks, lds, lds_bytes, s)
+                                : launch_render_m<MODE, true, false, SLICES>(A, blocks, lds, lds_bytes, s);
+    }
+    return forks ? launch_render_m<MODE, false, true, SLICES, VIEWS, REGIONS>(A, blocks, lds, lds_bytes, s)
+                 : launch_render_m<MODE, false, false, SLICES, VIEWS, REGIONS>(A, blocks, lds, lds_bytes, s);
+}
+
+// The one table (units, mode) -> kernel and grid, for a frame and for rtk_render_views / rtk_render_regions as one launch (the GROUP
+// modes, no statistics: launch_render has refused the rest).  `listed`: the workgroups of GROUP4's list, when the host knows.
+template <bool VIEWS, bool REGIONS>
+hipError_t launch_render_units(const dev::RenderArgs &A, int mode, unsigned units, unsigned listed, bool stats, bool forks, hipStream_t s) {
+    const size_t lds_bytes = (size_t)A.tree.n_nodes * sizeof(DevNode);
+    const bool lds = lds_bytes <= kMaxNodeLdsBytes;
+    switch (mode) {
+        // (with a workgroup list the kernel's workgroups beyond the list return at once; launched all the same they are ~100,000
+        // waves of a config-2 frame that only start and stop)
+        case RTK_TRACE_GROUP4: return launch_render_mode<RTK_TRACE_WAVE, 4, VIEWS, REGIONS>(A, listed, stats, forks, lds, lds_bytes, s);
+        case RTK_TRACE_GROUP8: return launch_render_mode<RTK_TRACE_WAVE, 8, VIEWS, REGIONS>(A, units, stats, forks, lds, lds_bytes, s);
+        case RTK_TRACE_GROUP16: return launch_render_mode<RTK_TRACE_WAVE, 16, VIEWS, REGIONS>(A, units, stats, forks, lds, lds_bytes, s);
+        default: break;
+    }
+    if constexpr (VIEWS || REGIONS) return hipErrorInvalidValue;
+    else {
+        const unsigned packed = (units + 3u) / 4u;                          // 4 pixel blocks per workgroup
+        switch (mode) {
+            case RTK_TRACE_LANE: return launch_render_mode<RTK_TRACE_LANE, 1, false, false>(A, packed, stats, forks, lds, lds_bytes, s);
+            case RTK_TRACE_WAVE: return launch_render_mode<RTK_TRACE_WAVE, 1, false, false>(A, packed, stats, forks, lds, lds_bytes, s);
+            default: return launch_render_mode<RTK_TRACE_AUTO, 1, false, false>(A, packed, stats, forks, lds, lds_bytes, s);
+        }
+    }
 }
 
 }  // namespace
@@ -967,46 +893,25 @@ hipError_t launch_render(const dev::RenderArgs &A, int mode, bool stats, bool fo
     hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, 4>), dim3(A.n_units), dim3(256), 0, s, A);
     return hipGetLastError();
 #else
+    // how many units the launch has, and whether they are what the arguments say they are: whoever did not make them consistent
+    // gets an error, not a kernel that indexes by them
     if (A.regions != nullptr) {
-        // (rectangle, block) units: the entries say how many there are; a launch that is not made of them gets an error
+        // (rectangle, block) units: the entries say how many there are
         if (stats || A.views != nullptr || A.n_regions == 0u || A.n_units == 0u || A.n_units > 0x7FFFFFFFu || A.world > 1) return hipErrorInvalidValue;
         const unsigned listed = (n_workgroups != 0u && n_workgroups < A.n_units) ? n_workgroups : A.n_units;
-        switch (mode) {
-            case RTK_TRACE_GROUP4: return launch_render_regions_m<4>(A, listed, forks, s);
-            case RTK_TRACE_GROUP8: return launch_render_regions_m<8>(A, A.n_units, forks, s);
-            case RTK_TRACE_GROUP16: return launch_render_regions_m<16>(A, A.n_units, forks, s);
-            default: return hipErrorInvalidValue;
-        }
+        return launch_render_units<false, true>(A, mode, A.n_units, listed, false, forks, s);
     }
-    const size_t lds_bytes = (size_t)A.tree.n_nodes * sizeof(DevNode);
-    const bool lds = lds_bytes <= kMaxNodeLdsBytes;
     const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
     const uint64_t waves = (uint64_t)A.buckets_per_rank * bpb * (A.views != nullptr ? A.n_views : 1u);   // one per 8x8 pixel block (of every view)
     if (waves == 0) return hipSuccess;
     if (waves > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const unsigned listed = (n_workgroups != 0u && n_workgroups < waves) ? n_workgroups : (unsigned)waves;
     if (A.views != nullptr) {
-        // (view, block) units: the caller made them consistent; whoever did not gets an error, not a kernel that indexes by them
+        // (view, block) units
         if (stats || (uint64_t)A.units_per_view * A.n_views != waves || A.n_units != waves) return hipErrorInvalidValue;
-        const unsigned listed = (n_workgroups != 0u && n_workgroups < waves) ? n_workgroups : (unsigned)waves;
-        switch (mode) {
-            case RTK_TRACE_GROUP4: return launch_render_views_m<4>(A, listed, forks, s);
-            case RTK_TRACE_GROUP8: return launch_render_views_m<8>(A, (unsigned)waves, forks, s);
-            case RTK_TRACE_GROUP16: return launch_render_views_m<16>(A, (unsigned)waves, forks, s);
-            default: return hipErrorInvalidValue;
-        }
+        return launch_render_units<true, false>(A, mode, (unsigned)waves, listed, false, forks, s);
     }
-    const unsigned packed = (unsigned)((waves + 3) / 4);                  // 4 pixel blocks per workgroup
-    switch (mode) {
-        case RTK_TRACE_LANE: return launch_render_mode<RTK_TRACE_LANE, 1>(A, packed, stats, forks, lds, lds_bytes, s);
-        case RTK_TRACE_WAVE: return launch_render_mode<RTK_TRACE_WAVE, 1>(A, packed, stats, forks, lds, lds_bytes, s);
-        // (with a workgroup list the kernel's workgroups beyond the list return at once; launched all the same they are ~100,000
-        // waves of a config-2 frame that only start and stop)
-        case RTK_TRACE_GROUP4: return launch_render_mode<RTK_TRACE_WAVE, 4>(A, (n_workgroups != 0u && n_workgroups < waves) ? n_workgroups : (unsigned)waves,
-                                                                            stats, forks, lds, lds_bytes, s);
-        case RTK_TRACE_GROUP8: return launch_render_mode<RTK_TRACE_WAVE, 8>(A, (unsigned)waves, stats, forks, lds, lds_bytes, s);
-        case RTK_TRACE_GROUP16: return launch_render_mode<RTK_TRACE_WAVE, 16>(A, (unsigned)waves, stats, forks, lds, lds_bytes, s);
-        default: return launch_render_mode<RTK_TRACE_AUTO, 1>(A, packed, stats, forks, lds, lds_bytes, s);
-    }
+    return launch_render_units<false, false>(A, mode, (unsigned)waves, listed, stats, forks, s);
 #endif
 }
 
@@ -1242,31 +1147,6 @@ hipError_t launch_order_by_cost(const uint32_t *cost, uint8_t *bins, uint32_t *o
     if (pack == 0u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dev::k_order_by_cost, dim3(1), dim3(1024), 0, s, cost, bins, order, wg_list, hdr, n, light_below, floor_below, pack);
     return hipGetLastError();
-}
-
-// Two-pass frame (spp == 1): k_primary -> k_tile_order -> primed k_render, all on one stream.
-hipError_t launch_twopass(const dev::RenderArgs &A, bool stats, bool forks, hipStream_t s) {
-    const uint32_t bpb = A.blocks_per_bucket_side * A.blocks_per_bucket_side;
-    const uint64_t tiles = (uint64_t)A.buckets_per_rank * bpb;
-    if (tiles == 0) return hipSuccess;
-    if (tiles > A.tile_cap) return hipErrorInvalidValue;
-#ifdef RTK_ONLY_LEAN_G4
-    return hipErrorNotSupported;
-#else
-    hipError_t e = hipMemsetAsync(A.bin_count, 0, (kCostBins + 1) * sizeof(uint32_t), s);      // + n_listed
-    if (e != hipSuccess) return e;
-    if (stats) hipLaunchKernelGGL((dev::k_primary<true, 4>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-    else hipLaunchKernelGGL((dev::k_primary<false, 4>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-    hipLaunchKernelGGL(dev::k_tile_order, dim3(kCostBins), dim3(256), 0, s, A);
-    if (stats) {
-        if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, true, true, false, 4, true>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, true, false, false, 4, true>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-    } else {
-        if (forks) hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, true, false, 4, true>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((dev::k_render<RTK_TRACE_WAVE, false, false, false, 4, true>), dim3((unsigned)tiles), dim3(256), 0, s, A);
-    }
-    return hipGetLastError();
-#endif
 }
 
 hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_rays, hipStream_t s) {

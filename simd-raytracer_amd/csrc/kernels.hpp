@@ -4,15 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include "rtk_internal.hpp"
+#include "counters.hpp"
 
 namespace rtk {
 
 constexpr int kMaxRayDepth = 16;                 // frame-stack capacity of the render kernel
-constexpr int kRayCounterShards = 64;              // k_render spreads its per-wave ray-count atomics over this many words
-constexpr int kCriticalWord = 8 + kRayCounterShards;   // [kRayCounterShards] longest pixel block of the frame in s_memrealtime ticks (10 ns), sharded
 constexpr unsigned long long kCriticalMinTicks = 1000;   // blocks shorter than 10 us do not report (one atomic per block would serialise the frame)
-constexpr int kCounterWords = 8 + 2 * kRayCounterShards;
-constexpr int kCostBins = 64;                      // two-pass frames: log-scale cost bins for longest-first scheduling
 constexpr uint32_t kSliceMinTrisDefault = 33;    // GROUP modes: leaves of at least two 64-triangle chunks are cut across the waves
 constexpr size_t kMaxNodeLdsBytes = 48 * 1024;   // node arrays up to this size are staged in LDS (1536 nodes)
 
@@ -84,13 +81,10 @@ struct RenderArgs {
     int compact;                      // 1: out is [buckets_per_rank][bucket][bucket][3]; 0: out is [h][w][3]
     float *out;
     unsigned long long *counters;
-    // two-pass frames (RTK_TRACE_TWOPASS): k_primary fills these, k_tile_order sorts, the primed k_render consumes
-    float4 *prim;                     // [output pixels] primary-ray candidate t,u,v,k
-    uint32_t *bin_count;              // [kCostBins] pixel blocks per cost bin
-    uint32_t *bin_list;               // [kCostBins][tile_cap] pixel-block ids per bin
-    uint32_t *tile_order;             // [tile_cap] pixel blocks with work, most expensive first
-    uint32_t *n_listed;               // number of entries in tile_order
-    uint32_t tile_cap;
+    // Never read or written.  It keeps the fields below at the kernel-argument offsets the kernels were tuned at: with them 48 bytes
+    // lower the compiler schedules the scalar loads of the arguments differently, and 17 k_render builds (the benchmark's among them)
+    // move by 1 to 3 instructions.  With the pad every kernel's instruction stream is the one it had before the fields here went.
+    unsigned long long keep_offsets_[6];
     const uint32_t *only_if;          // non-null: the kernel does nothing unless this word is non-zero (overflow fallback)
     // frame-to-frame scheduling feedback (api_frame.hip render_megakernel): every pixel block reports what it cost; the next
     // frame of the same shape starts its blocks most-expensive-first (results do not depend on the order)
@@ -149,7 +143,6 @@ hipError_t launch_block_prior(const dev::RenderArgs &A, uint8_t *cls, uint32_t *
 // a call made of several frames (the views of a fallback rtk_render_views, the launches of a chunked one): acc[] += cur[] for the
 // counts, max for the critical-path words; both [kCounterWords]
 hipError_t launch_counters_fold(const unsigned long long *cur, unsigned long long *acc, hipStream_t s);
-hipError_t launch_twopass(const dev::RenderArgs &A, bool stats, bool forks, hipStream_t s);
 hipError_t launch_assemble(const dev::AssembleArgs &A, hipStream_t s);
 hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_rays, hipStream_t s);
 hipError_t launch_to_rgb8(const float *d_rgb, size_t n, uint8_t *d_out, hipStream_t s);

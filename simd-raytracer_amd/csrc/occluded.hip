@@ -70,8 +70,10 @@ hipError_t launch_occluded_m(const dev::OccludedArgs &A, bool lds, size_t lds_by
     if (blocks == 0) return hipSuccess;
     // only the per-lane walk reads the node array from LDS (launch_intersect_m)
     constexpr bool kNeedsNodes = (MODE == RTK_TRACE_LANE || MODE == RTK_TRACE_AUTO);
-    if (lds && kNeedsNodes) hipLaunchKernelGGL((dev::k_occluded<MODE, true>), dim3(blocks), dim3(256), lds_bytes, s, A);
-    else hipLaunchKernelGGL((dev::k_occluded<MODE, false>), dim3(blocks), dim3(256), 0, s, A);
+    if constexpr (kNeedsNodes) {
+        if (lds) { hipLaunchKernelGGL((dev::k_occluded<MODE, true>), dim3(blocks), dim3(256), lds_bytes, s, A); return hipGetLastError(); }
+    }
+    hipLaunchKernelGGL((dev::k_occluded<MODE, false>), dim3(blocks), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 

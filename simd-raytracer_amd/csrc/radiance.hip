@@ -34,10 +34,10 @@ struct RadFrame {
 __global__ __launch_bounds__(256) void k_radiance_fold(const unsigned long long *lane_counters, unsigned long long *total,
                                                         const uint32_t *overflow) {
     if (threadIdx.x != 0u) return;
-    if (*overflow != 0u) { atomicAdd(total + 1, 1ull); return; }           // the fallback counts the chunk from scratch
-    unsigned long long rays = lane_counters[0];
-    for (int i = 0; i < kRayCounterShards; ++i) rays += lane_counters[8 + i];
-    atomicAdd(total, rays);
+    if (*overflow != 0u) { atomicAdd(total + kRadianceRedone, 1ull); return; }   // the fallback counts the chunk from scratch
+    unsigned long long rays = lane_counters[kWordRays];
+    for (int i = 0; i < kRayCounterShards; ++i) rays += lane_counters[kRayShardWord + i];
+    atomicAdd(total + kRadianceRays, rays);
 }
 
 template <bool LDS_NODES>
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_radiance_fallback(StreamArgs S, unsigne
         o[0] = 0.0f + result.x; o[1] = 0.0f + result.y; o[2] = 0.0f + result.z;
     }
     const uint32_t sum = wave_sum(nrays);
-    if ((threadIdx.x & 63u) == 0u && sum != 0u) atomicAdd(total, (unsigned long long)sum);
+    if ((threadIdx.x & 63u) == 0u && sum != 0u) atomicAdd(total + kRadianceRays, (unsigned long long)sum);
 }
 
 }  // namespace dev

@@ -22,17 +22,16 @@ __device__ __forceinline__ void stage_nodes(const DevNode *g_nodes, uint32_t n_n
 
 // per-ray statistics of a wave (STATS kernels).  The rays themselves are counted by the callers, in sharded words.
 __device__ __forceinline__ void flush_stats(const Stats &st, uint32_t rays, unsigned long long *counters) {
-    // counters: rays, primary, hits, nodes, boxpass, leaves, tris, packets16 (rtk_counters order)
     const uint32_t r = wave_sum(rays), h = wave_sum(st.hits), nd = wave_sum(st.nodes), bp = wave_sum(st.boxpass),
                    lv = wave_sum(st.leaves), tr = wave_sum(st.tris), pk = wave_sum(st.packets16);
     if ((threadIdx.x & 63u) == 0u) {
-        atomicAdd(counters + 0, (unsigned long long)r);
-        atomicAdd(counters + 2, (unsigned long long)h);
-        atomicAdd(counters + 3, (unsigned long long)nd);
-        atomicAdd(counters + 4, (unsigned long long)bp);
-        atomicAdd(counters + 5, (unsigned long long)lv);
-        atomicAdd(counters + 6, (unsigned long long)tr);
-        atomicAdd(counters + 7, (unsigned long long)pk);
+        atomicAdd(counters + kWordRays, (unsigned long long)r);
+        atomicAdd(counters + kWordHits, (unsigned long long)h);
+        atomicAdd(counters + kWordNodes, (unsigned long long)nd);
+        atomicAdd(counters + kWordBoxpass, (unsigned long long)bp);
+        atomicAdd(counters + kWordLeaves, (unsigned long long)lv);
+        atomicAdd(counters + kWordTris, (unsigned long long)tr);
+        atomicAdd(counters + kWordPackets16, (unsigned long long)pk);
     }
 }
 

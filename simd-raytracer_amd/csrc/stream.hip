@@ -128,7 +128,7 @@ __device__ __forceinline__ void add_rays(const StreamArgs &S, const Stats &st, c
     const uint32_t total = wave_sum(rays);
     unsigned long long *c = S.r.counters;
     if (stats) flush_stats(st, 0u, c);
-    if (__lane_id() == 0u && total != 0u) atomicAdd(c + 8 + (shard % (uint32_t)kRayCounterShards), (unsigned long long)total);
+    if (__lane_id() == 0u && total != 0u) atomicAdd(c + kRayShardWord + (shard % (uint32_t)kRayCounterShards), (unsigned long long)total);
 }
 
 __device__ __forceinline__ uint32_t grid_cell(const StreamArgs &S, const V3 p) {

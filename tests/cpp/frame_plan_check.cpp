@@ -248,6 +248,11 @@ void order_capacity() {
     CHECK(OrderState::frame_mode(RTK_TRACE_AUTO, 0, 0) == RTK_TRACE_GROUP4, "knob 0: never eight waves");
     for (int m : {RTK_TRACE_GROUP4, RTK_TRACE_GROUP8, RTK_TRACE_GROUP16, RTK_TRACE_WAVE, RTK_TRACE_LANE})
         CHECK(OrderState::frame_mode(m, 1, below) == m && OrderState::frame_mode(m, below + 1, below) == m, "mode %d is kept", m);
+    // the retired two-pass engine's mode: GROUP4's frames whatever the block count (never eight waves, never itself)
+    for (size_t units : {size_t(0), size_t(1), below - 1, below, below + 1})
+        CHECK(OrderState::frame_mode(RTK_TRACE_TWOPASS, units, below) == RTK_TRACE_GROUP4, "TWOPASS at %zu units", units);
+    CHECK(OrderState::frame_mode(RTK_TRACE_TWOPASS, 1, 0) == RTK_TRACE_GROUP4, "TWOPASS, knob 0");
+    CHECK(OrderState::frame_mode(RTK_TRACE_STREAM, 1, below) == RTK_TRACE_STREAM, "STREAM is kept");
     if (!g_failed) std::printf("capacity ok\n");
 }
 

@@ -376,8 +376,9 @@ int rtk_accel_update_vertices_device(rtk_accel *accel, const float *d_vertices /
  * every RTK_TRACE_* engine and its counters' `rays`.  RTK_TRAVERSAL_FAST accels included, with their leaf orders and the
  * opaque-only occlusion tree.  rtk_hit.tri is the global index in the new concatenated order.  A later
  * rtk_accel_update_vertices moves the vertices of the new topology.
- * Fixed by the call: the number of meshes, every mesh's vertex count, every mesh's material, the per-vertex uvs, materials,
- * textures, lights, camera and rtk_accel_params.  Every mesh's triangle count is free: 0, smaller, or larger than anything
+ * Fixed by the call: the number of meshes, every mesh's vertex count, every mesh's material, materials, textures, lights, camera and
+ * rtk_accel_params (the per-triangle uvs are gathered from the per-vertex uvs as they are NOW: rtk_accel_set_uvs, "textures and
+ * uvs of a live accel" below).  Every mesh's triangle count is free: 0, smaller, or larger than anything
  * before.  Vertices no triangle uses are legal and cost a few bytes each: a caller whose vertex count varies builds the scene
  * with a POOL of vertices per mesh, as large as it will ever need, and indexes into what it uses of it.
  * The topology tables -- vertex ids, the vertex -> (triangle, corner) lists the smooth normals are summed in, mesh / material and
@@ -553,8 +554,8 @@ int rtk_accel_set_lights_device(rtk_accel *accel, const rtk_light *d_lights /* D
 int rtk_accel_get_materials(const rtk_accel *accel, rtk_material *out /* [n_materials] */);
 /* n must equal the scene's n_materials: the meshes' material indices are fixed (rtk_accel_update_geometry).  Validation is
  * rtk_scene_create's: kind in [RTK_MAT_DIFFUSE, RTK_MAT_TEXTURE]; for RTK_MAT_TEXTURE 0 <= texture < n_textures, for every other
- * kind texture is stored as -1; `reserved` is ignored and stored as 0.  The textures themselves are not touched: a scene built
- * without textures cannot gain a texture material.
+ * kind texture is stored as -1; `reserved` is ignored and stored as 0.  n_textures is the LIVE count: the textures themselves are
+ * replaced through rtk_accel_set_textures ("textures and uvs of a live accel", below).
  * On an accel that has never been on a device the call only stores and needs no GPU.  On a resident accel it synchronises the
  * device at entry and writes the table.  What the launch paths derive from "some material is refractive" (early shadow exit, the
  * unlit-shadow skip, the lean / general kernel choice, the streaming plan, the one-launch path of rtk_render_views) follows; the
@@ -573,6 +574,62 @@ int rtk_accel_set_materials(rtk_accel *accel, const rtk_material *materials /* h
  * keep the background they were launched with.  NULL accel or rgb -> RTK_ERR_INVALID. */
 int rtk_accel_get_background(const rtk_accel *accel, float rgb[3]);
 int rtk_accel_set_background(rtk_accel *accel, const float rgb[3]);
+
+/* ---- textures and uvs of a live accel ----
+ * scene::textures (scene/scene.hpp:18) and the meshes' uvs are plain mutable members in the reference as well.  The contract of
+ * every setter below is that of the section above: after RTK_OK everything observable through the accel is, bit for bit and with
+ * the same `rays`, what a fresh rtk_accel_build gives for a scene that differs only in the replaced part (same params, same
+ * environment knobs): frames through every RTK_TRACE_* engine, sharded frames, rtk_render_views*, rtk_render_regions*,
+ * rtk_accel_radiance* and the counters.  The tree, rtk_accel_tree_dump, rtk_accel_intersect*, rtk_accel_occluded* and
+ * rtk_camera_rays* depend on none of it and do not change.  The state survives rtk_accel_update_vertices / _update_geometry (which
+ * gathers the per-triangle uvs from the CURRENT per-vertex uvs), rtk_accel_set_camera / _lights / _materials / _background, in any
+ * order.  A refused call leaves the accel exactly as it was and usable.  None of the calls is stream-capturable.
+ * Residency and ordering are those of rtk_accel_set_lights[_device]: on an accel that has never been on a device the host setters
+ * only store, need no GPU and never return RTK_ERR_NO_DEVICE; on a resident accel they SYNCHRONISE THE DEVICE AT ENTRY, build into
+ * spare buffers where something has to move, and swap at the end.  The _device variants put the accel on the device first (no
+ * usable device -> RTK_ERR_NO_DEVICE), synchronise the device at entry, work on `hip_stream` and record the event later work on any
+ * stream waits for; after entry they do not block the host, except to allocate when something outgrows its buffer (and, for the
+ * uvs of an accel no update has touched yet, once to put the build-time vertex ids on the device).
+ * The cost-feedback launch order and RTK_TRACE_AUTO's engine verdict are KEPT by all of them: a texture moves no silhouette and
+ * forks no ray.
+ * Errors, in this order: a NULL accel or required pointer, n < 0, a texture index outside the live table -> RTK_ERR_INVALID; what
+ * the call validates (below), rtk_accel_set_texture_* on a texture that is not a bitmap -> RTK_ERR_INVALID; then (_device variants)
+ * RTK_ERR_NO_DEVICE; RTK_ERR_HIP only from the runtime. */
+typedef struct { int32_t kind; float color_a[3]; float color_b[3]; float param; int32_t width, height; } rtk_texture; /* 40 bytes */
+
+/* *n = the number of textures; with `out`, the first min(cap, *n) of them.  A bitmap reads back with color_a, color_b and param
+ * 0 and its size; every other kind with width = height = 0. */
+int rtk_accel_get_textures(const rtk_accel *accel, rtk_texture *out /* may be NULL */, int32_t cap, int32_t *n);
+/* *n_bytes = width * height * 3 of texture `texture` (0 for a texture that is not a bitmap); with `out`, the first
+ * min(cap, *n_bytes) bytes, rows top-down.  After a device-side replacement they are fetched from the device, which synchronises it. */
+int rtk_accel_get_texture_pixels(const rtk_accel *accel, int32_t texture, uint8_t *out /* may be NULL */, size_t cap, size_t *n_bytes);
+/* Replaces the whole table; n is free: 0, fewer, or more than before, and an accel built without textures can gain them.
+ * Validation is rtk_scene_create's: kind in [RTK_TEX_ALBEDO, RTK_TEX_BITMAP]; a bitmap needs width, height >= 1,
+ * width * height <= 2^28 and a non-NULL pixels[i] (host [height][width][3]), and the texel bytes of all bitmaps together must fit
+ * an int32 offset.  Colours and param are taken as they are (a zero square_size, a NaN or an infinity is the caller's business).
+ * While a texture material of the live table refers to a texture >= n the call is refused: change the materials first.
+ * rtk_accel_set_materials validates against the live count. */
+int rtk_accel_set_textures(rtk_accel *accel, const rtk_texture *textures, int32_t n,
+                           const uint8_t *const *pixels /* [n]; entry i read only for RTK_TEX_BITMAP; may be NULL when no texture is a bitmap */);
+/* Replace the texels of ONE texture, which must be a bitmap; the size may differ from before.  On a resident accel every bitmap
+ * has a slot in one texel buffer: a replacement that fits its slot is written in place and allocates nothing (the device was
+ * synchronised at entry, so no launch enqueued earlier still reads it); one that outgrows it gets a new slot with head room at the
+ * buffer's end, or, when the buffer is full, a larger buffer into which the other bitmaps are copied on the device. */
+int rtk_accel_set_texture_pixels(rtk_accel *accel, int32_t texture, int32_t width, int32_t height, const uint8_t *rgb /* host [h][w][3] */);
+int rtk_accel_set_texture_pixels_device(rtk_accel *accel, int32_t texture, int32_t width, int32_t height, const uint8_t *d_rgb, void *hip_stream);
+/* Render to texture: the texels become what rtk_frame_to_rgb8_device makes of the width * height * 3 floats,
+ * uint8(255.999 * clamp(x, 0, 1)) with the product in double (ppm.hpp:17-19), rows top-down as a frame's and stbi_load's are;
+ * one kernel reads the floats and writes the bytes into the texture's slot.  With rtk_render_views_device this shows a view on a
+ * quad of the next frame without leaving the device. */
+int rtk_accel_set_texture_frame_device(rtk_accel *accel, int32_t texture, int32_t width, int32_t height,
+                                       const float *d_rgb /* device [h][w][3], a finished frame */, void *hip_stream);
+/* Dense per-vertex uvs in the layout of `vertices`: n_vertices rows, all meshes concatenated.  A mesh without uvs has zeros in
+ * the reference (loader.hpp:199-207), so the equivalent scene is "every mesh has these uvs", and on a fresh accel the getter
+ * returns the scene's uvs with zeros for such meshes.  Values are taken as they are.  On an accel without textures the setters
+ * only store; the per-triangle uvs are made when textures appear (csrc/topology.hip, k_tri_uv). */
+int rtk_accel_get_uvs(const rtk_accel *accel, float *uvs /* [n_vertices][2] */);
+int rtk_accel_set_uvs(rtk_accel *accel, const float *uvs /* host [n_vertices][2] */);
+int rtk_accel_set_uvs_device(rtk_accel *accel, const float *d_uvs /* device, 4-byte aligned */, void *hip_stream);
 
 /* ---- image out: replaces write_ppm (io/image/ppm.hpp:7-25) ---- */
 /* The quantisation of write_ppm on the device: out[i] = uint8(255.999 * clamp(rgb[i], 0, 1)) (ppm.hpp:17-19, the product in

@@ -54,6 +54,9 @@ ABI_SYMBOLS = [
     "rtk_render_regions", "rtk_render_regions_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
+    "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
+    "rtk_accel_set_texture_pixels_device", "rtk_accel_set_texture_frame_device",
+    "rtk_accel_get_uvs", "rtk_accel_set_uvs", "rtk_accel_set_uvs_device",
     "rtk_frame_to_rgb8_device", "rtk_format_ppm_rgb8", "rtk_write_ppm", "rtk_format_ppm",
 ]
 
@@ -139,7 +142,9 @@ RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,))])
 LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("intensity", "<f4")])                     # rtk.h rtk_light
 MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("smooth", "<i4"), ("albedo", "<f4", (3,)), ("ior", "<f4"), ("texture", "<i4"),
                            ("reserved", "<i4")])                                             # rtk.h rtk_material
-assert LIGHT_DTYPE.itemsize == 16 and MATERIAL_DTYPE.itemsize == 32
+TEXTURE_DTYPE = np.dtype([("kind", "<i4"), ("color_a", "<f4", (3,)), ("color_b", "<f4", (3,)), ("param", "<f4"), ("width", "<i4"),
+                          ("height", "<i4")])                                                # rtk.h rtk_texture
+assert LIGHT_DTYPE.itemsize == 16 and MATERIAL_DTYPE.itemsize == 32 and TEXTURE_DTYPE.itemsize == 40
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), ("mesh", "<u4"), ("normal", "<f4", (3,))])
 assert RAY_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
 
@@ -194,6 +199,15 @@ _L.rtk_accel_get_materials.argtypes = [_vp, _vp]
 _L.rtk_accel_set_materials.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_get_background.argtypes = [_vp, _vp]
 _L.rtk_accel_set_background.argtypes = [_vp, _vp]
+_L.rtk_accel_get_textures.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+_L.rtk_accel_get_texture_pixels.argtypes = [_vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
+_L.rtk_accel_set_textures.argtypes = [_vp, _vp, C.c_int32, _vp]
+_L.rtk_accel_set_texture_pixels.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]
+_L.rtk_accel_set_texture_pixels_device.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_L.rtk_accel_set_texture_frame_device.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+_L.rtk_accel_get_uvs.argtypes = [_vp, _vp]
+_L.rtk_accel_set_uvs.argtypes = [_vp, _vp]
+_L.rtk_accel_set_uvs_device.argtypes = [_vp, _vp, _vp]
 _L.rtk_frame_to_rgb8_device.argtypes = [_vp, C.c_size_t, _vp, _vp]
 _L.rtk_format_ppm_rgb8.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
 _L.rtk_write_ppm.argtypes = [_vp, C.c_int32, C.c_int32, C.c_char_p]
@@ -737,6 +751,89 @@ class KdTreeSimdAccel:
             raise ValueError("the background has 3 floats")
         rgb = np.ascontiguousarray(rgb)
         _check(_L.rtk_accel_set_background(self._h, rgb.ctypes.data))
+
+    # ---- textures and uvs of a live accel (rtk.h rtk_texture)
+    def textures(self) -> dict:
+        """kind [t] int32, color_a [t, 3], color_b [t, 3], param [t] float32, width [t], height [t] int32 (0 unless TEX_BITMAP)."""
+        n = C.c_int32(0)
+        _check(_L.rtk_accel_get_textures(self._h, None, 0, C.byref(n)))
+        tab = np.zeros(n.value, TEXTURE_DTYPE)
+        _check(_L.rtk_accel_get_textures(self._h, tab.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return {k: tab[k].copy() for k in TEXTURE_DTYPE.names}
+
+    def set_textures(self, kind, color_a=None, color_b=None, param=None, pixels=None) -> None:
+        """Replaces the whole texture table; the number of textures is free.  `pixels`: one entry per texture, uint8 [h, w, 3] for
+        a TEX_BITMAP and ignored (None) for every other kind.  What the values hold is judged by the library (RtkError)."""
+        kind = np.asarray(kind)
+        if kind.ndim != 1 or (kind.size and kind.dtype.kind not in "iub"):
+            raise ValueError("kind must be a list of integers, one per texture")
+        t = kind.shape[0]
+        color_a = np.zeros((t, 3), np.float32) if color_a is None else np.asarray(color_a, np.float32)
+        color_b = np.zeros((t, 3), np.float32) if color_b is None else np.asarray(color_b, np.float32)
+        param = np.zeros(t, np.float32) if param is None else np.asarray(param, np.float32)
+        if color_a.shape != (t, 3) or color_b.shape != (t, 3) or param.shape != (t,):
+            raise ValueError(f"color_a and color_b must have shape ({t}, 3) and param ({t},)")
+        pixels = [None] * t if pixels is None else list(pixels)
+        if len(pixels) != t:
+            raise ValueError("pixels must have one entry per texture")
+        tab = np.zeros(t, TEXTURE_DTYPE)
+        tab["kind"], tab["color_a"], tab["color_b"], tab["param"] = kind, color_a, color_b, param
+        keep, ptrs = [], (_vp * max(1, t))()
+        for i in range(t):
+            if pixels[i] is None or kind[i] != TEX_BITMAP:
+                continue
+            px = np.ascontiguousarray(pixels[i], np.uint8)
+            if px.ndim != 3 or px.shape[2] != 3:
+                raise ValueError("the texels of a bitmap are uint8 [height, width, 3]")
+            tab["height"][i], tab["width"][i] = px.shape[0], px.shape[1]
+            keep.append(px)
+            ptrs[i] = px.ctypes.data
+        _check(_L.rtk_accel_set_textures(self._h, tab.ctypes.data if t else None, t, ptrs))
+
+    def texture_pixels(self, texture: int) -> np.ndarray:
+        """uint8 [h, w, 3] of one bitmap texture (an empty array for another kind), fetched from the device after a device-side
+        replacement."""
+        n = C.c_size_t(0)
+        _check(_L.rtk_accel_get_texture_pixels(self._h, texture, None, 0, C.byref(n)))
+        tex = self.textures()
+        out = np.zeros((int(tex["height"][texture]), int(tex["width"][texture]), 3), np.uint8)
+        assert out.size == n.value
+        if out.size:
+            _check(_L.rtk_accel_get_texture_pixels(self._h, texture, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def set_texture_pixels(self, texture: int, rgb) -> None:
+        """New texels for one bitmap texture: uint8 [h, w, 3], rows top-down; the size may differ from before."""
+        px = np.asarray(rgb)
+        if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("the texels of a bitmap are uint8 [height, width, 3]")
+        px = np.ascontiguousarray(px)
+        _check(_L.rtk_accel_set_texture_pixels(self._h, texture, px.shape[1], px.shape[0], px.ctypes.data if px.size else None))
+
+    def set_texture_pixels_device(self, texture: int, width: int, height: int, d_rgb_ptr: int, stream: int = 0) -> None:
+        """d_rgb_ptr: device uint8 [height, width, 3]; copied on `stream`, later work on any stream sees it (rtk.h)."""
+        _check(_L.rtk_accel_set_texture_pixels_device(self._h, texture, width, height, d_rgb_ptr or None, stream))
+
+    def set_texture_frame_device(self, texture: int, width: int, height: int, d_rgb_ptr: int, stream: int = 0) -> None:
+        """Render to texture: d_rgb_ptr is a device float32 frame [height, width, 3]; the texels become its write_ppm bytes."""
+        _check(_L.rtk_accel_set_texture_frame_device(self._h, texture, width, height, d_rgb_ptr or None, stream))
+
+    def uvs(self) -> np.ndarray:
+        """float32 [n_vertices, 2]: the uvs of all meshes' vertices, zeros for a mesh that has none."""
+        out = np.zeros((self.scene.info.n_vertices, 2), np.float32)
+        _check(_L.rtk_accel_get_uvs(self._h, out.ctypes.data))
+        return out
+
+    def set_uvs(self, uv) -> None:
+        uv = np.asarray(uv, np.float32)
+        if uv.shape != (self.scene.info.n_vertices, 2):
+            raise ValueError(f"uvs must have shape ({self.scene.info.n_vertices}, 2)")
+        uv = np.ascontiguousarray(uv)
+        _check(_L.rtk_accel_set_uvs(self._h, uv.ctypes.data))
+
+    def set_uvs_device(self, d_uvs_ptr: int, stream: int = 0) -> None:
+        """d_uvs_ptr: device float32 [n_vertices, 2]; read on `stream`, later work on any stream sees the new uvs (rtk.h)."""
+        _check(_L.rtk_accel_set_uvs_device(self._h, d_uvs_ptr or None, stream))
 
     def last_critical_path_ms(self) -> float:
         """Longest 8x8 pixel block of the most recent megakernel frame (ms): the frame's critical path."""

@@ -322,7 +322,7 @@ struct rtk_accel {
     // numbers: the host arrays they came from are dropped by the updates.
     std::vector<int32_t> mesh_nverts, mesh_ntris;
     rtk::DevBuf<rtk::dev::TopoMesh> topo_meshes;   // [n_meshes + 1] the small per-mesh table of the call in flight
-    rtk::DevBuf<float> topo_vert_uv;           // [n_vertices][2], zero for meshes without uvs; made once, with textures only
+    rtk::DevBuf<float> topo_vert_uv;           // [n_vertices][2], zero for meshes without uvs: the current ones while vert_uv_dev
     rtk::DevBuf<uint32_t> topo_keys;           // the sorted vertex ids of the incidence sort
     rtk::DevBuf<uint8_t> topo_temp;            // rocPRIM's
     rtk::DevBuf<uint32_t> up_idx_stage;        // staging of the host variant's indices
@@ -337,6 +337,22 @@ struct rtk_accel {
     rtk::DevBuf<rtk::DevMaterial> st_materials;    // the spare material table: written, read by the regather, then swapped with d_materials
     rtk::DevBuf<rtk::dev::OcclLeaf> st_leaves;     // one row per leaf of the active tree
     rtk::DevBuf<uint32_t> st_counts;           // opaque references per leaf
+    // ---- tx_* / vert_uv: textures and uvs of a live accel (api_state.hip).  On the host scene.textures / scene.tex_pixels stay the
+    // dense table rtk_scene_create makes; a resident accel keeps every bitmap in a slot of d_tex_pixels, 16-byte aligned once a
+    // setter has laid the buffer out, and d_textures holds the slots' offsets.
+    struct TexSlot {
+        int32_t off = 0;                       // of the texels in d_tex_pixels
+        size_t cap = 0;                        // bytes the slot has room for
+        bool on_device = false;                // set through a _device call: the host's bytes of this texture are stale
+    };
+    std::vector<TexSlot> tx_slots;             // one per texture of a resident accel (used by the bitmaps)
+    size_t tx_used = 0;                        // bytes of d_tex_pixels handed out
+    rtk::DevBuf<rtk::DevTexture> tx_textures;  // the spare table and the spare texel buffer: written, then swapped in
+    rtk::DevBuf<uint8_t> tx_pixels;
+    std::vector<float> vert_uv;                // [n_vertices][2] of all meshes, zeros for a mesh without uvs; made on first use
+    bool vert_uv_made = false;
+    bool uvs_on_device = false;                // rtk_accel_set_uvs_device: the values are in topo_vert_uv only
+    bool vert_uv_dev = false;                  // topo_vert_uv holds the current uvs
     // ---- the last frame (rtk_render_last_counters, rtk_render_last_critical_path)
     hipStream_t last_stream = nullptr;
     uint64_t last_primary = 0;
@@ -409,6 +425,13 @@ inline void forget_orders(rtk_accel *a, unsigned keep = 0u) {
 // from the active tree into the spare buffers and swapped in.  `d_materials`: the new table on the device; a->scene.materials
 // and a->has_refractive are still the old ones and stay so on failure.
 int remake_occluders(rtk_accel *a, const std::vector<DevMaterial> &materials, const DevMaterial *d_materials, hipStream_t s);
+// The topology tables of the scene the accel was built from, on the device (topo): made once, on the first call that needs them.
+int ensure_update_static(rtk_accel *a);
+// api_state.hip
+// the slots of a dense texel upload (ensure_device), the per-vertex uvs on the host, and the same on the device (topo_vert_uv)
+void dense_texture_slots(rtk_accel *a);
+const std::vector<float> &host_vert_uv(rtk_accel *a);
+int ensure_vert_uv_dev(rtk_accel *a);
 // api_frame.hip
 int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g);
 int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes);

@@ -54,6 +54,7 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
         RTK_TRY(upload(a->tree.dev_tri_uv, a->topo.tri_uv));
         if (!a->scene.tex_pixels.empty()) RTK_TRY(upload(a->scene.tex_pixels, a->d_tex_pixels));
     }
+    dense_texture_slots(a);
     RTK_MEM(a->d_counters.reserve(kCounterAllocWords));                     // (the counters and their tail: counters.hpp)
     RTK_HIP(hipMemset(a->d_counters.get(), 0, kCounterAllocWords * sizeof(unsigned long long)));
     a->on_device = true;

@@ -11,11 +11,9 @@ using namespace rtk;
 
 // (Buffers that have to grow do so by grow_bytes; freeing synchronises the device: this is the "second block" of an update, taken
 // only then.)
-namespace {
-
 // The topology tables of an update of the vertices (update_plan.hpp, host_topology): made on the host from the scene the accel
 // was built from, on its first update; rtk_accel_update_geometry replaces them by what topology.hip makes of its triangle lists.
-int ensure_update_static(rtk_accel *a) {
+int rtk::ensure_update_static(rtk_accel *a) {
     if (a->up_static) return RTK_OK;
     HostTopology H;
     if (const char *why = host_topology(a->scene, a->mesh_nverts, H)) return fail(RTK_ERR_INVALID, why);
@@ -28,6 +26,8 @@ int ensure_update_static(rtk_accel *a) {
     a->up_static = true;
     return RTK_OK;
 }
+
+namespace {
 
 // New triangle lists for an update (null: the vertices alone moved).
 struct NewTopology {
@@ -52,17 +52,7 @@ int prepare_topology(rtk_accel *a, const NewTopology &N, hipStream_t s, dev::Top
     RTK_HIP_AS(topology_temp_bytes(uint32_t(nt), uint32_t(nv), &temp_bytes), "size the incidence sort");
     RTK_MEM(a->topo_temp.reserve(temp_bytes, grow_bytes()));
     RTK_MEM(a->topo_meshes.reserve(nm + 1));                                // (once: the number of meshes is fixed)
-    if (textured && !a->topo_vert_uv.get()) {                                     // kdtree.cpp:283-: a mesh without uvs has zeros
-        std::vector<float> uv(std::max<size_t>(1, nv) * 2, 0.0f);
-        size_t voff = 0;
-        for (size_t mi = 0; mi < nm; ++mi) {
-            const std::vector<float> &mu = a->scene.meshes[mi].uvs;
-            const size_t n = std::min(mu.size(), size_t(a->mesh_nverts[mi]) * 2);
-            if (n > 0) std::memcpy(uv.data() + voff * 2, mu.data(), n * sizeof(float));
-            voff += size_t(a->mesh_nverts[mi]);
-        }
-        RTK_TRY(upload(uv, a->topo_vert_uv));
-    }
+    if (textured) RTK_TRY(ensure_vert_uv_dev(a));                           // the CURRENT per-vertex uvs (rtk_accel_set_uvs)
     RTK_MEM(a->up_stage.reserve((nm + 1) * sizeof(dev::TopoMesh), grow_bytes()));
     dev::TopoMesh *rows = reinterpret_cast<dev::TopoMesh *>(a->up_stage.get());
     uint32_t tri = 0u, vert = 0u;

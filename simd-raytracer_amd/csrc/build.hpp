@@ -109,6 +109,8 @@ hipError_t launch_occl_gather(const dev::OcclArgs &O, hipStream_t s);
 // header memset + (with `topo`: the topology tables, topology.hip) + triangles + vertex normals + tree
 hipError_t launch_build(const dev::BuildArgs &B, const dev::TopoArgs *topo, hipStream_t s);
 hipError_t launch_topology(const dev::TopoArgs &T, hipStream_t s);
+// DevTriUv of the n_tris triangles whose vertex ids `index` holds, from the per-vertex uvs
+hipError_t launch_tri_uv(const uint32_t *index, const float *vert_uv, uint32_t n_tris, uint32_t n_verts, DevTriUv *tri_uv, hipStream_t s);
 hipError_t topology_temp_bytes(uint32_t n_tris, uint32_t n_verts, size_t *bytes);
 hipError_t launch_gather(const dev::GatherArgs &G, hipStream_t s);
 

@@ -792,12 +792,37 @@ __global__ void k_add_word(unsigned long long *dst, const unsigned long long *sr
 }
 
 // write_ppm's quantisation (io/image/ppm.hpp:17-19): uint8(255.999 * clamp(c, 0, 1)), the product in double.
+__device__ __forceinline__ uint8_t to_rgb8(const float c) {
+    const float k = (c < 0.0f) ? 0.0f : ((1.0f < c) ? 1.0f : c);           // std::clamp(c, 0.f, 1.f)
+    return (uint8_t)(255.999 * (double)k);
+}
+
 __global__ __launch_bounds__(256) void k_to_rgb8(const float *rgb, size_t n, uint8_t *out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float c = rgb[i];
-    const float k = (c < 0.0f) ? 0.0f : ((1.0f < c) ? 1.0f : c);           // std::clamp(c, 0.f, 1.f)
-    out[i] = (uint8_t)(255.999 * (double)k);
+    out[i] = to_rgb8(rgb[i]);
+}
+
+// rtk_accel_set_texture_frame_device: the same bytes, packed, to a texture's slot -- any byte address.  Behind the up to three
+// bytes in front of the first dword boundary a thread owns four pixels: twelve floats in, three dwords out, so a wave's stores
+// are 768 consecutive bytes.  The thread behind the last group writes the ragged head and tail (fewer than 15 bytes) one by one.
+__global__ __launch_bounds__(256) void k_frame_to_texels(const float *rgb, size_t n, uint8_t *out) {
+    const size_t to_boundary = (size_t)((4u - (unsigned)((uintptr_t)out & 3u)) & 3u);
+    const size_t head = to_boundary < n ? to_boundary : n;
+    const size_t groups = (n - head) / 12u;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < groups) {
+        const float *src = rgb + head + t * 12u;
+        uint32_t *dst = reinterpret_cast<uint32_t *>(out + head) + t * 3u;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float *c = src + j * 4;
+            dst[j] = (uint32_t)to_rgb8(c[0]) | ((uint32_t)to_rgb8(c[1]) << 8) | ((uint32_t)to_rgb8(c[2]) << 16) | ((uint32_t)to_rgb8(c[3]) << 24);
+        }
+    } else if (t == groups) {
+        for (size_t i = 0; i < head; ++i) out[i] = to_rgb8(rgb[i]);
+        for (size_t i = head + groups * 12u; i < n; ++i) out[i] = to_rgb8(rgb[i]);
+    }
 }
 
 }  // namespace dev
@@ -1172,6 +1197,13 @@ hipError_t launch_region_accumulate(const dev::RenderArgs &A, uint64_t first, ui
 
 hipError_t launch_add_word(unsigned long long *dst, const unsigned long long *src, hipStream_t s) {
     hipLaunchKernelGGL(dev::k_add_word, dim3(1), dim3(64), 0, s, dst, src);
+    return hipGetLastError();
+}
+
+hipError_t launch_frame_to_texels(const float *d_rgb, size_t n, uint8_t *d_out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const size_t threads = n / 12u + 1u;                                    // (at most the groups, and the one behind them)
+    hipLaunchKernelGGL(dev::k_frame_to_texels, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_rgb, n, d_out);
     return hipGetLastError();
 }
 

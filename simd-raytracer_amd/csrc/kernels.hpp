@@ -146,6 +146,8 @@ hipError_t launch_counters_fold(const unsigned long long *cur, unsigned long lon
 hipError_t launch_assemble(const dev::AssembleArgs &A, hipStream_t s);
 hipError_t launch_camera_rays(const dev::RenderArgs &A, int sample, rtk_ray *d_rays, hipStream_t s);
 hipError_t launch_to_rgb8(const float *d_rgb, size_t n, uint8_t *d_out, hipStream_t s);
+// the same bytes for the n = width * height * 3 floats of a frame, to any byte address (a texture's slot)
+hipError_t launch_frame_to_texels(const float *d_rgb, size_t n, uint8_t *d_out, hipStream_t s);
 // The streaming path of rtk_render_regions, per sample and chunk of `n` pixels starting at pixel `first` of the launch's entries
 // (RegionEntry::first_pixel order): the camera rays of those pixels at `sample` with their frame pixel indices ...
 hipError_t launch_region_rays(const dev::RenderArgs &A, int sample, uint64_t first, uint32_t n, rtk_ray *d_rays, uint32_t *d_ids, hipStream_t s);

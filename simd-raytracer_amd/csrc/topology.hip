@@ -7,6 +7,7 @@
 //                   vertex array, DevShade::mesh / ::material, the opaque flag, DevTriUv
 //   the sort        rocPRIM, stable: the 3 n (vertex, triangle * 3 + corner) pairs by vertex
 //   k_topo_offsets  one thread per vertex: where its run begins in the sorted pairs
+//   k_tri_uv        one thread per triangle: DevTriUv alone, for new per-vertex uvs on the topology as it is
 //
 // An index is the caller's and may be anything.  k_topo_tris is the only kernel that sees it raw: it compares it with the vertex
 // count of the triangle's own mesh, raises kBuildBadIndex and puts the mesh's first vertex in its place.  Everything behind it --
@@ -26,6 +27,14 @@
 namespace rtk {
 namespace dev {
 namespace {
+
+// triangle::uvs, loader.hpp:199-207 (kdtree.cpp build_tree): the uvs of a triangle's three vertices, by their ids over all meshes
+__device__ __forceinline__ DevTriUv gather_tri_uv(const float *vert_uv, const uint32_t (&g)[3]) {
+    DevTriUv u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { u.uv[k * 2] = vert_uv[size_t(g[k]) * 2]; u.uv[k * 2 + 1] = vert_uv[size_t(g[k]) * 2 + 1]; }
+    return u;
+}
 
 __global__ __launch_bounds__(256) void k_topo_tris(const TopoArgs T) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,13 +60,19 @@ __global__ __launch_bounds__(256) void k_topo_tris(const TopoArgs T) {
     T.opaque[i] = uint8_t(M.opaque);
     DevShade *sh = T.shade + i;                                     // (fn: k_build_tris; n0..n2: k_build_normals, every corner is in one list)
     sh->mesh = m; sh->material = M.material; sh->pad[0] = 0u; sh->pad[1] = 0u;
-    if (T.tri_uv != nullptr) {                                      // triangle::uvs, loader.hpp:199-207 (kdtree.cpp build_tree)
-        DevTriUv u;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { u.uv[k * 2] = T.vert_uv[size_t(g[k]) * 2]; u.uv[k * 2 + 1] = T.vert_uv[size_t(g[k]) * 2 + 1]; }
-        T.tri_uv[i] = u;
-    }
+    if (T.tri_uv != nullptr) T.tri_uv[i] = gather_tri_uv(T.vert_uv, g);
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull && __lane_id() == 0u) atomicAnd(&T.hdr->ok, ~kBuildBadIndex);
+}
+
+// rtk_accel_set_uvs / _set_textures: the per-triangle uvs alone, through the vertex ids of the live topology (`index` as
+// k_topo_tris or the host wrote it: every id is a vertex; the clamp keeps a table that lies from becoming an address).
+__global__ __launch_bounds__(256) void k_tri_uv(const uint32_t *index, const float *vert_uv, uint32_t n_tris, uint32_t n_verts, DevTriUv *tri_uv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tris) return;
+    uint32_t g[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { const uint32_t v = index[size_t(i) * 3 + k]; g[k] = v < n_verts ? v : n_verts - 1u; }
+    tri_uv[i] = gather_tri_uv(vert_uv, g);
 }
 
 // inc_off[v] = the number of pairs whose vertex is below v, for v in [0, n_verts]: vertices no triangle uses get an empty run.
@@ -88,6 +103,12 @@ hipError_t topology_temp_bytes(uint32_t n_tris, uint32_t n_verts, size_t *bytes)
     uint32_t *nk = nullptr;
     return rocprim::radix_sort_pairs(nullptr, *bytes, nk, nk, rocprim::counting_iterator<uint32_t>(0u), nk, size_t(n_tris) * 3, 0u,
                                      dev::key_bits(n_verts), nullptr);
+}
+
+hipError_t launch_tri_uv(const uint32_t *index, const float *vert_uv, uint32_t n_tris, uint32_t n_verts, DevTriUv *tri_uv, hipStream_t s) {
+    if (n_tris == 0u || n_verts == 0u) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_tri_uv, dim3((n_tris + 255u) / 256u), dim3(256), 0, s, index, vert_uv, n_tris, n_verts, tri_uv);
+    return hipGetLastError();
 }
 
 hipError_t launch_topology(const dev::TopoArgs &T, hipStream_t s) {

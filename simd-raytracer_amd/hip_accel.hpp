@@ -50,35 +50,13 @@ struct hip_accel {
         // scene.textures is keyed by name (scene/scene.hpp:18); the C-ABI refers to textures by index
         std::vector<std::string> texture_names;
         for (const auto &[name, tv] : sc.textures) {
-            float a[3] = {0.f, 0.f, 0.f}, b[3] = {0.f, 0.f, 0.f}, prm = 0.f;
-            int kind = -1;
-            int32_t bmp[3] = {0, 0, 0};
-            std::visit([&](const auto &t) {
-                using T = std::decay_t<decltype(t)>;
-                if constexpr (std::is_same_v<T, albedo_texture<F>>) { kind = RTK_TEX_ALBEDO; a[0] = t.albedo.red; a[1] = t.albedo.green; a[2] = t.albedo.blue; }
-                else if constexpr (std::is_same_v<T, edge_texture<F>>) {
-                    kind = RTK_TEX_EDGES; prm = t.edge_width;
-                    a[0] = t.edge_color.red; a[1] = t.edge_color.green; a[2] = t.edge_color.blue;
-                    b[0] = t.inner_color.red; b[1] = t.inner_color.green; b[2] = t.inner_color.blue;
-                } else if constexpr (std::is_same_v<T, checker_texture<F>>) {
-                    kind = RTK_TEX_CHECKER; prm = t.square_size;
-                    a[0] = t.color_a.red; a[1] = t.color_a.green; a[2] = t.color_a.blue;
-                    b[0] = t.color_b.red; b[1] = t.color_b.green; b[2] = t.color_b.blue;
-                } else {                                  // bitmap_texture (scene/texture/bitmap.hpp:40-44)
-                    kind = RTK_TEX_BITMAP;
-                    const std::size_t h = t.texture.get_height(), w = t.texture.get_width();
-                    bmp[0] = static_cast<int32_t>(tex_pixels.size()); bmp[1] = static_cast<int32_t>(w); bmp[2] = static_cast<int32_t>(h);
-                    for (std::size_t r = 0; r < h; ++r) for (std::size_t c = 0; c < w; ++c) {
-                        const auto &px = t.texture.get_pixel(r, c);     // F(byte) * F(1.0 / 255.0), bitmap.hpp:19-28: invert exactly
-                        const F ch[3] = {px.red, px.green, px.blue};
-                        for (F v : ch) tex_pixels.push_back(static_cast<uint8_t>(v * F(255) + F(0.5)));
-                    }
-                }
-            }, tv);
+            const int32_t first_byte = static_cast<int32_t>(tex_pixels.size());
+            const rtk_texture t = to_texture(tv, tex_pixels);
+            const int32_t bmp[3] = {t.kind == RTK_TEX_BITMAP ? first_byte : 0, t.width, t.height};
             tex_bitmap.insert(tex_bitmap.end(), bmp, bmp + 3);
             texture_names.push_back(name);
-            tex_kind.push_back(kind); tex_param.push_back(prm);
-            tex_a.insert(tex_a.end(), a, a + 3); tex_b.insert(tex_b.end(), b, b + 3);
+            tex_kind.push_back(t.kind); tex_param.push_back(t.param);
+            tex_a.insert(tex_a.end(), t.color_a, t.color_a + 3); tex_b.insert(tex_b.end(), t.color_b, t.color_b + 3);
         }
         for (const auto &mesh : sc.meshes) {
             mesh_material.push_back(static_cast<int32_t>(mesh.material_idx));
@@ -339,6 +317,82 @@ struct hip_accel {
         return color<F>{rgb[0], rgb[1], rgb[2]};
     }
 
+    // Textures and uvs of later frames (rtk_accel_set_textures / _set_texture_pixels / _set_uvs), in the same way: the accel moves,
+    // the scene is const.  set_textures replaces the whole table, by name and in the caller's order (a texture_material handed to a
+    // later set_materials names one of THESE); a table that drops a texture some live material uses is refused.  A bitmap comes
+    // back as its image<F>: bitmap_texture can only be made from a file (scene/texture/bitmap.hpp:43).
+    using named_texture = std::pair<std::string, texture_variant<F>>;
+    using texture_now = std::variant<albedo_texture<F>, edge_texture<F>, checker_texture<F>, image<F>>;
+    void set_textures(std::span<const named_texture> textures) {
+        std::vector<rtk_texture> in(textures.size() + 1);
+        std::vector<std::vector<uint8_t>> texels(textures.size());
+        std::vector<const uint8_t *> pixels(textures.size() + 1, nullptr);
+        std::vector<std::string> names;
+        for (std::size_t i = 0; i < textures.size(); ++i) {
+            in[i] = to_texture(textures[i].second, texels[i]);
+            pixels[i] = texels[i].data();
+            names.push_back(textures[i].first);
+        }
+        check(rtk_accel_set_textures(accel_.get(), in.data(), static_cast<int32_t>(textures.size()), pixels.data()));
+        texture_names_ = std::move(names);
+    }
+    [[nodiscard]] std::vector<std::pair<std::string, texture_now>> textures_now() const {
+        int32_t n = 0;
+        check(rtk_accel_get_textures(accel_.get(), nullptr, 0, &n));
+        std::vector<rtk_texture> in(static_cast<std::size_t>(n) + 1);
+        check(rtk_accel_get_textures(accel_.get(), in.data(), n, &n));
+        std::vector<std::pair<std::string, texture_now>> out;
+        for (std::size_t i = 0; i < static_cast<std::size_t>(n); ++i) {
+            const rtk_texture &t = in[i];
+            const color<F> a{t.color_a[0], t.color_a[1], t.color_a[2]}, b{t.color_b[0], t.color_b[1], t.color_b[2]};
+            const std::string &name = texture_names_.at(i);
+            if (t.kind == RTK_TEX_EDGES) out.emplace_back(name, edge_texture<F>{a, b, t.param});
+            else if (t.kind == RTK_TEX_CHECKER) out.emplace_back(name, checker_texture<F>{a, b, t.param});
+            else if (t.kind == RTK_TEX_BITMAP) {
+                const std::size_t w = static_cast<std::size_t>(t.width), h = static_cast<std::size_t>(t.height);
+                std::vector<uint8_t> bytes(w * h * 3);
+                std::size_t got = 0;
+                check(rtk_accel_get_texture_pixels(accel_.get(), static_cast<int32_t>(i), bytes.data(), bytes.size(), &got));
+                const F color_scale = F(1.0 / 255.0);                             // bitmap.hpp:19
+                std::vector<std::vector<color<F>>> px(h, std::vector<color<F>>(w));
+                for (std::size_t r = 0; r < h; ++r) for (std::size_t c = 0; c < w; ++c) {
+                    const uint8_t *p = bytes.data() + (r * w + c) * 3;
+                    px[r][c] = color<F>{static_cast<F>(p[0]) * color_scale, static_cast<F>(p[1]) * color_scale, static_cast<F>(p[2]) * color_scale};
+                }
+                out.emplace_back(name, image<F>(h, w, std::move(px)));
+            } else out.emplace_back(name, albedo_texture<F>{a});
+        }
+        return out;
+    }
+    // new texels for the bitmap texture `name`; the size may differ from before
+    void set_texture_pixels(const std::string &name, const image<F> &im) {
+        std::vector<uint8_t> texels;
+        int32_t w = 0, h = 0;
+        to_texels(im, w, h, texels);
+        texels.push_back(0);                                                      // (a valid pointer for an empty image: the library judges the size)
+        check(rtk_accel_set_texture_pixels(accel_.get(), static_cast<int32_t>(texture_index(name, "hip_accel::set_texture_pixels")), w, h, texels.data()));
+    }
+    // one uv per vertex, all meshes' vertices one behind the other (a mesh without uvs has zeros, loader.hpp:199-207)
+    void set_uvs(std::span<const vec2<F>> uvs) {
+        std::size_t nv = 0;
+        for (const auto &mesh : scene_ptr->meshes) nv += mesh.vertices.size();
+        if (uvs.size() != nv) throw std::invalid_argument("hip_accel::set_uvs: one uv per vertex of the scene");
+        std::vector<float> flat;
+        flat.reserve(nv * 2 + 2);
+        for (const auto &uv : uvs) { flat.push_back(uv.x); flat.push_back(uv.y); }
+        flat.push_back(0.f);
+        check(rtk_accel_set_uvs(accel_.get(), flat.data()));
+    }
+    [[nodiscard]] std::vector<vec2<F>> uvs_now() const {
+        std::size_t nv = 0;
+        for (const auto &mesh : scene_ptr->meshes) nv += mesh.vertices.size();
+        std::vector<float> flat(nv * 2 + 2);
+        check(rtk_accel_get_uvs(accel_.get(), flat.data()));
+        std::vector<vec2<F>> out(nv);
+        for (std::size_t i = 0; i < nv; ++i) out[i] = vec2<F>{flat[i * 2], flat[i * 2 + 1]};
+        return out;
+    }
+
     // One whole frame per camera from one call (rtk_render_views): image v is what set_camera(views[v]) + render_frame(params)
     // gives, and the accel's own camera stays.  counters: totals over the views.
     [[nodiscard]] std::vector<std::vector<std::vector<color<F>>>> render_views(std::span<const camera<F>> views, const rtk_render_params &params,
@@ -457,6 +511,45 @@ private:
     std::vector<std::size_t> first_triangle_;     // global triangle index of each mesh's first triangle
     std::size_t n_triangles_ = 0;
     std::vector<std::string> texture_names_;      // the C-ABI's texture indices, in the order the constructor met scene.textures
+
+    // one row of the texture table, as the constructor flattens scene.textures; a bitmap's texels are appended to `texels`
+    [[nodiscard]] static rtk_texture to_texture(const texture_variant<F> &tv, std::vector<uint8_t> &texels) {
+        rtk_texture out{};
+        std::visit([&](const auto &t) {
+            using T = std::decay_t<decltype(t)>;
+            float *a = out.color_a, *b = out.color_b;
+            if constexpr (std::is_same_v<T, albedo_texture<F>>) { out.kind = RTK_TEX_ALBEDO; a[0] = t.albedo.red; a[1] = t.albedo.green; a[2] = t.albedo.blue; }
+            else if constexpr (std::is_same_v<T, edge_texture<F>>) {
+                out.kind = RTK_TEX_EDGES; out.param = t.edge_width;
+                a[0] = t.edge_color.red; a[1] = t.edge_color.green; a[2] = t.edge_color.blue;
+                b[0] = t.inner_color.red; b[1] = t.inner_color.green; b[2] = t.inner_color.blue;
+            } else if constexpr (std::is_same_v<T, checker_texture<F>>) {
+                out.kind = RTK_TEX_CHECKER; out.param = t.square_size;
+                a[0] = t.color_a.red; a[1] = t.color_a.green; a[2] = t.color_a.blue;
+                b[0] = t.color_b.red; b[1] = t.color_b.green; b[2] = t.color_b.blue;
+            } else {                                  // bitmap_texture (scene/texture/bitmap.hpp:40-44)
+                out.kind = RTK_TEX_BITMAP;
+                to_texels(t.texture, out.width, out.height, texels);
+            }
+        }, tv);
+        return out;
+    }
+
+    // image<F> back as the bytes stbi_load gave: a channel is F(byte) * F(1.0 / 255.0) (bitmap.hpp:19-28), inverted exactly
+    static void to_texels(const image<F> &im, int32_t &width, int32_t &height, std::vector<uint8_t> &texels) {
+        const std::size_t h = im.get_height(), w = im.get_width();
+        width = static_cast<int32_t>(w); height = static_cast<int32_t>(h);
+        for (std::size_t r = 0; r < h; ++r) for (std::size_t c = 0; c < w; ++c) {
+            const auto &px = im.get_pixel(r, c);
+            const F ch[3] = {px.red, px.green, px.blue};
+            for (F v : ch) texels.push_back(static_cast<uint8_t>(v * F(255) + F(0.5)));
+        }
+    }
+
+    [[nodiscard]] std::size_t texture_index(const std::string &name, const char *who) const {
+        for (std::size_t ti = 0; ti < texture_names_.size(); ++ti) if (texture_names_[ti] == name) return ti;
+        throw std::invalid_argument(std::string(who) + ": unknown texture '" + name + "'");
+    }
 
     // one row of the material table, as the constructor flattens scene.materials
     [[nodiscard]] rtk_material to_material(const material_variant<F> &mv) const {

@@ -3,6 +3,7 @@
 #include <mutex>
 
 #include "accel.hpp"
+#include "batch_plan.hpp"
 #include "repack.hpp"
 #include "occluded.hpp"
 
@@ -41,29 +42,24 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
     // then walked wave-cooperatively when the sort makes tight waves (three varying dimensions: 10 bits each), with the per-lane
     // fallback when it cannot (six: 5 bits each).  4 M rays on scene5: shuffled camera rays 4.5 -> 0.47 ms, uniform secondary
     // rays 11.3 -> 4.1 ms, camera rays in pixel order 0.8 (RTK_TRACE_AUTO before) -> 0.3 ms.
-    const bool big = n >= (size_t(1) << 18) && n < (size_t(1) << 32);
-    const bool forced = mode == RTK_TRACE_REPACK;
-    if (forced) mode = RTK_TRACE_AUTO;
-    const bool sortable = !stats && n >= 2 && n < (size_t(1) << 32);
-    const bool probe = !stats && !forced && mode == RTK_TRACE_AUTO && a->knobs.repack && big;
-    if ((forced && sortable) || probe) {
+    // (the arithmetic of these decisions: batch_plan.hpp)
+    const BatchKnobs bk = {a->knobs.repack, a->knobs.repack_full_bounds, a->knobs.repack_skip_bits, a->knobs.repack_skip_bits2, a->knobs.repack_trace};
+    const BatchPlan plan = plan_batch(n, mode, stats, bk);
+    mode = plan.mode;
+    if (plan.workspace) {
         RTK_TRY(ensure_repack_ws(a, n));
         // The workspace (bounds, keys, permutation) belongs to the accel: a batch on another stream may still be walking the
         // permutation of the previous call.  Its k_intersect recorded rp_last; this stream waits for it before it rewrites anything.
         RTK_HIP(a->rp_last.wait_previous(s));
         hipError_t eb = hipSuccess;
-        bool sort = forced;
-        unsigned sort_from_bit = 0u;
-        bool keys_made = false;
-        int sorted_mode = RTK_TRACE_AUTO;                                    // any order: wave-cooperative with the per-lane fallback
-        if (probe) {
+        uint32_t sort_word = 0u, dims_word = 0u;
+        if (plan.probe) {
             // AUTO: the probe's verdict is needed on the host (one stream synchronisation; RTK_TRACE_REPACK and RTK_REPACK=0 never block)
             // The verdict is made on the device (k_raster_probe) and needed on the host; while it travels, the launch a coherent
             // batch needs is already under way -- it reads the same verdict and does nothing if the batch is to be sorted.
-            const uint32_t probe_stride = uint32_t(((n + 63) / 64 + 4095) / 4096 > 16 ? ((n + 63) / 64 + 4095) / 4096 : 16);   // ~4,096 waves looked at
             unsigned fold = 0;
-            eb = launch_ray_bounds(d_rays, n, a->rp_bounds.get(), probe_stride, true, s, &fold);
-            if (eb == hipSuccess) eb = launch_raster_probe(d_rays, n, a->rp_bounds.get(), a->knobs.raster_tiles, s, fold);
+            eb = launch_ray_bounds(d_rays, n, a->rp_bounds.get(), plan.probe_stride, true, s, &fold);
+            if (eb == hipSuccess) eb = launch_raster_probe(d_rays, n, a->rp_bounds.get(), a->knobs.raster_tiles, s, fold, a->knobs.repack_dirs3);
             if (eb != hipSuccess) return hip_fail(eb, "launch k_ray_bounds (probe)");
             RTK_MEM(a->rp_host.reserve(kRepackBoundsWords));
             RTK_MEM(a->rp_probe_ev.ensure());
@@ -75,35 +71,25 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
             RTK_HIP_AS(launch_intersect(Spec, RTK_TRACE_WAVE, false, s), "launch k_intersect");
             // ... and so are the keys a batch to be sorted needs (k_ray_keys returns at once if it is not): the verdict's trip to the
             // host and the launches that follow it no longer leave the stream idle
-            if (!a->knobs.repack_full_bounds) {
+            if (plan.keys_ahead) {
                 eb = launch_ray_keys(d_rays, n, a->rp_bounds.get(), a->rp_keys.get(), a->rp_idx.get(), s, a->knobs.repack_dirs3, true);
                 if (eb != hipSuccess) return hip_fail(eb, "launch k_ray_keys");
-                keys_made = true;
             }
             RTK_HIP(a->rp_last.record(s));                                        // (both read the workspace's verdict words)
             RTK_HIP(hipEventSynchronize(a->rp_probe_ev.get()));                   // the verdict, not the trace
-            sort = rp_host[16] != 0u;
-            if (!sort) return RTK_OK;                                        // coherent as it comes: that launch was the batch
-            if (rp_host[17] <= 3u) {
-                sorted_mode = RTK_TRACE_WAVE;                                // ten or fifteen bits per dimension: the sort makes tight waves
-                // ... also when the lowest ones stay unsorted: one or two radix passes less (two dimensions: 8 of the 15 bits each)
-                sort_from_bit = rp_host[17] <= 2u ? uint32_t(a->knobs.repack_skip_bits2) : uint32_t(a->knobs.repack_skip_bits);
-            }
+            sort_word = rp_host[16]; dims_word = rp_host[17];
         }
-        if (sort) {
-            // The cells of the sort keys lie in the bounds of a SAMPLE of the batch (the probe's, where there was one; ~4,096 waves
-            // otherwise): a ray outside them lands in a border cell -- an order a little worse for it, never another result -- and a
-            // pass over all rays (0.13 ms of a 2^24-ray batch's 1.8) is saved.
-            if (!probe) {
-                const size_t waves = (n + 63) / 64;
-                eb = launch_ray_bounds(d_rays, n, a->rp_bounds.get(), a->knobs.repack_full_bounds ? 1u : uint32_t((waves + 4095) / 4096), false, s);
-            } else if (a->knobs.repack_full_bounds) eb = launch_ray_bounds(d_rays, n, a->rp_bounds.get(), 1u, false, s);
-            if (eb == hipSuccess && !keys_made) eb = launch_ray_keys(d_rays, n, a->rp_bounds.get(), a->rp_keys.get(), a->rp_idx.get(), s, a->knobs.repack_dirs3, false);
-            if (eb == hipSuccess) eb = launch_key_sort(n, a->rp_keys.get(), a->rp_idx.get(), a->rp_temp.get(), a->rp_temp_bytes, s, sort_from_bit);
-            if (eb != hipSuccess) return hip_fail(eb, "ray repacking");
-            A.perm = a->rp_idx.get() + n;
-            mode = a->knobs.repack_trace >= 0 ? a->knobs.repack_trace : sorted_mode;
-        }
+        const SortPlan sp = plan_sort(plan, sort_word, dims_word, bk);
+        if (!sp.sort) return RTK_OK;                                         // coherent as it comes: the probe's launch was the batch
+        // The cells of the sort keys lie in the bounds of a SAMPLE of the batch (the probe's, where there was one; ~4,096 waves
+        // otherwise): a ray outside them lands in a border cell -- an order a little worse for it, never another result -- and a
+        // pass over all rays (0.13 ms of a 2^24-ray batch's 1.8) is saved.
+        if (sp.rebound) eb = launch_ray_bounds(d_rays, n, a->rp_bounds.get(), sp.bounds_stride, false, s);
+        if (eb == hipSuccess && !plan.keys_ahead) eb = launch_ray_keys(d_rays, n, a->rp_bounds.get(), a->rp_keys.get(), a->rp_idx.get(), s, a->knobs.repack_dirs3, false);
+        if (eb == hipSuccess) eb = launch_key_sort(n, a->rp_keys.get(), a->rp_idx.get(), a->rp_temp.get(), a->rp_temp_bytes, s, sp.sort_from_bit);
+        if (eb != hipSuccess) return hip_fail(eb, "ray repacking");
+        A.perm = a->rp_idx.get() + n;
+        mode = sp.mode;
     }
     RTK_HIP_AS(launch_intersect(A, mode, stats, s), "launch k_intersect");
     if (A.perm != nullptr) RTK_HIP(a->rp_last.record(s));

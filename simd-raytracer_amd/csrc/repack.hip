@@ -194,8 +194,9 @@ __global__ __launch_bounds__(256) void k_ray_bounds(const rtk_ray *rays, size_t 
 // it -- a wrong guess costs speed, never a result.
 // ... and the probe's verdict, on the device (the host reads the same words): bounds[16] = 1 when the batch comes in no useful
 // order and is to be sorted (the criteria of RTK_TRACE_AUTO: a quarter of the probed waves with directions more than 0.25 apart, or
-// origins spread over a quarter of the batch's extent), bounds[17] = how many of the key's coordinates vary at all (k_ray_keys).
-__device__ void probe_verdict(uint32_t *bounds) {
+// origins spread over a quarter of the batch's extent), bounds[17] = how many of the key's coordinates vary at all (k_ray_keys:
+// the same bounds, the same thresholds and the same dirs3, so that the host skips low key bits of the key that is made).
+__device__ void probe_verdict(uint32_t *bounds, const uint32_t dirs3) {
     auto k2f = [](uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); };
     float scale = 0.0f, ext[6], oext = 0.0f;
     for (int k = 0; k < 6; ++k) {
@@ -206,7 +207,7 @@ __device__ void probe_verdict(uint32_t *bounds) {
     uint32_t dims = 0u;
     for (int k = 0; k < 6; ++k)
         if (ext[k] > 1.0e-6f * scale && ext[k] < 1.0e30f) { dims += 1u; if (k < 3 && ext[k] > oext) oext = ext[k]; }
-    if (oext == 0.0f) {                                                     // one origin: k_ray_keys takes the directions' octahedral coordinates
+    if (oext == 0.0f && dirs3 == 0u) {                                      // one origin: k_ray_keys takes the directions' octahedral coordinates
         dims = 0u;
         for (int k = 0; k < 2; ++k) {
             const float e = k2f(bounds[20 + k]) - k2f(bounds[18 + k]);
@@ -220,10 +221,10 @@ __device__ void probe_verdict(uint32_t *bounds) {
     bounds[17] = dims;
 }
 
-__global__ __launch_bounds__(256) void k_raster_probe(const rtk_ray *rays, size_t n, uint32_t *bounds, uint32_t want_raster, uint32_t fold_blocks) {
+__global__ __launch_bounds__(256) void k_raster_probe(const rtk_ray *rays, size_t n, uint32_t *bounds, uint32_t want_raster, uint32_t fold_blocks, uint32_t dirs3) {
     uint32_t *out = bounds + 15;
     if (fold_blocks != 0u) fold_partials(bounds, fold_blocks);
-    if (threadIdx.x == 0u) probe_verdict(bounds);
+    if (threadIdx.x == 0u) probe_verdict(bounds, dirs3);
     if (want_raster == 0u) { if (threadIdx.x == 0u) out[0] = 0u; return; }
     __shared__ float s_step0;
     __shared__ uint32_t s_first, s_bad;
@@ -311,6 +312,7 @@ __global__ __launch_bounds__(256) void k_ray_keys(const rtk_ray *rays, size_t n,
     }
     const uint32_t bits = n_active != 0u ? 30u / n_active : 0u;             // per dimension: 2 active -> 15, 3 -> 10, 6 -> 5
     const float cells = (float)(1u << bits);
+    const uint32_t last_cell = (1u << bits) - 1u;
     float to_cell[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) to_cell[k] = cells / ext[k];               // (only the order of the rays hangs on these, no result)
@@ -348,8 +350,11 @@ __global__ __launch_bounds__(256) void k_ray_keys(const rtk_ray *rays, size_t n,
                 float x = (v[k] - lo[k]) * to_cell[k];
                 x = (x == x) ? x : 0.0f;                                    // a NaN ray goes to cell 0 (it misses everything anyway)
                 x = __builtin_fminf(__builtin_fmaxf(x, 0.0f), cells - 1.0f);   // (so does one outside the sampled bounds: a border cell)
+                // (one dimension: 30 bits, and cells - 1 is no float -- it rounds to cells, bit 30, which the sort does not look at:
+                // the ray at the maximum came first.  The integer is held to the last cell as well.)
+                const uint32_t cell = (uint32_t)x < last_cell ? (uint32_t)x : last_cell;
                 place -= 1u;
-                key |= spread_bits((uint32_t)x, n_active, bits) << place;
+                key |= spread_bits(cell, n_active, bits) << place;
             }
         }
         __syncthreads();                                                     // the tile is read: the next one may land
@@ -375,8 +380,8 @@ hipError_t launch_ray_bounds(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds
     return hipGetLastError();
 }
 
-hipError_t launch_raster_probe(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds, bool want_raster, hipStream_t s, unsigned fold_blocks) {
-    hipLaunchKernelGGL(dev::k_raster_probe, dim3(1), dim3(256), 0, s, d_rays, n, d_bounds, want_raster ? 1u : 0u, (uint32_t)fold_blocks);
+hipError_t launch_raster_probe(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds, bool want_raster, hipStream_t s, unsigned fold_blocks, bool dirs3) {
+    hipLaunchKernelGGL(dev::k_raster_probe, dim3(1), dim3(256), 0, s, d_rays, n, d_bounds, want_raster ? 1u : 0u, (uint32_t)fold_blocks, dirs3 ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -22,8 +22,9 @@ constexpr size_t kRepackBoundsAlloc = size_t(kRepackBoundsWords) + size_t(kRepac
 hipError_t launch_ray_bounds(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds, uint32_t wave_stride, bool probe, hipStream_t s,
                              unsigned *unfolded_blocks = nullptr);
 // behind launch_ray_bounds' probe: d_bounds[16], [17] = the verdict (see above); d_bounds[15] = width of the raster the batch is
-// (rows of camera rays), 0 if it is none or want_raster is false
-hipError_t launch_raster_probe(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds, bool want_raster, hipStream_t s, unsigned fold_blocks = 0);
+// (rows of camera rays), 0 if it is none or want_raster is false.  dirs3: as launch_ray_keys will be told -- [17] counts the key's dimensions
+hipError_t launch_raster_probe(const rtk_ray *d_rays, size_t n, uint32_t *d_bounds, bool want_raster, hipStream_t s, unsigned fold_blocks = 0,
+                               bool dirs3 = false);
 hipError_t repack_temp_bytes(size_t n, size_t *bytes);
 // keys (and the identity permutation) from the bounds; only_if_sort: the kernel does nothing unless the probe's verdict (d_bounds[16]) says sort
 hipError_t launch_ray_keys(const rtk_ray *d_rays, size_t n, const uint32_t *d_bounds, uint32_t *d_keys, uint32_t *d_idx, hipStream_t s,

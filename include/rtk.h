@@ -409,6 +409,10 @@ int rtk_render_frame(rtk_accel *accel, const rtk_render_params *p, float *rgb /*
                      rtk_counters *counters /* may be NULL */);
 /* world_size <= 1: d_out is the frame [h][w][3].  world_size > 1: d_out is this rank's compact bucket
  * buffer [buckets_per_rank][bucket][bucket][3] (equal length on every rank, ready for an all-gather). */
+/* Frames of one accel are meant for one stream at a time.  A frame on another stream than the accel's previous frame zeroes its
+ * counters itself; a frame on the same stream may find them zeroed by the frame before it.  Streams are told apart by their
+ * handle: before a stream on which an accel has rendered is destroyed, synchronise it, so that a stream created later at the same
+ * address starts behind that accel's last frame. */
 int rtk_render_frame_device(rtk_accel *accel, const rtk_render_params *p, float *d_out, void *hip_stream);
 /* counters of the most recent rtk_render_frame_device on this accel; synchronises the stream it ran on */
 int rtk_render_last_counters(rtk_accel *accel, rtk_counters *counters);
@@ -416,6 +420,9 @@ int rtk_render_last_counters(rtk_accel *accel, rtk_counters *counters);
  * the frame's critical path -- no number of compute units or GPUs makes the frame shorter than this.  0 for frames that
  * went through the streaming pipeline or whose blocks all took less than 10 microseconds.  Synchronises the stream the frame ran on. */
 int rtk_render_last_critical_path(rtk_accel *accel, double *ms);
+/* Diagnostic, not part of the rendering contract: how many times frames, views and regions calls of this accel have zeroed its
+ * counters with a fill of their own since it was built.  A steady megakernel frame issues none.  Needs no device. */
+int rtk_debug_counter_fills(rtk_accel *accel, uint64_t *fills);
 /* after the all-gather: d_gathered = [world][buckets_per_rank][bucket][bucket][3] -> d_rgb [h][w][3] */
 int rtk_tiles_assemble_device(const rtk_accel *accel, const rtk_render_params *p, const float *d_gathered,
                               float *d_rgb, void *hip_stream);

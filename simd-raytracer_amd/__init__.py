@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "rtk_accel_update_vertices", "rtk_accel_update_vertices_device",
     "rtk_accel_update_geometry", "rtk_accel_update_geometry_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
-    "rtk_render_last_critical_path",
+    "rtk_render_last_critical_path", "rtk_debug_counter_fills",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_render_regions", "rtk_render_regions_device",
@@ -183,6 +183,8 @@ _L.rtk_render_frame.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.POINTER(Cou
 _L.rtk_render_frame_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp]
 _L.rtk_render_last_counters.argtypes = [_vp, C.POINTER(Counters)]
 _L.rtk_render_last_critical_path.argtypes = [_vp, C.POINTER(C.c_double)]
+if hasattr(_L, "rtk_debug_counter_fills"):            # (an older build loaded through RTK_LIB_OVERRIDE for an A/B run has no such diagnostic)
+    _L.rtk_debug_counter_fills.argtypes = [_vp, C.POINTER(C.c_uint64)]
 _L.rtk_tiles_assemble_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]
 _L.rtk_camera_rays.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp]
 _L.rtk_camera_rays_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, _vp]
@@ -840,6 +842,12 @@ class KdTreeSimdAccel:
         ms = C.c_double(0.0)
         _check(_L.rtk_render_last_critical_path(self._h, C.byref(ms)))
         return ms.value
+
+    def counter_fills(self) -> int:
+        """Diagnostic: fills of the counters issued by this accel's frames, views and regions calls so far (a steady frame issues none)."""
+        n = C.c_uint64(0)
+        _check(_L.rtk_debug_counter_fills(self._h, C.byref(n)))
+        return int(n.value)
 
     def assemble_device(self, cfg: RenderConfig, d_gathered_ptr: int, d_rgb_ptr: int, stream: int = 0) -> None:
         p = cfg.to_c()

@@ -246,7 +246,10 @@ struct rtk_accel {
     rtk::DevBuf<rtk::DevLight> d_lights;           // its capacity is the rows it has room for: grows with head room, never shrinks
     rtk::DevBuf<rtk::DevTexture> d_textures;
     rtk::DevBuf<uint8_t> d_tex_pixels;
-    rtk::DevBuf<unsigned long long> d_counters;    // [kCounterAllocWords] counters.hpp
+    // [2][kCounterAllocWords] counters.hpp: the block in use (counters_now) and the one a steady frame's kernel clears for the next frame
+    rtk::DevBuf<unsigned long long> d_counters;
+    rtk::CounterState cnt;                         // which is which (frame_plan.hpp)
+    uint64_t counter_fills = 0;                    // fills of the block in use issued so far (rtk_debug_counter_fills)
     uint32_t occl_n_leaves = 0;
     bool occl_on = false;
     // ---- ws_* / lane_*: streaming-pipeline workspace (api_frame.hip ensure_stream_ws; grown on demand)
@@ -404,6 +407,11 @@ inline bool scene_forks(const rtk_accel *a, int diffuse_rays) { return a->has_re
 // ... and whether it needs the general build of the kernels (+ refraction, diffuse GI, textures) and not the lean one
 inline bool scene_general(const rtk_accel *a, int diffuse_rays) { return scene_forks(a, diffuse_rays) || !a->scene.textures.empty(); }
 
+// The accel's counter block in use and the other one (frame_plan.hpp CounterState).  Whoever counts into the current block without
+// handing a kernel the other one to clear (everything but a steady megakernel frame) fills what it uses itself and calls a->cnt.forget().
+inline unsigned long long *counters_now(const rtk_accel *a) { return a->d_counters.get() + size_t(a->cnt.current) * kCounterAllocWords; }
+inline unsigned long long *counters_other(const rtk_accel *a) { return a->d_counters.get() + size_t(a->cnt.current ^ 1) * kCounterAllocWords; }
+
 // api.hip
 // `s`: the stream the caller is about to issue work on.  It waits for the geometry of the last rtk_accel_update_vertices
 // (which was built on that call's stream) unless that has completed already.
@@ -414,6 +422,7 @@ dev::TreeView tree_view(const rtk_accel *a);
 enum : unsigned { kKeepViewOrders = 1u, kKeepTrial = 2u };
 inline void forget_orders(rtk_accel *a, unsigned keep = 0u) {
     a->fb.forget();
+    a->cnt.forget();                  // (with the frames' order: the next frame fills its counters itself)
     if (!(keep & kKeepViewOrders)) for (rtk_cost_feedback &f : a->fb_views) f.forget();
     for (rtk_cost_feedback &f : a->fb_regions) f.forget();
     if (!(keep & kKeepTrial)) a->trial.abandon();

@@ -55,8 +55,9 @@ int ensure_device(rtk_accel *a, hipStream_t s) {
         if (!a->scene.tex_pixels.empty()) RTK_TRY(upload(a->scene.tex_pixels, a->d_tex_pixels));
     }
     dense_texture_slots(a);
-    RTK_MEM(a->d_counters.reserve(kCounterAllocWords));                     // (the counters and their tail: counters.hpp)
-    RTK_HIP(hipMemset(a->d_counters.get(), 0, kCounterAllocWords * sizeof(unsigned long long)));
+    RTK_MEM(a->d_counters.reserve(2 * kCounterAllocWords));                 // (two blocks of the counters and their tail: counters.hpp, accel.hpp)
+    RTK_HIP(hipMemset(a->d_counters.get(), 0, 2 * kCounterAllocWords * sizeof(unsigned long long)));
+    a->cnt = CounterState{};
     a->on_device = true;
     return RTK_OK;
 }

@@ -35,7 +35,7 @@ static int intersect_device_impl(rtk_accel *a, const rtk_ray *d_rays, size_t n, 
     if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail(RTK_ERR_INVALID, "hit buffer must be 16-byte aligned");
     dev::IntersectArgs A;
     A.tree = tree_view(a);
-    A.rays = d_rays; A.out = d_out; A.n = n; A.cull = cull ? 1 : 0; A.counters = a->d_counters.get(); A.perm = nullptr; A.raster_w = 0u; A.verdict = nullptr;
+    A.rays = d_rays; A.out = d_out; A.n = n; A.cull = cull ? 1 : 0; A.counters = counters_now(a); A.perm = nullptr; A.raster_w = 0u; A.verdict = nullptr;
     A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;
     // Ray repacking (repack.hip).  Large batches are probed first (every 16th wave; one stream synchronisation): waves that are
     // coherent as they come are walked wave-cooperatively; a batch in no useful order is sorted by origin / direction cell and
@@ -111,10 +111,11 @@ int rtk_accel_intersect_stats(rtk_accel *a, const rtk_ray *d_rays, size_t n, int
         if (!a || !counters) return fail(RTK_ERR_INVALID, "null accel or counters");
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        RTK_HIP(hipMemsetAsync(a->d_counters.get(), 0, kCounterWords * sizeof(unsigned long long), nullptr));
+        a->cnt.forget();                                                    // (a user of the counters that is no steady frame: frame_plan.hpp CounterState)
+        RTK_HIP(hipMemsetAsync(counters_now(a), 0, kCounterWords * sizeof(unsigned long long), nullptr));
         RTK_TRY(intersect_device_impl(a, d_rays, n, cull, mode, d_out, nullptr, true));
         unsigned long long h[kRayShardWord];
-        RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
+        RTK_HIP(hipMemcpy(h, counters_now(a), sizeof(h), hipMemcpyDeviceToHost));
         counters_from_block(h, true, counters);
         return RTK_OK;
     });
@@ -161,7 +162,7 @@ static int occluded_launch(rtk_accel *a, const rtk_ray *d_rays, const float *d_m
     A.rays = d_rays; A.max_t = d_max_t; A.out = d_out; A.n = n;
     A.shadow_bias = shadow_bias;
     A.has_refractive = a->has_refractive ? 1 : 0;
-    A.n_intersect = count ? a->d_counters.get() + kOccludedCountWord : nullptr;
+    A.n_intersect = count ? counters_now(a) + kOccludedCountWord : nullptr;
     RTK_HIP_AS(launch_occluded(A, mode, s), "launch k_occluded");
     return RTK_OK;
 }
@@ -192,12 +193,15 @@ int rtk_accel_occluded(rtk_accel *a, const rtk_ray *rays, const float *max_t, si
         RTK_MEM(a->oc_out.reserve(n));
         RTK_HIP(hipMemcpy(a->oc_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
         RTK_HIP(hipMemcpy(a->oc_max_t.get(), max_t, n * sizeof(float), hipMemcpyHostToDevice));
-        if (n_intersections) RTK_HIP(hipMemsetAsync(a->d_counters.get() + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
+        if (n_intersections) {
+            a->cnt.forget();
+            RTK_HIP(hipMemsetAsync(counters_now(a) + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
+        }
         RTK_TRY(occluded_launch(a, a->oc_rays.get(), a->oc_max_t.get(), n, shadow_bias, mode, a->oc_out.get(), nullptr, n_intersections != nullptr));
         RTK_HIP(hipMemcpy(out, a->oc_out.get(), n, hipMemcpyDeviceToHost));
         if (n_intersections) {
             unsigned long long h = 0;
-            RTK_HIP(hipMemcpy(&h, a->d_counters.get() + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
+            RTK_HIP(hipMemcpy(&h, counters_now(a) + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));
             *n_intersections = h;
         }
         return RTK_OK;

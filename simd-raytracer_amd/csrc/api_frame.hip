@@ -168,9 +168,15 @@ dev::RenderArgs scene_args(const rtk_accel *a, int stats_mode) {
     return A;
 }
 
-// the counters of a frame or a part of a call start at zero, with the tail behind them (counters.hpp)
+// the counters of a frame or a part of a call start at zero, with the tail behind them (counters.hpp): the block in use is filled
+hipError_t fill_counters(rtk_accel *a, hipStream_t s) {
+    a->counter_fills += 1;
+    return hipMemsetAsync(counters_now(a), 0, kCounterAllocWords * sizeof(unsigned long long), s);
+}
+// ... by everyone but a steady frame (render_frame_impl), whose block the frame before it cleared: what that frame knew is forgotten
 hipError_t zero_counters(rtk_accel *a, hipStream_t s) {
-    return hipMemsetAsync(a->d_counters.get(), 0, kCounterAllocWords * sizeof(unsigned long long), s);
+    a->cnt.forget();
+    return fill_counters(a, s);
 }
 
 // what rtk_render_last_counters and rtk_render_last_critical_path go by
@@ -347,42 +353,56 @@ int ensure_feedback_ws(rtk_accel *a, rtk_cost_feedback &fb, const FrameGeom &g, 
     const uint64_t tx = (uint64_t(a->scene.width > 0 ? a->scene.width : 0) + bk - 1) / bk, ty = (uint64_t(a->scene.height > 0 ? a->scene.height : 0) + bk - 1) / bk;
     const size_t cap = fb.state.capacity(units, &fb == &a->fb, g.blocks_of(tx * ty));
     RTK_MEM(fb.cost.reserve(cap));
-    RTK_MEM(fb.order.reserve(2 * cap + 4 + 8));                       // order, header, workgroup list, prior's counters
+    RTK_MEM(fb.order.reserve(2 * (2 * cap + 4) + 8));                 // two sets (OrderState) of order, header, workgroup list
     RTK_MEM(fb.bins.reserve(cap));
     fb.state.units = cap;
     return RTK_OK;
 }
 
-// The launch order of a megakernel launch of `units` units: what fb.state (frame_plan.hpp OrderState) says this frame's is made
-// from is launched here, in front of the frame, and handed to the kernel in A.
+// Set k of a table's two sets of launch lists (frame_plan.hpp OrderState): order [units], header [4], workgroup list [units].
+struct ListSet { uint32_t *order, *hdr, *wg_list; };
+ListSet list_set(rtk_cost_feedback &fb, int k, size_t units) {
+    uint32_t *const order = fb.order.get() + size_t(k) * (2 * fb.state.units + 4);
+    return {order, order + units, order + units + 4};
+}
+
+// k_order_by_cost from the costs the last frame stored, into set k, and the read-back of the list's length behind it
+int launch_sort(rtk_accel *a, rtk_cost_feedback &fb, int k, int frame_mode, size_t units, hipStream_t s) {
+    const ListSet L = list_set(fb, k, units);
+    // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
+    RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), L.order, L.wg_list, L.hdr, uint32_t(units),
+                                    frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
+               "launch k_order_by_cost");
+    // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
+    RTK_MEM(fb.nwgs_host.reserve(1));
+    RTK_MEM(fb.nwgs_ev.ensure());
+    RTK_HIP(hipMemcpyAsync(fb.nwgs_host.get(), L.hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RTK_HIP(hipEventRecord(fb.nwgs_ev.get(), s));
+    return RTK_OK;
+}
+
+// The launch order of a megakernel launch of `units` units: what fb.state (frame_plan.hpp OrderState) says is launched in front of
+// the frame is launched here, and the set of lists the frame reads is handed to the kernel in A.  `step`: the decisions, for the
+// caller, which launches the re-sort that goes BEHIND the frame.
 int order_launch(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A, int frame_mode,
-                 size_t units, hipStream_t s) {
+                 size_t units, hipStream_t s, OrderState::Step &step) {
     uint64_t sig[5];
     shape_sig(g, p->spp, p->max_ray_depth, p->diffuse_rays, sig);
     sig[3] = (uint64_t(uint32_t(g.bucket)) << 32) | (uint64_t(uint32_t(g.sample_end - g.sample_begin) & 0xFFFFu) << 16) | uint32_t(p->trace_mode);
     sig[4] = A.regions ? ((1ull << 63) | (uint64_t(A.n_regions) << 32) | uint64_t(A.n_units))   // (its list is compared by the caller)
                        : (A.views ? uint64_t(A.n_views) : 0ull);                                // (0: a frame; a views launch of one view is not one)
     RTK_TRY(ensure_feedback_ws(a, fb, g, units));
-    uint32_t *const order = fb.order.get(), *const order_hdr = order + units, *const wg_list = order + units + 4;
-    const OrderState::Step step = fb.state.step(sig, frame_mode, p->collect_stats != 0, A.regions != nullptr,
-                                                {a->knobs.first_frame_prior, a->knobs.resort_every});
+    step = fb.state.step(sig, frame_mode, p->collect_stats != 0, A.regions != nullptr, {a->knobs.first_frame_prior, a->knobs.resort_every});
+    const ListSet L = list_set(fb, step.read_set, units);
     // (k_block_prior: background blocks packed four to a workgroup, the others by what their centre ray looks at.  A one-shot
     // render is exactly this frame: the reference CLI renders one, src/main.cpp:13-25)
     if (step.prior)
-        RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), order, wg_list, order_hdr,
-                                      reinterpret_cast<uint32_t *>(a->d_counters.get() + kPriorScratchWord), 4u, s), "launch k_block_prior");
-    if (step.resort) {
-        // blocks that cost less than light_cycles (background, a handful of nodes) are packed four to a workgroup: GROUP4 only
-        RTK_HIP_AS(launch_order_by_cost(fb.cost.get(), fb.bins.get(), order, wg_list, order_hdr, uint32_t(units),
-                                        frame_mode == RTK_TRACE_GROUP4 ? a->knobs.light_cycles >> 4 : 0u, a->knobs.order_floor_cycles >> 4, 4u, s),
-                   "launch k_order_by_cost");
-        // how many workgroups the list has: known on the host a frame or two later; until then the launch covers every block
-        RTK_MEM(fb.nwgs_host.reserve(1));
-        RTK_MEM(fb.nwgs_ev.ensure());
-        RTK_HIP(hipMemcpyAsync(fb.nwgs_host.get(), order_hdr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        RTK_HIP(hipEventRecord(fb.nwgs_ev.get(), s));
-    }
-    if (step.use_order) { A.order_in = order; A.order_hdr = order_hdr; A.wg_list = wg_list; }
+        RTK_HIP_AS(launch_block_prior(A, fb.bins.get(), L.order, L.wg_list, L.hdr,
+                                      reinterpret_cast<uint32_t *>(A.counters + kPriorScratchWord), 4u, s), "launch k_block_prior");
+    // (a shape's first sort: the later ones were launched behind the frame before, into the set this frame now reads)
+    if (step.sort_front) RTK_TRY(launch_sort(a, fb, step.read_set, frame_mode, units, s));
+    if (step.use_order) { A.order_in = L.order; A.order_hdr = L.hdr; A.wg_list = L.wg_list; }
+    if (&fb == &a->fb) a->cnt.after_order(step);
     A.cost_out = fb.cost.get();
     return RTK_OK;
 }
@@ -399,8 +419,9 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
     const size_t units = A.regions ? size_t(A.n_units) : (A.views ? g.blocks() * A.n_views : g.blocks());
     A.n_units = uint32_t(units);
     const int frame_mode = OrderState::frame_mode(p->trace_mode, units, a->knobs.group8_below);
+    OrderState::Step step = {};
     if (a->knobs.cost_feedback && units > 0 && units <= 0x7FFFFFFFull) {
-        const int rc = order_launch(a, fb, p, g, A, frame_mode, units, s);
+        const int rc = order_launch(a, fb, p, g, A, frame_mode, units, s, step);
         if (rc != RTK_OK) { fb.forget(); return rc; }                     // (the state ran ahead of the launches)
     }
     unsigned n_wgs = 0;
@@ -409,8 +430,14 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
         if (fb.state.awaits_count() && !(ready = hipEventQuery(fb.nwgs_ev.get()) == hipSuccess)) (void)hipGetLastError();   // not ready: clear the sticky status
         n_wgs = fb.state.workgroups(ready, fb.nwgs_host.get());
     }
-    RTK_HIP_AS(launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs), "launch k_render");
-    return RTK_OK;
+    int rc = RTK_OK;
+    const hipError_t e = launch_render(A, frame_mode, p->collect_stats != 0, general, s, n_wgs);
+    if (e != hipSuccess) rc = hip_fail(e, "launch k_render");
+    // The next frame of this shape starts a new list: it is sorted here, behind this frame and from the costs it has just stored, into
+    // the set no frame reads (the pinned length is this frame's no more: it has been read above).
+    if (rc == RTK_OK && step.sort_behind) rc = launch_sort(a, fb, step.write_set, frame_mode, units, s);
+    if (rc != RTK_OK) fb.forget();
+    return rc;
 }
 
 // what every engine's launch arguments hold for a frame of shape `g` seen from `cam` into `d_out`
@@ -424,23 +451,27 @@ dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const
     A.bucket = g.bucket; A.tiles_x = g.tiles_x; A.tiles_y = g.tiles_y; A.n_buckets = g.n_buckets;
     A.blocks_per_bucket_side = g.blocks_side; A.buckets_per_rank = g.buckets_per_rank;
     A.rank = g.rank; A.world = g.world; A.compact = g.world > 1 ? 1 : 0; A.skew_q = g.skew_q;
-    A.out = d_out; A.counters = a->d_counters.get();
+    A.out = d_out; A.counters = counters_now(a);
     return A;
 }
 
-// One frame seen from `cam` (the accel's own camera, or a view of rtk_render_views' view-after-view path): the camera is part
-// of the launch arguments, so frames already enqueued keep theirs.
-int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out, hipStream_t s) {
-    dev::RenderArgs A = frame_args(a, p, g, cam, d_out);
+// `steady`: a frame of its own (not a view of a views call, whose counters are folded part by part): a megakernel frame without
+// statistics then counts into the block the frame before it cleared and clears the other one for the next (frame_plan.hpp CounterState).
+int render_frame_body(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out, hipStream_t s, bool steady) {
     // the megakernel comes in two builds: the lean one (diffuse / reflective / constant materials only) and the general one
     // (template FORKS: + refraction, diffuse GI, textures), so that the lean one does not carry the general one's registers
     const bool forks = scene_forks(a, p->diffuse_rays), general = scene_general(a, p->diffuse_rays);
-    RTK_HIP(zero_counters(a, s));
-    // buckets past the end of the frame (padding so that every rank has equal length) stay zero
-    if (g.world > 1 && g.sample_begin == 0) RTK_HIP(hipMemsetAsync(d_out, 0, out_pixels(g) * 3 * sizeof(float), s));
     bool stream = false;
     hipEvent_t trial[2] = {nullptr, nullptr};
     RTK_TRY(choose_engine(a, p, g, forks, stream, trial));
+    // The counters start at zero.  In the steady state no fill is issued for that: the blocks change places, and this frame's kernel
+    // clears the one the previous frame counted into.  Everything else fills the block in use, as every other user of the counters does.
+    const CounterState::Step cs = a->cnt.frame(s, steady && !stream && p->collect_stats == 0);
+    if (cs.fill) RTK_HIP(fill_counters(a, s));
+    dev::RenderArgs A = frame_args(a, p, g, cam, d_out);                 // (A.counters: the block in use, now that it is chosen)
+    if (cs.carry) A.zero_next = counters_other(a);
+    // buckets past the end of the frame (padding so that every rank has equal length) stay zero
+    if (g.world > 1 && g.sample_begin == 0) RTK_HIP(hipMemsetAsync(d_out, 0, out_pixels(g) * 3 * sizeof(float), s));
     // (the streaming pipeline starts its trial itself, behind its workspace allocation)
     if (trial[0] && !stream) RTK_HIP(hipEventRecord(trial[0], s));
     // (the retired two-pass engine's mode keeps its refusal; its frames are GROUP4's: frame_plan.hpp OrderState::frame_mode)
@@ -452,11 +483,19 @@ int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
     return RTK_OK;
 }
 
+// One frame seen from `cam` (the accel's own camera, or a view of rtk_render_views' view-after-view path): the camera is part
+// of the launch arguments, so frames already enqueued keep theirs.
+int render_frame_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out, hipStream_t s, bool steady) {
+    const int rc = render_frame_body(a, p, g, cam, d_out, s, steady);
+    if (rc != RTK_OK) a->cnt.forget();                                   // (the state ran ahead of the launches)
+    return rc;
+}
+
 int render_device_impl(rtk_accel *a, const rtk_render_params *p, float *d_out, hipStream_t s) {
     FrameGeom g;
     RTK_TRY(frame_geom(a, p, g));
     if (!d_out) return fail(RTK_ERR_INVALID, "null output buffer");
-    return render_frame_impl(a, p, g, accel_camera(a), d_out, s);
+    return render_frame_impl(a, p, g, accel_camera(a), d_out, s, true);
 }
 
 // ---------------------------------------------------------------- rtk_render_views
@@ -496,9 +535,9 @@ struct CallCounters {
         return RTK_OK;
     }
     int zero_part() { RTK_HIP(zero_counters(a, s)); return RTK_OK; }   // (a frame zeroes its own)
-    int after_part() { if (many) RTK_HIP_AS(launch_counters_fold(a->d_counters.get(), a->d_views_counters.get(), s), "launch k_counters_fold"); return RTK_OK; }
+    int after_part() { if (many) RTK_HIP_AS(launch_counters_fold(counters_now(a), a->d_views_counters.get(), s), "launch k_counters_fold"); return RTK_OK; }
     int end() {
-        if (many) RTK_HIP(hipMemcpyAsync(a->d_counters.get(), a->d_views_counters.get(), kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        if (many) RTK_HIP(hipMemcpyAsync(counters_now(a), a->d_views_counters.get(), kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
         return RTK_OK;
     }
 };
@@ -548,7 +587,7 @@ int render_views_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeom 
         CallCounters cc{a, n > 1, s};
         RTK_TRY(cc.begin());
         for (size_t v = 0; v < n; ++v) {
-            RTK_TRY(render_frame_impl(a, p, g, h_views[v], d_out + v * stride, s));
+            RTK_TRY(render_frame_impl(a, p, g, h_views[v], d_out + v * stride, s, false));
             RTK_TRY(cc.after_part());
         }
         RTK_TRY(cc.end());
@@ -576,6 +615,7 @@ int radiance_check(const rtk_accel *a, const void *rays, const void *ids, size_t
 // lanes, followed by its counter fold and its overflow fallback.  Nothing here waits on the host.
 int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
                          float *d_rgb, hipStream_t s, uint32_t *n_chunks_out) {
+    a->cnt.forget();                                     // (no steady frame: frame_plan.hpp CounterState)
     dev::RenderArgs A = scene_args(a, 0);
     // one colour per ray: "sample 0 of 1" for k_combine, whatever sample the RNG keys name
     A.spp = 1; A.sample_begin = 0; A.sample_end = 1; A.spp_f = 1.0f;
@@ -720,7 +760,7 @@ int render_regions_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
                     RTK_HIP_AS(launch_region_rays(A, smp, first, cn, a->rg_rays.get(), a->rg_ids.get(), s), "launch k_region_rays");
                     rp.sample = smp;
                     RTK_TRY(radiance_device_impl(a, a->rg_rays.get(), a->rg_ids.get(), cn, &rp, a->rg_rgb.get(), s, nullptr));
-                    RTK_HIP_AS(launch_add_word(a->d_counters.get(), a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes) + kRadianceRays, s), "launch k_add_word");
+                    RTK_HIP_AS(launch_add_word(counters_now(a), a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes) + kRadianceRays, s), "launch k_add_word");
                     RTK_HIP_AS(launch_region_accumulate(A, first, cn, a->rg_rgb.get(), smp == 0, p->spp != 1 && smp + 1 == p->spp, s), "launch k_region_accumulate");
                 }
             }
@@ -765,7 +805,7 @@ int rtk_render_last_counters(rtk_accel *a, rtk_counters *c) {
         RTK_HIP(hipSetDevice(a->device));
         RTK_HIP(hipStreamSynchronize(a->last_stream));
         unsigned long long h[kCounterWords];
-        RTK_HIP(hipMemcpy(h, a->d_counters.get(), sizeof(h), hipMemcpyDeviceToHost));
+        RTK_HIP(hipMemcpy(h, counters_now(a), sizeof(h), hipMemcpyDeviceToHost));
         counters_from_block(h, a->last_stats, c);
         for (int i = 0; i < kRayCounterShards; ++i) c->rays += h[kRayShardWord + i];      // the frame kernel shards its ray counter
         c->primary = a->last_primary;
@@ -781,9 +821,18 @@ int rtk_render_last_critical_path(rtk_accel *a, double *ms) {
         RTK_HIP(hipSetDevice(a->device));
         RTK_HIP(hipStreamSynchronize(a->last_stream));
         unsigned long long shard[kRayCounterShards], ticks = 0;
-        RTK_HIP(hipMemcpy(shard, a->d_counters.get() + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
+        RTK_HIP(hipMemcpy(shard, counters_now(a) + kCriticalWord, sizeof(shard), hipMemcpyDeviceToHost));
         for (unsigned long long t : shard) ticks = t > ticks ? t : ticks;
         *ms = double(ticks) * 1.0e-5;                                        // s_memrealtime counts at 100 MHz; 0 = no block took 10 us
+        return RTK_OK;
+    });
+}
+
+int rtk_debug_counter_fills(rtk_accel *a, uint64_t *fills) {
+    return abi_guard([&]() -> int {
+        if (!a || !fills) return fail(RTK_ERR_INVALID, "null accel or fills");
+        std::lock_guard<std::mutex> lock(a->mu);
+        *fills = a->counter_fills;
         return RTK_OK;
     });
 }

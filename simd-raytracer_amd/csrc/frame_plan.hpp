@@ -62,7 +62,10 @@ struct EngineTrial {
 // The HIP-free half of a set of cost-feedback tables (rtk_cost_feedback): what they hold and how old it is.
 struct OrderState {
     struct Knobs { bool first_frame_prior; unsigned resort_every; };
-    struct Step { bool prior, resort, use_order; };    // launch k_block_prior / k_order_by_cost; give the kernel the tables' order
+    // prior: launch k_block_prior (into set 0).  resort: this frame is the first of a new list -- k_order_by_cost is launched in front of
+    // it into read_set (sort_front), unless the frame before launched it behind itself.  use_order: give the kernel set read_set's lists.
+    // sort_behind: the next frame of this shape starts a new list: launch k_order_by_cost behind this frame's kernel, into write_set.
+    struct Step { bool prior, resort, use_order, sort_front, sort_behind; int read_set, write_set; };
     size_t units = 0;                  // capacity of the tables, never shrunk
     uint64_t sig[5] = {0, 0, 0, 0, 0};
     bool valid = false;                // cost holds the costs of a frame of shape sig
@@ -70,8 +73,14 @@ struct OrderState {
     unsigned age = 0;                  // frames rendered with the current order
     // the number of workgroups in order's workgroup list is read back behind the sort that made it
     bool nwgs_pending = false, nwgs_known = false;
+    // The tables hold two sets of lists (order, header, workgroup list).  A re-sort is launched behind the last frame of the old list,
+    // from the costs that frame has just stored, into the set no frame reads; the frame after it changes sets.  It then sits behind a
+    // frame instead of in front of one (same stream, same ~50 us every resort_every frames: a caller that looks at a frame as soon as
+    // its kernel is done no longer waits for a sort first).  Only a shape's first sort, which has no list to go on with, is in front.
+    int set = 0;                       // the set the frames read
+    bool presorted = false;            // the other set's list was launched behind the previous frame
 
-    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; }
+    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; set = 0; presorted = false; }
 
     // RTK_TRACE_AUTO for the megakernel: four waves per pixel block when there are enough blocks to fill the chip several times
     // over, eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
@@ -98,19 +107,28 @@ struct OrderState {
     // One frame of shape `s`.  The first frame of a shape has no costs to go by: a prior from the camera rays alone stands in
     // for them (GROUP4 only; not with per-ray statistics; a new rectangle list runs in the natural order, k_block_prior maps
     // units through the buckets).  From the second on the order comes from the newest costs, refreshed every few frames only:
-    // the sort is one small workgroup whose ~28 us sit in front of the frame, and an order a few frames old is as good.
+    // the sort is one small workgroup whose ~50 us sit between two frames, and an order a few frames old is as good.  A re-sort
+    // is launched behind the last frame of the old list into the other set of lists (sort_behind), a shape's first sort in front.
     // A caller whose launches then fail calls forget().
     Step step(const uint64_t s[5], int mode, bool stats, bool regions, const Knobs &k) {
         const bool same_shape = valid && std::memcmp(s, sig, sizeof(sig)) == 0;
-        if (!same_shape) order_valid = false;
-        Step r = {!same_shape && k.first_frame_prior && mode == RTK_TRACE_GROUP4 && !stats && !regions, false, false};
+        if (!same_shape) { order_valid = false; set = 0; presorted = false; }
+        Step r = {!same_shape && k.first_frame_prior && mode == RTK_TRACE_GROUP4 && !stats && !regions, false, false, false, false, 0, 0};
         if (same_shape) {
             r.resort = !order_valid || age >= k.resort_every;
             // (how many workgroups the new list has is known on the host a frame or two later)
-            if (r.resort) { order_valid = true; age = 0; nwgs_known = false; nwgs_pending = true; }
+            if (r.resort) {
+                r.sort_front = !presorted;
+                if (presorted) set ^= 1;
+                presorted = false;
+                order_valid = true; age = 0; nwgs_known = false; nwgs_pending = true;
+            }
             age += 1;
+            r.sort_behind = age >= k.resort_every;      // (the next frame of this shape re-sorts: its list is made behind this one)
+            presorted = r.sort_behind;
         }
         r.use_order = r.prior || same_shape;
+        r.read_set = set; r.write_set = set ^ 1;
         std::memcpy(sig, s, sizeof(sig));
         valid = true;
         return r;
@@ -124,6 +142,33 @@ struct OrderState {
         if (!order_valid) return 0;
         if (nwgs_pending && ready) { nwgs_pending = false; nwgs_known = true; }
         return nwgs_known && !nwgs_pending ? *host_word : 0;
+    }
+};
+
+// The HIP-free half of an accel's two counter blocks (counters.hpp; rtk_accel::d_counters).  A megakernel frame without per-ray
+// statistics counts into the current block and its workgroup 0 clears the other one (RenderArgs::zero_next), so the next such frame
+// on the same stream finds a zeroed block waiting: it flips the blocks and issues no fill.  What is held: which block is current,
+// and whether the other one is known to be zero behind everything enqueued on `stream`.  Every other user of the counters (the
+// streaming engine, views, regions, statistics, the batches) fills and uses the current block itself and calls forget(), as does a
+// failed call and whatever resets the launch orders (accel.hpp forget_orders): the next frame then fills again.
+// A stream is known by its handle: a caller that destroys a stream and creates another must not count on the accel telling them
+// apart (rtk.h, rtk_render_frame_device).
+// (tests/cpp/counter_state_check.cpp pins the sequences; tests/test_gpu_steady_frames.py renders them.)
+struct CounterState {
+    struct Step { int current; bool fill, carry; };    // the block to count into; fill it with zeros first; hand the kernel the other one to clear
+    int current = 0;
+    bool other_zero = false;
+    const void *stream = nullptr;
+
+    void forget() { other_zero = false; }
+    // behind the order step of a frame's own tables: a frame of a new shape starts the order over, and the counter blocks with it
+    void after_order(const OrderState::Step &st) { if (st.prior || !st.use_order) forget(); }
+    // One frame on stream `s`.  `carries`: its launch clears the other block (a megakernel frame, no statistics, no only_if).
+    Step frame(const void *s, bool carries) {
+        const bool flip = carries && other_zero && stream == s;
+        if (flip) current ^= 1;
+        other_zero = carries; stream = s;
+        return {current, !flip, carries};
     }
 };
 

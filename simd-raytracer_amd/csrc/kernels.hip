@@ -192,6 +192,8 @@ template <int MODE, bool STATS, bool FORKS, bool LDS_NODES, int SLICES, bool VIE
 __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : SLICES == 8 ? 2 : (SLICES == 4 && !STATS ? RTK_G4_WAVES : 4)) void k_render(RenderArgs A) {
     FrameProbe phases = FrameProbe::enter();                     // diagnostic build only (phases.hip.hpp); empty in the product
     if (A.only_if != nullptr && *A.only_if == 0u) return;        // fallback launch behind the streaming pipeline: nothing overflowed
+    // the counters of the NEXT frame start at zero: nothing else touches that block while this launch runs (frame_plan.hpp CounterState)
+    if (A.zero_next != nullptr && blockIdx.x == 0u && threadIdx.x < (uint32_t)kCounterAllocWords) A.zero_next[threadIdx.x] = 0ull;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     DevNode *lds_nodes = reinterpret_cast<DevNode *>(smem);
     // the per-lane path reads nodes from LDS; the wave-cooperative paths fetch them with scalar loads instead

@@ -81,10 +81,13 @@ struct RenderArgs {
     int compact;                      // 1: out is [buckets_per_rank][bucket][bucket][3]; 0: out is [h][w][3]
     float *out;
     unsigned long long *counters;
+    // Non-null (a megakernel frame without statistics, api_frame.hip): the accel's other counter block, kCounterAllocWords words that
+    // workgroup 0 of k_render stores zeros to, so that the next frame counts into it without a fill in front (frame_plan.hpp CounterState).
+    unsigned long long *zero_next;
     // Never read or written.  It keeps the fields below at the kernel-argument offsets the kernels were tuned at: with them 48 bytes
     // lower the compiler schedules the scalar loads of the arguments differently, and 17 k_render builds (the benchmark's among them)
-    // move by 1 to 3 instructions.  With the pad every kernel's instruction stream is the one it had before the fields here went.
-    unsigned long long keep_offsets_[6];
+    // move by 1 to 3 instructions.  With the pad (zero_next took its first word) every field below stays where it was.
+    unsigned long long keep_offsets_[5];
     const uint32_t *only_if;          // non-null: the kernel does nothing unless this word is non-zero (overflow fallback)
     // frame-to-frame scheduling feedback (api_frame.hip render_megakernel): every pixel block reports what it cost; the next
     // frame of the same shape starts its blocks most-expensive-first (results do not depend on the order)

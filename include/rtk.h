@@ -524,6 +524,53 @@ int rtk_render_regions(rtk_accel *accel, const rtk_render_params *p, const rtk_r
 int rtk_render_regions_device(rtk_accel *accel, const rtk_render_params *p, const rtk_rect *rects /* HOST */, int32_t n_rects,
                               int layout, float *d_out /* device */, void *hip_stream);
 
+/* ---- what the camera rays hit: first-hit depth, position, normal, albedo, barycentrics and ids as planes ----
+ * hit<F> (render/hit.hpp:9-21) of `accel.template intersect<true>(ray)` for the camera ray of every pixel (render/render.hpp:35-64),
+ * written field by field into separate arrays, for n_views cameras in one launch: what a depth map, a denoiser's feature
+ * buffers or an id mask need, without the detour over 24 B of ray and 32 B of rtk_hit per pixel.
+ * Contract, per pixel (px, py) of view v: r = the ray rtk_camera_rays(.., sample) gives for that pixel after
+ * rtk_accel_set_camera(views[v]) -- pixel centres at spp == 1, otherwise the jitter of root key (seed, py * width + px inside the
+ * view, sample) -- and h = intersect<cull = true>(r).  Every plane but `albedo` holds, bit for bit, the corresponding field of
+ * rtk_accel_intersect(cull = 1) on those rays (`position` = r.origin + (h.t * r.direction) in float, kd_tree_simd.hpp:254; `material`
+ * = the material index of h.mesh), and on a miss what rtk_accel_intersect writes there.  `albedo` on a hit: for a material of kind
+ * RTK_MAT_TEXTURE sample(texture, hit, uvs), the very value color_hit multiplies the light into (render.hpp:234-235); for every
+ * other kind the material's `albedo` as rtk_accel_get_materials returns it.
+ * First hit only and ONE sample per call: the caller averages or picks.  Nothing behind the first hit (no reflection, no
+ * refraction), no rectangles inside the call, one size for all views, no sharding (world_size > 1 is refused: deal whole views to
+ * ranks), no counters.
+ * The call reads the live state -- camera, geometry after rtk_accel_update_*, materials, textures, texels, uvs, background -- and
+ * changes none of: the accel's camera, the cost-feedback launch orders, RTK_TRACE_AUTO's verdict, the frame counters
+ * (rtk_render_last_counters, rtk_debug_counter_fills and the counter block a steady frame relies on).
+ * On an RTK_TRAVERSAL_FAST accel `depth` and the hit / miss pattern are those of the parity mode; the other planes carry the tie
+ * caveat of RTK_TRAVERSAL_FAST above (the leaf order is chosen per wave, and a wave here is an 8x8 pixel block of a view).
+ * What runs: one kernel (csrc/gbuffer.hip), one wave per 8x8 pixel block of a view, the blocks anchored at the view's corner; a
+ * wave none of whose rays enters the tree's root box writes its miss values and ends.  Only the planes asked for are written.  A
+ * call of more than 2^30 blocks is cut into launches of whole views.
+ * trace_mode, max_ray_depth, diffuse_rays, the biases, sample_begin and sample_count of *p are validated as a frame validates them
+ * and otherwise not consulted.
+ * Errors, in this order: a NULL accel, p or out; what rtk_render_frame refuses for *p; sample outside [0, spp); world_size > 1,
+ * collect_stats != 0, n_views < 0; NULL views with n_views != 1; all eight planes NULL; more than 2^56 pixels -> RTK_ERR_INVALID.
+ * Then n_views == 0 -> RTK_OK, nothing touched, device or not.  Then (device variant) a plane pointer or view table that is not 4-byte
+ * aligned -> RTK_ERR_INVALID.  Then RTK_ERR_NO_DEVICE.
+ * The device variant is stream-ordered, waits (on the device) for the geometry of the last update like every other entry point,
+ * allocates nothing and never blocks the host once the accel is resident.  Stream capture is neither claimed nor tested.  The
+ * host variant stages views and planes in buffers the accel owns (they grow with head room and never shrink) and is synchronous. */
+typedef struct {            /* any pointer may be NULL = plane not wanted; at least one must be set.  [n_views][h][w] each */
+    float    *depth;        /* hit<F>::t of the camera ray (ray parameter; the camera rays are unit length); miss: -1 */
+    float    *position;     /* [..][3] ray.origin + (t * ray.direction), kd_tree_simd.hpp:254; miss: 0 0 0 */
+    float    *normal;       /* [..][3] hit<F>::hit_normal exactly as rtk_hit.normal (normalize_hit_normal honoured); miss: 0 0 0 */
+    float    *albedo;       /* [..][3] see above; miss: the accel's background */
+    float    *bary;         /* [..][2] u, v; miss: 0 0 */
+    uint32_t *tri, *mesh, *material;   /* rtk_hit.tri / .mesh, and the mesh's material index; miss: 0xFFFFFFFF */
+} rtk_gbuffer;              /* 64 bytes */
+
+int rtk_render_gbuffer(rtk_accel *accel, const rtk_render_params *p, int32_t sample,
+                       const rtk_view *views /* host; NULL = the accel's camera, n_views must be 1 */, int32_t n_views,
+                       const rtk_gbuffer *out /* host planes */);
+int rtk_render_gbuffer_device(rtk_accel *accel, const rtk_render_params *p, int32_t sample,
+                              const rtk_view *d_views /* DEVICE, 4-byte aligned; NULL as above */, int32_t n_views,
+                              const rtk_gbuffer *out /* struct on the HOST, DEVICE plane pointers, 4-byte aligned */, void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_render_regions", "rtk_render_regions_device",
+    "rtk_render_gbuffer", "rtk_render_gbuffer_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
@@ -138,6 +139,16 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class GBuffer(C.Structure):
+    """rtk.h rtk_gbuffer: one pointer per plane, NULL = plane not wanted; 64 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "albedo", "bary", "tri", "mesh", "material")]
+
+
+# the planes of a g-buffer in the struct's order: name -> (trailing shape, dtype); miss values in rtk.h
+GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
+                  "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
+                  "material": ((), np.uint32)}
+
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,))])
 LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("intensity", "<f4")])                     # rtk.h rtk_light
 MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("smooth", "<i4"), ("albedo", "<f4", (3,)), ("ior", "<f4"), ("texture", "<i4"),
@@ -194,7 +205,9 @@ _L.rtk_render_views.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _v
 _L.rtk_render_views_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, _vp, _vp]
 _L.rtk_render_regions.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, C.POINTER(Counters)]
 _L.rtk_render_regions_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, _vp]
-_L.rtk_accel_get_lights.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+_L.rtk_render_gbuffer.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer)]
+_L.rtk_render_gbuffer_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer), _vp]
+_L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
 _L.rtk_accel_get_materials.argtypes = [_vp, _vp]
@@ -697,6 +710,46 @@ class KdTreeSimdAccel:
         p = cfg.to_c()
         _check(_L.rtk_render_regions_device(self._h, C.byref(p), arr.ctypes.data if arr.shape[0] else None, arr.shape[0], layout,
                                             d_out_ptr or None, stream))
+
+    # ---- what the camera rays hit, as planes (rtk.h rtk_gbuffer)
+    def render_gbuffer(self, cfg: RenderConfig, sample: int = 0, views: np.ndarray | None = None,
+                       planes=tuple(GBUFFER_PLANES)) -> dict:
+        """First hit of every pixel's camera ray at sample `sample`: {plane name: array [K, h, w(, c)]} for the planes asked for.
+        views: [K, 12] float32 (position, matrix), or None for the accel's own camera (K = 1).  Every plane but `albedo` holds the
+        bits of camera_rays + intersect(cull=True); the accel's camera, launch orders and counters stay as they are."""
+        unknown = [n for n in planes if n not in GBUFFER_PLANES]
+        if unknown:
+            raise ValueError(f"unknown g-buffer planes {unknown}: choose from {list(GBUFFER_PLANES)}")
+        if views is None:
+            k, vptr = 1, None
+        else:
+            views = np.asarray(views)
+            if views.dtype != np.float32 or views.ndim != 2 or views.shape[1] != 12:
+                raise ValueError("views must be float32 of shape (K, 12)")
+            views = np.ascontiguousarray(views)
+            k = views.shape[0]
+            if k == 0:
+                views = np.zeros((1, 12), np.float32)               # (no views: a valid pointer nothing is read through)
+            vptr = views.ctypes.data
+        w = cfg.width or self.scene.info.width
+        h = cfg.height or self.scene.info.height
+        out = {n: np.zeros((k, h, w) + GBUFFER_PLANES[n][0], GBUFFER_PLANES[n][1]) for n in GBUFFER_PLANES if n in planes}
+        spare = np.zeros(1, np.uint32)                              # (likewise for planes without pixels)
+        gb = GBuffer(**{n: a.ctypes.data if a.size else spare.ctypes.data for n, a in out.items()})
+        p = cfg.to_c()
+        _check(_L.rtk_render_gbuffer(self._h, C.byref(p), sample, vptr, k, C.byref(gb)))
+        return out
+
+    def render_gbuffer_device(self, cfg: RenderConfig, planes: dict, sample: int = 0, d_views_ptr: int = 0, n_views: int = 1,
+                              stream: int = 0) -> None:
+        """planes: {plane name: device pointer} of float32 / uint32 arrays [n_views, h, w(, c)], 4-byte aligned; d_views_ptr: device
+        float32 [n_views, 12], or 0 for the accel's own camera (n_views = 1); stream-ordered, allocates nothing (rtk.h)."""
+        unknown = [n for n in planes if n not in GBUFFER_PLANES]
+        if unknown:
+            raise ValueError(f"unknown g-buffer planes {unknown}: choose from {list(GBUFFER_PLANES)}")
+        gb = GBuffer(**{n: (int(ptr) or None) for n, ptr in planes.items()})
+        p = cfg.to_c()
+        _check(_L.rtk_render_gbuffer_device(self._h, C.byref(p), sample, d_views_ptr or None, n_views, C.byref(gb), stream))
 
     # ---- lights, materials and background of a live accel (rtk.h rtk_light, rtk_material)
     def lights(self):

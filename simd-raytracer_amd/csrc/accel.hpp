@@ -291,6 +291,9 @@ struct rtk_accel {
     rtk::DevBuf<uint32_t> rg_ids;
     rtk::DevBuf<float> rg_rgb;
     rtk::DevBuf<float> rg_out;                 // staging of the host variant
+    // ---- gb_*: staging of the host variant of rtk_render_gbuffer (api_gbuffer.hip): grows with head room, never shrinks
+    rtk::DevBuf<rtk_view> gb_views;
+    rtk::DevBuf<uint32_t> gb_out;              // the wanted planes one behind the other, dwords
     // ---- trial*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     rtk::TimedEvent trial_ev[4];
     rtk::EngineTrial trial;
@@ -443,6 +446,8 @@ const std::vector<float> &host_vert_uv(rtk_accel *a);
 int ensure_vert_uv_dev(rtk_accel *a);
 // api_frame.hip
 int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g);
+rtk_view accel_camera(const rtk_accel *a);                                                       // the camera later frames are rendered from
+void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A);   // the camera half of the launch arguments
 int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes);
 void free_stream_ws(rtk_accel *a);
 

@@ -186,6 +186,9 @@ void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary) {
     a->last_primary = primary;
 }
 
+}  // namespace
+
+// (these two are api_gbuffer.hip's as well: accel.hpp)
 // the accel's own camera: the scene's at rtk_accel_build, then whatever rtk_accel_set_camera stored there
 rtk_view accel_camera(const rtk_accel *a) {
     rtk_view v;
@@ -208,6 +211,8 @@ void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeo
     A.spp = p->spp; A.seed = p->seed;
     A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height); A.spp_f = static_cast<float>(p->spp);
 }
+
+namespace {
 
 // ---------------------------------------------------------------- the streaming pipeline's setup, for both of its clients
 

@@ -417,6 +417,44 @@ struct hip_accel {
         return out;
     }
 
+    // What the camera rays hit, as planes (rtk_render_gbuffer): hit<F> of intersect<true>(camera ray of `sample`) for every pixel of
+    // every view, field by field.  `planes`: the gbuffer_* bits wanted; a plane that is not wanted stays empty.  Every plane is
+    // [views][height][width] flattened (x fastest), position / normal / albedo with 3 and bary with 2 floats per pixel.  No views =
+    // the accel's own camera (one view).  A miss: depth -1, ids 0xFFFFFFFF, albedo the background, zeros elsewhere.
+    enum : unsigned {
+        gbuffer_depth = 1u, gbuffer_position = 2u, gbuffer_normal = 4u, gbuffer_albedo = 8u, gbuffer_bary = 16u, gbuffer_tri = 32u,
+        gbuffer_mesh = 64u, gbuffer_material = 128u, gbuffer_all = 255u
+    };
+    struct gbuffer_result {
+        std::size_t views = 0, width = 0, height = 0;
+        std::vector<float> depth, position, normal, albedo, bary;
+        std::vector<std::uint32_t> tri, mesh, material;
+    };
+    [[nodiscard]] gbuffer_result render_gbuffer(const rtk_render_params &params, std::int32_t sample, std::span<const camera<F>> views,
+                                                unsigned planes = gbuffer_all) const {
+        std::size_t n = 0;
+        check(rtk_render_output_floats(accel_.get(), &params, &n));
+        gbuffer_result r;
+        r.views = views.empty() ? 1 : views.size();
+        r.width = params.width > 0 ? static_cast<std::size_t>(params.width) : scene_ptr->config.image_width;
+        r.height = n / 3 / r.width;
+        const std::size_t pixels = r.views * r.width * r.height;
+        rtk_gbuffer out{};
+        const auto want = [&](unsigned bit, auto &plane, std::size_t comps) {
+            if (planes & bit) plane.resize(pixels * comps + 1);              // (+ 1: a valid pointer for a call without pixels)
+            return (planes & bit) ? plane.data() : nullptr;
+        };
+        out.depth = want(gbuffer_depth, r.depth, 1); out.position = want(gbuffer_position, r.position, 3);
+        out.normal = want(gbuffer_normal, r.normal, 3); out.albedo = want(gbuffer_albedo, r.albedo, 3); out.bary = want(gbuffer_bary, r.bary, 2);
+        out.tri = want(gbuffer_tri, r.tri, 1); out.mesh = want(gbuffer_mesh, r.mesh, 1); out.material = want(gbuffer_material, r.material, 1);
+        std::vector<rtk_view> in(views.size());
+        for (std::size_t v = 0; v < views.size(); ++v) in[v] = to_view(views[v]);
+        check(rtk_render_gbuffer(accel_.get(), &params, sample, in.empty() ? nullptr : in.data(), static_cast<std::int32_t>(r.views), &out));
+        const auto trim = [&](auto &plane, std::size_t comps) { if (!plane.empty()) plane.resize(pixels * comps); };
+        trim(r.depth, 1); trim(r.position, 3); trim(r.normal, 3); trim(r.albedo, 3); trim(r.bary, 2); trim(r.tri, 1); trim(r.mesh, 1); trim(r.material, 1);
+        return r;
+    }
+
     // Rectangles of the frame `params` describes, all in one call (rtk_render_regions).  Tile: anything with x0, y0, x1, y1 --
     // the reference's render_tile (render/tile/tile.hpp), what its single / region / bucket schedulers hand to tile_worker, or
     // rtk_rect.  Every pixel is what render_frame(params) gives there; counters: the call's totals.

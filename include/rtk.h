@@ -571,6 +571,51 @@ int rtk_render_gbuffer_device(rtk_accel *accel, const rtk_render_params *p, int3
                               const rtk_view *d_views /* DEVICE, 4-byte aligned; NULL as above */, int32_t n_views,
                               const rtk_gbuffer *out /* struct on the HOST, DEVICE plane pointers, 4-byte aligned */, void *hip_stream);
 
+/* ---- a frame whose pixel blocks stop sampling once they have converged ----
+ * The sample loop of tile_worker (render/render.hpp:30-77: for every pixel, for sample in [0, samples_per_pixel): camera ray,
+ * intersect, color_hit, pixel_sum += colour; then pixel_sum / samples_per_pixel) cut short per 8x8 pixel block of the frame's own
+ * grid (edge blocks are partial).  p->spp is the ceiling.  Blocks are judged at the checkpoints min_samples, min_samples + step,
+ * ..., and spp itself as the last one (the last round may be shorter than step).
+ * Contract:
+ *  1. samples[px] is one of the checkpoints and equal over a block.  rgb[px] is, bit for bit, the pixel rtk_render_frame leaves
+ *     with the same parameters and spp = samples[px] (a sample's jitter and RNG keys depend on the seed, the pixel index and the
+ *     sample, not on spp, for spp >= 2; the sum is kept in sample order and divided by float(samples[px])).  This holds against
+ *     any engine and is claimed for RTK_TRAVERSAL_REFERENCE accels; RTK_TRAVERSAL_FAST accels carry the tie caveat that
+ *     rtk_accel_radiance states.
+ *  2. counters.rays is the sum, over the checkpoints n, of what rtk_render_regions(spp = n, RTK_TRACE_STREAM) reports for the
+ *     blocks that ended at n; counters.primary is the sum of samples[px].  rtk_render_last_counters reports the call (the call
+ *     fills the accel's counter block as a regions call does; rtk_render_last_critical_path reports 0 for it).
+ *  3. The statistic.  Per sample colour c: y = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b in float, without contraction.  Per
+ *     pixel, in double and in sample order: S1 += (double)y, S2 += (double)y * (double)y.  At a checkpoint n, for every valid pixel
+ *     i of block B in row-major order, all in double: m_i = S1 / n, v_i = max(0, (S2 - S1 * S1 / n) / (n - 1)) / n, e_i = sqrt(v_i),
+ *     and E_B = (sum e_i / |B|) / max(sum m_i / |B|, (double)floor).  The block stops iff E_B <= (double)threshold evaluates true; a
+ *     NaN keeps sampling to the ceiling (both max() pass a NaN on).  noise[px] = (float)e_i at the pixel's final count.
+ *  4. The call reads the live state -- camera, updated geometry, lights, materials, textures, background -- and leaves alone the
+ *     accel's camera, the cost tables of frames, views and regions, the regions table and RTK_TRACE_AUTO's verdict.
+ * What runs (csrc/adaptive.hip): round by round, the active pixels in chunks of at most 2^20 (RTK_ADAPTIVE_CHUNK_PIXELS), per
+ * chunk and sample the camera rays, the streaming pipeline of rtk_accel_radiance and a kernel that adds the colours into the sums
+ * and the statistic; at the checkpoint one wave per active block decides.  The order of the blocks in a later round's list is not
+ * deterministic; no result depends on it.  The workspace (24 B per pixel) belongs to the accel and grows with head room.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL accel, p, ap or rgb; what rtk_render_frame refuses for *p; trace_mode other
+ * than RTK_TRACE_AUTO or RTK_TRACE_STREAM; spp < 2; sample_begin or sample_count not 0; collect_stats != 0; world_size > 1;
+ * min_samples < 2 or > spp; step < 1; a threshold that is non-finite or negative; a floor that is non-finite or not positive; a
+ * frame of more than 2^31 pixels.  Then RTK_ERR_NO_DEVICE.  A refused call leaves the accel unchanged and usable.
+ * The device variant is stream-ordered: everything is enqueued on hip_stream.  It BLOCKS THE HOST once per round but the last, to
+ * read back one 64-bit word (the pixels and blocks still active), and may block again, once, to grow the workspace.  It is NOT
+ * stream-capturable.  d_samples and d_noise may be NULL.  Resuming an earlier adaptive render with a higher ceiling is not offered. */
+typedef struct {
+    int32_t min_samples;   /* >= 2: every pixel gets at least this many */
+    int32_t step;          /* >= 1: samples per round after the first */
+    float   threshold;     /* finite, >= 0: a block stops once E_B <= threshold */
+    float   floor;         /* finite, > 0: lower bound of the block mean in E_B's denominator */
+} rtk_adaptive_params;     /* 16 bytes */
+
+int rtk_render_adaptive(rtk_accel *accel, const rtk_render_params *p, const rtk_adaptive_params *ap,
+                        float *rgb /* host [h][w][3] */, uint32_t *samples /* host [h][w], may be NULL */,
+                        float *noise /* host [h][w], may be NULL */, rtk_counters *counters /* may be NULL */);
+int rtk_render_adaptive_device(rtk_accel *accel, const rtk_render_params *p, const rtk_adaptive_params *ap,
+                               float *d_rgb, uint32_t *d_samples, float *d_noise, void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

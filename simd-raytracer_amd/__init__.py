@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_render_regions", "rtk_render_regions_device",
     "rtk_render_gbuffer", "rtk_render_gbuffer_device",
+    "rtk_render_adaptive", "rtk_render_adaptive_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
@@ -144,6 +145,11 @@ class GBuffer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "albedo", "bary", "tri", "mesh", "material")]
 
 
+class AdaptiveParams(C.Structure):
+    """rtk.h rtk_adaptive_params; 16 bytes."""
+    _fields_ = [("min_samples", C.c_int32), ("step", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
 # the planes of a g-buffer in the struct's order: name -> (trailing shape, dtype); miss values in rtk.h
 GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
@@ -207,6 +213,8 @@ _L.rtk_render_regions.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, 
 _L.rtk_render_regions_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, _vp]
 _L.rtk_render_gbuffer.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer)]
 _L.rtk_render_gbuffer_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer), _vp]
+_L.rtk_render_adaptive.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, C.POINTER(Counters)]
+_L.rtk_render_adaptive_device.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp]
 _L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
@@ -390,6 +398,18 @@ class RenderConfig:
                             self.fov_degrees, np.float32(self.shadow_bias), np.float32(self.reflection_bias),
                             np.float32(self.refraction_bias), self.trace_mode, self.rank, self.world_size,
                             int(self.collect_stats), self.sample_begin, self.sample_count)
+
+
+@dataclass
+class AdaptiveConfig:
+    """rtk.h rtk_adaptive_params: when the 8x8 pixel blocks of render_adaptive stop taking samples (cfg.spp is the ceiling)."""
+    min_samples: int = 16      # >= 2: every pixel gets at least this many
+    step: int = 16             # >= 1: samples per round after the first
+    threshold: float = 0.02    # a block stops once its noise estimate E_B <= threshold
+    floor: float = 0.01        # lower bound of the block's mean luminance in E_B's denominator
+
+    def to_c(self) -> AdaptiveParams:
+        return AdaptiveParams(self.min_samples, self.step, np.float32(self.threshold), np.float32(self.floor))
 
 
 @dataclass(frozen=True)
@@ -750,6 +770,29 @@ class KdTreeSimdAccel:
         gb = GBuffer(**{n: (int(ptr) or None) for n, ptr in planes.items()})
         p = cfg.to_c()
         _check(_L.rtk_render_gbuffer_device(self._h, C.byref(p), sample, d_views_ptr or None, n_views, C.byref(gb), stream))
+
+    # ---- a frame whose pixel blocks stop sampling once they have converged (rtk.h rtk_adaptive_params)
+    def render_adaptive(self, cfg: RenderConfig, adaptive: AdaptiveConfig):
+        """-> (rgb [h, w, 3] float32, samples [h, w] uint32, noise [h, w] float32, counters).  Every pixel is, bit for bit, the pixel
+        of render_frame(cfg with spp = samples[pixel]); samples is constant over an 8x8 block; noise is the standard error of the
+        pixel's mean luminance at its final count (the statistic is spelt out in rtk.h)."""
+        w = cfg.width or self.scene.info.width
+        h = cfg.height or self.scene.info.height
+        rgb = np.zeros((h, w, 3), np.float32)
+        samples = np.zeros((h, w), np.uint32)
+        noise = np.zeros((h, w), np.float32)
+        p, ap = cfg.to_c(), adaptive.to_c()
+        c = Counters()
+        _check(_L.rtk_render_adaptive(self._h, C.byref(p), C.byref(ap), rgb.ctypes.data, samples.ctypes.data, noise.ctypes.data, C.byref(c)))
+        return rgb, samples, noise, c.as_dict()
+
+    def render_adaptive_device(self, cfg: RenderConfig, adaptive: AdaptiveConfig, d_rgb_ptr: int, d_samples_ptr: int = 0,
+                               d_noise_ptr: int = 0, stream: int = 0) -> None:
+        """d_rgb_ptr: device float32 [h, w, 3]; d_samples_ptr / d_noise_ptr: device uint32 / float32 [h, w], or 0.  Stream-ordered,
+        but blocks the host once per round (rtk.h); not capturable."""
+        p, ap = cfg.to_c(), adaptive.to_c()
+        _check(_L.rtk_render_adaptive_device(self._h, C.byref(p), C.byref(ap), d_rgb_ptr or None, d_samples_ptr or None,
+                                             d_noise_ptr or None, stream))
 
     # ---- lights, materials and background of a live accel (rtk.h rtk_light, rtk_material)
     def lights(self):

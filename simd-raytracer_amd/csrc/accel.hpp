@@ -58,6 +58,7 @@ struct rtk_knobs {
     bool camera_keeps_order = false;                        // RTK_CAMERA_KEEPS_ORDER: rtk_accel_set_camera leaves the cost-feedback launch order of the previous camera in place
     size_t views_launch_units = 131072;                     // RTK_VIEWS_LAUNCH_UNITS: pixel blocks of one rtk_render_views launch (api_frame.hip; a test lowers it)
     bool traversal_fast = false;                            // RTK_TRAVERSAL_FAST: front-to-back leaf order (rtk.h; NOT the parity mode)
+    size_t adaptive_chunk_pixels = size_t(1) << 20;         // RTK_ADAPTIVE_CHUNK_PIXELS: pixels of one chunk of an adaptive round (adaptive_plan.hpp; a test lowers it)
 
     static rtk_knobs from_env() {
         rtk_knobs k;
@@ -99,6 +100,7 @@ struct rtk_knobs {
         if (geti("RTK_VIEWS_LAUNCH_UNITS", v) && v >= 1 && v <= (1l << 30)) k.views_launch_units = size_t(v);
         if (geti("RTK_CAMERA_KEEPS_ORDER", v)) k.camera_keeps_order = v != 0;
         if (geti("RTK_STREAM_LANES", v) && v >= 1 && v <= rtk::dev::kStreamLanes) k.stream_lanes = int(v);
+        if (geti("RTK_ADAPTIVE_CHUNK_PIXELS", v) && v >= 1 && v <= (1l << 30)) k.adaptive_chunk_pixels = size_t(v);
         return k;
     }
 };
@@ -294,6 +296,18 @@ struct rtk_accel {
     // ---- gb_*: staging of the host variant of rtk_render_gbuffer (api_gbuffer.hip): grows with head room, never shrinks
     rtk::DevBuf<rtk_view> gb_views;
     rtk::DevBuf<uint32_t> gb_out;              // the wanted planes one behind the other, dwords
+    // ---- ad_*: rtk_render_adaptive (api_adaptive.hip, adaptive.hip).  24 B per pixel of the largest frame so far: the luminance sums,
+    // the two lists of active pixels a round reads and writes; beside them the two block lists, the count word with its pinned host
+    // copy, the rays and colours of one chunk, and the staging of the host variant.  All grow with head room and never shrink.
+    rtk::DevBuf<double> ad_s1, ad_s2;
+    rtk::DevBuf<uint32_t> ad_list;             // [2][pixels]
+    rtk::DevBuf<uint32_t> ad_blocks;           // [2][blocks]
+    rtk::DevBuf<unsigned long long> ad_count;  // adaptive_plan.hpp ad_count_word
+    rtk::PinBuf<unsigned long long> ad_count_host;
+    rtk::DevBuf<rtk_ray> ad_rays;
+    rtk::DevBuf<float> ad_rgb;
+    rtk::DevBuf<uint32_t> ad_out;              // host variant: rgb, samples and noise one behind the other, dwords
+    rtk::LastUse ad_last;                      // of the workspace by a call's kernels: a call on another stream waits for it
     // ---- trial*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     rtk::TimedEvent trial_ev[4];
     rtk::EngineTrial trial;
@@ -449,6 +463,10 @@ int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g);
 rtk_view accel_camera(const rtk_accel *a);                                                       // the camera later frames are rendered from
 void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A);   // the camera half of the launch arguments
 int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes);
+hipError_t zero_counters(rtk_accel *a, hipStream_t s);                                           // the block in use starts at zero; no steady frame behind it
+void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary);                     // what rtk_render_last_counters goes by
+int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
+                         float *d_rgb, hipStream_t s, uint32_t *n_chunks_out);                   // rtk_accel_radiance_device behind its checks
 void free_stream_ws(rtk_accel *a);
 
 }  // namespace rtk

@@ -173,6 +173,10 @@ hipError_t fill_counters(rtk_accel *a, hipStream_t s) {
     a->counter_fills += 1;
     return hipMemsetAsync(counters_now(a), 0, kCounterAllocWords * sizeof(unsigned long long), s);
 }
+
+}  // namespace
+
+// (these two are api_adaptive.hip's as well: accel.hpp)
 // ... by everyone but a steady frame (render_frame_impl), whose block the frame before it cleared: what that frame knew is forgotten
 hipError_t zero_counters(rtk_accel *a, hipStream_t s) {
     a->cnt.forget();
@@ -185,8 +189,6 @@ void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary) {
     a->last_stats = stats;
     a->last_primary = primary;
 }
-
-}  // namespace
 
 // (these two are api_gbuffer.hip's as well: accel.hpp)
 // the accel's own camera: the scene's at rtk_accel_build, then whatever rtk_accel_set_camera stored there
@@ -616,8 +618,11 @@ int radiance_check(const rtk_accel *a, const void *rays, const void *ids, size_t
     return RTK_OK;
 }
 
+}  // namespace
+
 // The batch cut into chunks, every chunk one run of the streaming pipeline (level 0 = the chunk's rays) on one of the accel's
 // lanes, followed by its counter fold and its overflow fallback.  Nothing here waits on the host.
+// (api_adaptive.hip's as well: accel.hpp)
 int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
                          float *d_rgb, hipStream_t s, uint32_t *n_chunks_out) {
     a->cnt.forget();                                     // (no steady frame: frame_plan.hpp CounterState)
@@ -668,6 +673,8 @@ int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_
     RTK_TRY(join_lanes(a, lanes, s));
     return release_stream_ws(a, s);
 }
+
+namespace {
 
 // ---------------------------------------------------------------- rtk_render_regions
 

@@ -524,6 +524,35 @@ struct hip_accel {
         return px;
     }
 
+    // A frame whose 8x8 pixel blocks stop taking samples once they have converged (rtk_render_adaptive): params.spp is the
+    // ceiling.  pixels [h][w]; samples and noise are [h * w], x fastest.  Every pixel is the pixel of render_frame with
+    // spp = samples[pixel], bit for bit; noise is the standard error of the pixel's mean luminance at its final count.
+    struct adaptive_result {
+        std::size_t width = 0, height = 0;
+        std::vector<std::vector<color<F>>> pixels;
+        std::vector<std::uint32_t> samples;
+        std::vector<float> noise;
+    };
+    [[nodiscard]] adaptive_result render_adaptive(const rtk_render_params &params, const rtk_adaptive_params &adaptive,
+                                                  rtk_counters *counters = nullptr) const {
+        std::size_t n = 0;
+        check(rtk_render_output_floats(accel_.get(), &params, &n));
+        adaptive_result r;
+        r.width = params.width > 0 ? static_cast<std::size_t>(params.width) : scene_ptr->config.image_width;
+        r.height = n / 3 / r.width;
+        std::vector<float> rgb(n);
+        r.samples.resize(n / 3);
+        r.noise.resize(n / 3);
+        check(rtk_render_adaptive(accel_.get(), &params, &adaptive, rgb.data(), r.samples.data(), r.noise.data(), counters));
+        r.pixels.assign(r.height, std::vector<color<F>>(r.width));
+        for (std::size_t y = 0; y < r.height; ++y)
+            for (std::size_t x = 0; x < r.width; ++x) {
+                const float *px = rgb.data() + (y * r.width + x) * 3;
+                r.pixels[y][x] = color<F>{px[0], px[1], px[2]};
+            }
+        return r;
+    }
+
     // config.hpp:6-17 defaults
     [[nodiscard]] static rtk_render_params default_params() noexcept {
         rtk_render_params p{};

@@ -616,6 +616,66 @@ int rtk_render_adaptive(rtk_accel *accel, const rtk_render_params *p, const rtk_
 int rtk_render_adaptive_device(rtk_accel *accel, const rtk_render_params *p, const rtk_adaptive_params *ap,
                                float *d_rgb, uint32_t *d_samples, float *d_noise, void *hip_stream);
 
+/* ---- an edge-avoiding filter of a frame, guided by the g-buffer ----
+ * Consumes what rtk_render_gbuffer and rtk_render_adaptive write: a 5x5 a-trous filter of `rgb` along the surfaces that `normal`,
+ * `position` and `depth` describe, weighted by the variance that `noise` gives.  The reference has no denoiser; the arithmetic is
+ * spelt out here and pinned, bit for bit, by tests/denoise_model.py.  The calls take no accel: the filter depends on no scene state.
+ * Inputs are n_images images of width x height, one behind the other: rgb, normal, position and albedo [n_images][h][w][3], depth
+ * and noise [n_images][h][w], in the layouts rtk_gbuffer and rtk_render_adaptive write.  noise may be NULL, albedo may be NULL.
+ * The output is rgb_out [n_images][h][w][3].
+ * All arithmetic is float, in the order written, without contraction.  A pixel is a HIT iff `depth >= 0.0f` evaluates true (a miss,
+ * -1, or a NaN is not a hit).  lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.  max(x, f) = x > f ? x : f.
+ * Prologue, per pixel p.  With an albedo plane: a = max(albedo, albedo_floor) per channel; on a hit c = rgb / a per channel, on a
+ *   miss c = rgb.  Without one c = rgb.  var = 1.0f without a noise plane, noise * noise with one; on a hit with albedo then
+ *   var = var / (la * la) with la = lum(a).
+ * Iterations k = 0 .. iterations - 1 with s = 1 << k; h = {1/16, 1/4, 3/8, 1/4, 1/16}, sl2 = sigma_luminance * sigma_luminance,
+ *   sp2 = sigma_plane * sigma_plane.  A miss pixel's c and var pass through unchanged.  For a hit pixel p:
+ *   1. lp = lum(c_p), den = sl2 * var_p + 1e-8f, sum_c = sum_v = sum_w = +0.
+ *   2. The taps dy = -2..2 (outer loop), dx = -2..2 (inner loop), q = p + s * (dx, dy).  A tap outside the image is skipped (never
+ *      clamped, never wrapped, never another image's pixel); a tap that is not a hit is skipped.
+ *   3. The centre tap dx = dy = 0 gets w = 0.140625f.
+ *   4. Every other tap: t = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z; t = t > 0 ? t : 0; normal_power_log2 times t = t * t;
+ *      D = P_q - P_p; pd = (n_p.x * D.x + n_p.y * D.y) + n_p.z * D.z; wd = 1.0f / (1.0f + (pd * pd) / sp2);
+ *      dl = lum(c_q) - lp; wl = 1.0f / (1.0f + (dl * dl) / den); w = (((h[dy + 2] * h[dx + 2]) * t) * wd) * wl.
+ *   5. Per channel sum_c = sum_c + w * c_q; sum_v = sum_v + (w * w) * var_q; sum_w = sum_w + w.
+ *   6. After the taps c_p' = sum_c / sum_w and var_p' = sum_v / (sum_w * sum_w).
+ *   Every iteration reads the previous iteration's c and var of all pixels; the guide planes never change.
+ * Epilogue.  On a hit with albedo rgb_out = c * a, otherwise rgb_out = c: a miss pixel leaves with the bits it came with.
+ * rgb_out may be the very pointer rgb (in place); any other overlap of the output or the workspace with a plane is the caller's fault.
+ * What runs (csrc/denoise.hip): k_denoise_prepare packs (c, var) and the guides into 16-byte records in the workspace; then one
+ * launch of k_denoise_atrous per iteration, one 256-thread workgroup per 16x16 pixel tile of an image.  Steps up to
+ * RTK_DENOISE_LDS_MAX_STEP (environment, read once per process; 0 = never, default 4, at most 8) load the tile with its halo of 2 * s pixels into LDS
+ * and run the taps from there, larger steps read the records from global memory; the results do not depend on it.  The last
+ * iteration applies the epilogue and writes rgb_out.
+ * The caller supplies the workspace of the device variant: rtk_denoise_workspace_bytes says how much (at most 64 B per pixel; 0
+ * for n_images == 0); it needs 16-byte alignment and is scratch, its contents before and after a call mean nothing.  The planes need
+ * 4-byte alignment.  The device variant is stream-ordered on the current device, allocates nothing and never blocks the host.
+ * Stream capture is neither claimed nor tested.  The host variant stages planes and workspace in device buffers of its own, which
+ * it frees, and is synchronous.
+ * Errors, in this order: a NULL p, in or (rtk_denoise_workspace_bytes) bytes -> RTK_ERR_INVALID.  Then width < 1 or height < 1;
+ * more than 2^28 pixels per image; iterations outside [1, 8]; normal_power_log2 outside [0, 8]; a sigma_luminance, sigma_plane or
+ * albedo_floor that is non-finite or not positive; n_images < 0; more than 2^31 pixels in total -> RTK_ERR_INVALID.  Then
+ * n_images == 0 -> RTK_OK, nothing touched, device or not.  Then a NULL rgb, normal, position, depth or output -> RTK_ERR_INVALID.
+ * Then (device variant) a plane that is not 4-byte aligned; a NULL workspace or one that is not 16-byte aligned; a workspace
+ * smaller than asked for -> RTK_ERR_INVALID.  Then RTK_ERR_NO_DEVICE. */
+typedef struct {
+    int32_t width, height;        /* of every image; at most 2^28 pixels */
+    int32_t iterations;           /* 1..8: steps 1, 2, 4, ... */
+    int32_t normal_power_log2;    /* 0..8: the normal weight is max(n_p . n_q, 0) to the power 2^this */
+    float   sigma_luminance;      /* finite, > 0: in standard deviations of the pixel's own luminance */
+    float   sigma_plane;          /* finite, > 0: distance from the tangent plane of p, in scene units */
+    float   albedo_floor;         /* finite, > 0: lower bound of the albedo that the colour is divided by */
+    int32_t reserved;
+} rtk_denoise_params;             /* 32 bytes */
+typedef struct { const float *rgb, *noise, *albedo, *normal, *position, *depth; } rtk_denoise_inputs;   /* 48 bytes */
+
+int rtk_denoise_workspace_bytes(const rtk_denoise_params *p, int32_t n_images, size_t *bytes);
+int rtk_denoise_frame(const rtk_denoise_params *p, int32_t n_images, const rtk_denoise_inputs *in /* host planes */,
+                      float *rgb_out /* host */);
+int rtk_denoise_frame_device(const rtk_denoise_params *p, int32_t n_images,
+                             const rtk_denoise_inputs *in /* struct on the HOST, DEVICE planes */, float *d_rgb_out,
+                             void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

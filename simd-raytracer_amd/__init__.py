@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "rtk_render_regions", "rtk_render_regions_device",
     "rtk_render_gbuffer", "rtk_render_gbuffer_device",
     "rtk_render_adaptive", "rtk_render_adaptive_device",
+    "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
@@ -150,6 +151,17 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("min_samples", C.c_int32), ("step", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """rtk.h rtk_denoise_params; 32 bytes."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float), ("albedo_floor", C.c_float), ("reserved", C.c_int32)]
+
+
+class DenoiseInputs(C.Structure):
+    """rtk.h rtk_denoise_inputs: one pointer per plane, noise and albedo may be NULL; 48 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "albedo", "normal", "position", "depth")]
+
+
 # the planes of a g-buffer in the struct's order: name -> (trailing shape, dtype); miss values in rtk.h
 GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
@@ -215,6 +227,9 @@ _L.rtk_render_gbuffer.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, 
 _L.rtk_render_gbuffer_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer), _vp]
 _L.rtk_render_adaptive.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, C.POINTER(Counters)]
 _L.rtk_render_adaptive_device.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp]
+_L.rtk_denoise_workspace_bytes.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(C.c_size_t)]
+_L.rtk_denoise_frame.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp]
+_L.rtk_denoise_frame_device.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp, _vp, C.c_size_t, _vp]
 _L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
@@ -410,6 +425,20 @@ class AdaptiveConfig:
 
     def to_c(self) -> AdaptiveParams:
         return AdaptiveParams(self.min_samples, self.step, np.float32(self.threshold), np.float32(self.floor))
+
+
+@dataclass
+class DenoiseConfig:
+    """rtk.h rtk_denoise_params without the image size: the edge-avoiding a-trous filter of denoise()."""
+    iterations: int = 5            # 1..8: steps 1, 2, 4, ...
+    normal_power_log2: int = 2     # 0..8: the normal weight is max(n_p . n_q, 0) ** (2 ** this)
+    sigma_luminance: float = 1.5   # in standard deviations of the pixel's own luminance (the noise plane)
+    sigma_plane: float = 0.05      # distance from the centre pixel's tangent plane, in scene units
+    albedo_floor: float = 0.01     # lower bound of the albedo that the colour is divided by
+
+    def to_c(self, width: int, height: int) -> DenoiseParams:
+        return DenoiseParams(width, height, self.iterations, self.normal_power_log2, np.float32(self.sigma_luminance),
+                             np.float32(self.sigma_plane), np.float32(self.albedo_floor), 0)
 
 
 @dataclass(frozen=True)
@@ -973,6 +1002,64 @@ def format_ppm(rgb: np.ndarray) -> bytes:
 def frame_to_rgb8_device(d_rgb_ptr: int, n_floats: int, d_out_ptr: int, stream: int = 0) -> None:
     """uint8(255.999 * clamp(c, 0, 1)) per channel on the device (io/image/ppm.hpp:17-19)."""
     _check(_L.rtk_frame_to_rgb8_device(d_rgb_ptr, n_floats, d_out_ptr, stream))
+
+
+# ---- an edge-avoiding filter of a frame, guided by the g-buffer (rtk.h rtk_denoise_params)
+def denoise_workspace_bytes(width: int, height: int, n_images: int = 1, cfg: DenoiseConfig | None = None) -> int:
+    """Bytes of device workspace denoise_device needs for n_images images of width x height (at most 64 per pixel)."""
+    p = (cfg or DenoiseConfig()).to_c(width, height)
+    n = C.c_size_t(0)
+    _check(_L.rtk_denoise_workspace_bytes(C.byref(p), n_images, C.byref(n)))
+    return n.value
+
+
+def denoise(rgb: np.ndarray, normal: np.ndarray, position: np.ndarray, depth: np.ndarray, noise: np.ndarray | None = None,
+            albedo: np.ndarray | None = None, cfg: DenoiseConfig | None = None) -> np.ndarray:
+    """rgb filtered along the surfaces that normal, position and depth describe (the planes render_gbuffer writes), weighted by
+    the variance noise ** 2 (the plane render_adaptive writes) and, with albedo, with the texture divided out first.  rgb, normal,
+    position, albedo: float32 [h, w, 3] or [K, h, w, 3]; depth, noise: [h, w] or [K, h, w].  -> float32 of rgb's shape.  The
+    arithmetic is spelt out in rtk.h; a pixel whose depth is not >= 0 keeps its bits."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim not in (3, 4) or rgb.shape[-1] != 3:
+        raise ValueError("rgb must be [h, w, 3] or [K, h, w, 3]")
+    lead = rgb.shape[:-1]
+    k = 1 if rgb.ndim == 3 else lead[0]
+    h, w = lead[-2], lead[-1]
+
+    def plane(a, shape, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32)
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}, not {a.shape}")
+        return a
+
+    normal, position = plane(normal, rgb.shape, "normal"), plane(position, rgb.shape, "position")
+    albedo = plane(albedo, rgb.shape, "albedo")
+    depth, noise = plane(depth, lead, "depth"), plane(noise, lead, "noise")
+    if normal is None or position is None or depth is None:
+        raise ValueError("normal, position and depth are required")
+    out = np.zeros_like(rgb)
+    if rgb.size == 0:
+        return out
+    ptr = lambda a: None if a is None else a.ctypes.data
+    inputs = DenoiseInputs(ptr(rgb), ptr(noise), ptr(albedo), ptr(normal), ptr(position), ptr(depth))
+    p = (cfg or DenoiseConfig()).to_c(w, h)
+    _check(_L.rtk_denoise_frame(C.byref(p), k, C.byref(inputs), out.ctypes.data))
+    return out
+
+
+def denoise_device(width: int, height: int, d_rgb_ptr: int, d_normal_ptr: int, d_position_ptr: int, d_depth_ptr: int, d_out_ptr: int,
+                   d_workspace_ptr: int, workspace_bytes: int, d_noise_ptr: int = 0, d_albedo_ptr: int = 0, n_images: int = 1,
+                   cfg: DenoiseConfig | None = None, stream: int = 0) -> None:
+    """The same on device planes (float32, 4-byte aligned; d_noise_ptr / d_albedo_ptr may be 0), into d_out_ptr, which may be
+    d_rgb_ptr.  d_workspace_ptr: denoise_workspace_bytes(...) bytes of scratch, 16-byte aligned.  Stream-ordered on the current
+    device, allocates nothing, never blocks the host (rtk.h)."""
+    inputs = DenoiseInputs(d_rgb_ptr or None, d_noise_ptr or None, d_albedo_ptr or None, d_normal_ptr or None, d_position_ptr or None,
+                           d_depth_ptr or None)
+    p = (cfg or DenoiseConfig()).to_c(width, height)
+    _check(_L.rtk_denoise_frame_device(C.byref(p), n_images, C.byref(inputs), d_out_ptr or None, d_workspace_ptr or None,
+                                       workspace_bytes, stream or None))
 
 
 def format_ppm_rgb8(rgb8: np.ndarray) -> bytes:

@@ -616,6 +616,47 @@ int rtk_render_adaptive(rtk_accel *accel, const rtk_render_params *p, const rtk_
 int rtk_render_adaptive_device(rtk_accel *accel, const rtk_render_params *p, const rtk_adaptive_params *ap,
                                float *d_rgb, uint32_t *d_samples, float *d_noise, void *hip_stream);
 
+/* ---- a frame of a fixed sample count, with its noise plane ----
+ * What rtk_denoise_frame wants beside the frame: the `noise` plane of rtk_render_adaptive, for a caller who wants every pixel to
+ * take all p->spp samples, at the speed of a frame.  An adaptive render with min_samples = spp gives the same two planes, one
+ * sample of one chunk at a time; this call renders a streamed frame and takes the statistic where the samples already lie.
+ * Contract:
+ *  1. rgb is, bit for bit, what rtk_render_frame leaves with the same *p, through any engine; counters.rays and counters.primary
+ *     are the frame's.  rtk_render_last_counters reports the call, rtk_render_last_critical_path reports 0 for it.  This is claimed
+ *     for RTK_TRAVERSAL_REFERENCE accels; RTK_TRAVERSAL_FAST accels carry the tie caveat that rtk_accel_radiance states.
+ *  2. noise[px] = (float)e_i of item 3 of rtk_render_adaptive's contract at n = spp: per sample colour c, as radiance returns it
+ *     (+0 + c), y = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b in float, without contraction; S1 += (double)y and
+ *     S2 += (double)y * (double)y in double, in sample order; then v = max(0, (S2 - S1 * S1 / n) / (n - 1)) / n and e = sqrt(v) in
+ *     double (max passes a NaN on).  noise is therefore, bit for bit, the noise plane of rtk_render_adaptive with the same *p and
+ *     min_samples = spp: both are built without contraction from the same double expressions and the same square root.
+ *  3. The call reads the live state -- camera, updated geometry, lights, materials, textures, background -- and leaves alone the
+ *     accel's camera, the cost tables of frames, views and regions, the regions table and RTK_TRACE_AUTO's trial and verdict: it
+ *     neither takes part in the trial nor abandons it, beyond what growing the queues it shares with the frames already does.  On
+ *     the accel's counter block (rtk_debug_counter_fills, the block a steady frame relies on) it has the effect of an
+ *     RTK_TRACE_STREAM frame in its place.
+ *  4. The call always runs through the streaming engine: RTK_TRACE_AUTO means RTK_TRACE_STREAM here, as for rtk_accel_radiance.
+ * What runs (csrc/frame_noise.hip): the batches of an RTK_TRACE_STREAM frame, and behind every batch's last kernel one more, a
+ * thread per pixel, that adds the batch's sample luminances to the pixel's two sums, or, in the batch that ends at spp, writes the
+ * noise.  The sums (16 B per pixel) are the workspace of rtk_render_adaptive, which belongs to the accel and grows with head room.
+ * Overflow.  A streamed frame whose queues overflow is normally redone by the megakernel, which has no statistic.  This call reads
+ * the overflow flag back and, if it is set, redoes itself as rtk_render_adaptive with min_samples = spp, step = 1, threshold = 0 and
+ * floor = 1: by items 1 and 2 the same rgb, noise, rays and primary; only the time differs (and the counter block is filled a
+ * second time).  rtk_debug_noise_fallbacks counts such calls.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL accel, p, rgb or noise (a caller without use for the noise has
+ * rtk_render_frame); what rtk_render_frame refuses for *p; trace_mode other than RTK_TRACE_AUTO or RTK_TRACE_STREAM; spp < 2;
+ * sample_begin or sample_count not 0 (the statistic of a progressive frame would need a second running buffer in the caller's
+ * hands: not offered); collect_stats != 0; world_size > 1; a frame of more than 2^31 pixels.  Then RTK_ERR_NO_DEVICE.  A refused
+ * call leaves the accel unchanged and usable.
+ * The device variant is stream-ordered on hip_stream.  It may block the host to grow a workspace, and it BLOCKS THE HOST ONCE AT
+ * ITS END to read back one 32-bit word, whether any queue overflowed.  It is NOT stream-capturable.  The host variant stages rgb
+ * and noise in a buffer the accel owns and is synchronous. */
+int rtk_render_frame_noise(rtk_accel *accel, const rtk_render_params *p, float *rgb /* host [h][w][3] */,
+                           float *noise /* host [h][w] */, rtk_counters *counters /* may be NULL */);
+int rtk_render_frame_noise_device(rtk_accel *accel, const rtk_render_params *p, float *d_rgb, float *d_noise, void *hip_stream);
+/* Diagnostic, like rtk_debug_counter_fills: the rtk_render_frame_noise calls on this accel that were redone because a queue
+ * overflowed, since it was built.  Needs no device. */
+int rtk_debug_noise_fallbacks(rtk_accel *accel, uint64_t *count);
+
 /* ---- an edge-avoiding filter of a frame, guided by the g-buffer ----
  * Consumes what rtk_render_gbuffer and rtk_render_adaptive write: a 5x5 a-trous filter of `rgb` along the surfaces that `normal`,
  * `position` and `depth` describe, weighted by the variance that `noise` gives.  The reference has no denoiser; the arithmetic is

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "rtk_render_regions", "rtk_render_regions_device",
     "rtk_render_gbuffer", "rtk_render_gbuffer_device",
     "rtk_render_adaptive", "rtk_render_adaptive_device",
+    "rtk_render_frame_noise", "rtk_render_frame_noise_device", "rtk_debug_noise_fallbacks",
     "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
@@ -227,7 +228,11 @@ _L.rtk_render_gbuffer.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, 
 _L.rtk_render_gbuffer_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer), _vp]
 _L.rtk_render_adaptive.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, C.POINTER(Counters)]
 _L.rtk_render_adaptive_device.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp]
-_L.rtk_denoise_workspace_bytes.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(C.c_size_t)]
+if hasattr(_L, "rtk_render_frame_noise"):             # (as above: an older build under RTK_LIB_OVERRIDE has no such call)
+    _L.rtk_render_frame_noise.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp, C.POINTER(Counters)]
+    _L.rtk_render_frame_noise_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]
+    _L.rtk_debug_noise_fallbacks.argtypes = [_vp, C.POINTER(C.c_uint64)]
+_L.rtk_denoise_workspace_bytes.argtypes =[C.POINTER(DenoiseParams), C.c_int32, C.POINTER(C.c_size_t)]
 _L.rtk_denoise_frame.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp]
 _L.rtk_denoise_frame_device.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp, _vp, C.c_size_t, _vp]
 _L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
@@ -822,6 +827,32 @@ class KdTreeSimdAccel:
         p, ap = cfg.to_c(), adaptive.to_c()
         _check(_L.rtk_render_adaptive_device(self._h, C.byref(p), C.byref(ap), d_rgb_ptr or None, d_samples_ptr or None,
                                              d_noise_ptr or None, stream))
+
+    # ---- a frame of a fixed sample count with the noise plane the denoiser weights by (rtk.h rtk_render_frame_noise)
+    def render_frame_noise(self, cfg: RenderConfig):
+        """-> (rgb [h, w, 3] float32, noise [h, w] float32, counters).  rgb and counters are render_frame(cfg)'s, noise is, bit for bit,
+        the noise plane of render_adaptive(cfg, min_samples = cfg.spp): the standard error of the pixel's mean luminance after all
+        cfg.spp samples.  A streamed frame (TRACE_AUTO means TRACE_STREAM here), cfg.spp >= 2, not progressive, not sharded."""
+        w = cfg.width or self.scene.info.width
+        h = cfg.height or self.scene.info.height
+        rgb = np.zeros((h, w, 3), np.float32)
+        noise = np.zeros((h, w), np.float32)
+        p = cfg.to_c()
+        c = Counters()
+        _check(_L.rtk_render_frame_noise(self._h, C.byref(p), rgb.ctypes.data, noise.ctypes.data, C.byref(c)))
+        return rgb, noise, c.as_dict()
+
+    def render_frame_noise_device(self, cfg: RenderConfig, d_rgb_ptr: int, d_noise_ptr: int, stream: int = 0) -> None:
+        """d_rgb_ptr: device float32 [h, w, 3]; d_noise_ptr: device float32 [h, w].  Stream-ordered, but blocks the host once at its
+        end, to learn whether a queue overflowed (rtk.h); not capturable."""
+        p = cfg.to_c()
+        _check(_L.rtk_render_frame_noise_device(self._h, C.byref(p), d_rgb_ptr or None, d_noise_ptr or None, stream))
+
+    def noise_fallbacks(self) -> int:
+        """rtk.h rtk_debug_noise_fallbacks: render_frame_noise calls on this accel that were redone because a queue overflowed."""
+        n = C.c_uint64(0)
+        _check(_L.rtk_debug_noise_fallbacks(self._h, C.byref(n)))
+        return n.value
 
     # ---- lights, materials and background of a live accel (rtk.h rtk_light, rtk_material)
     def lights(self):

@@ -308,6 +308,11 @@ struct rtk_accel {
     rtk::DevBuf<float> ad_rgb;
     rtk::DevBuf<uint32_t> ad_out;              // host variant: rgb, samples and noise one behind the other, dwords
     rtk::LastUse ad_last;                      // of the workspace by a call's kernels: a call on another stream waits for it
+    // ---- fn_*: rtk_render_frame_noise (api_frame_noise.hip, frame_noise.hip).  Its running sums are ad_s1 / ad_s2, behind ad_last;
+    // its own are the pinned word the overflow flag is read back into, the staging of the host variant and the count of redone calls.
+    rtk::PinBuf<uint32_t> fn_overflow_host;
+    rtk::DevBuf<float> fn_out;                 // host variant: rgb and noise one behind the other
+    uint64_t noise_fallbacks = 0;              // calls redone through the adaptive path because a queue overflowed (rtk_debug_noise_fallbacks)
     // ---- trial*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     rtk::TimedEvent trial_ev[4];
     rtk::EngineTrial trial;
@@ -468,5 +473,20 @@ void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary);    
 int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
                          float *d_rgb, hipStream_t s, uint32_t *n_chunks_out);                   // rtk_accel_radiance_device behind its checks
 void free_stream_ws(rtk_accel *a);
+// (the streaming pipeline's setup and its lanes are api_frame_noise.hip's as well)
+struct StreamSetup {
+    dev::StreamArgs S;
+    int deep_level, deep_mode, sort_from, slices;      // launch_stream_sample's
+    size_t factor, node_bytes, budget;                 // stream_plan.hpp's
+};
+StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffuse_rays, bool forks);
+int claim_stream_ws(rtk_accel *a, hipStream_t s);                                                // the queues' previous user finishes first, on the device
+int release_stream_ws(rtk_accel *a, hipStream_t s);
+int fork_lanes(rtk_accel *a, int lanes, hipStream_t s);                                          // lanes 1.. start behind everything enqueued on `s`
+int join_lanes(rtk_accel *a, int lanes, hipStream_t s);                                          // `s` continues behind every lane's last launch
+dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out);
+// api_adaptive.hip
+int adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,
+                         uint32_t *d_samples, float *d_noise, hipStream_t s);                    // rtk_render_adaptive_device behind its checks
 
 }  // namespace rtk

@@ -38,8 +38,11 @@ int ensure_adaptive_ws(rtk_accel *a, size_t pixels, size_t blocks, size_t chunk)
     return RTK_OK;
 }
 
+}  // namespace
+
 // The rounds of a call.  Everything is enqueued on `s`; the host waits once per round that is not the last, for the count word.
-int adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,
+// (api_frame_noise.hip's as well, for the call it redoes after a queue overflow: accel.hpp)
+int rtk::adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,
                          uint32_t *d_samples, float *d_noise, hipStream_t s) {
     const uint64_t pixels = uint64_t(g.width) * g.height, blocks = adaptive_blocks(g.width, g.height);
     const uint64_t chunk = a->knobs.adaptive_chunk_pixels;
@@ -104,8 +107,6 @@ int adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_ada
     record_last(a, s, false, primary);
     return RTK_OK;
 }
-
-}  // namespace
 
 int rtk_render_adaptive_device(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, float *d_rgb, uint32_t *d_samples,
                                float *d_noise, void *stream) {

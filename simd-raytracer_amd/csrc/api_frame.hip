@@ -214,15 +214,8 @@ void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeo
     A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height); A.spp_f = static_cast<float>(p->spp);
 }
 
-namespace {
-
-// ---------------------------------------------------------------- the streaming pipeline's setup, for both of its clients
-
-struct StreamSetup {
-    dev::StreamArgs S;
-    int deep_level, deep_mode, sort_from, slices;      // launch_stream_sample's
-    size_t factor, node_bytes, budget;                 // stream_plan.hpp's
-};
+// ---------------------------------------------------------------- the streaming pipeline's setup, for all of its clients
+// (these six are api_frame_noise.hip's as well: accel.hpp, where StreamSetup is)
 
 // Zeroed StreamArgs with what does not depend on the client: a frame and a radiance chunk then set only what is theirs.
 StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffuse_rays, bool forks) {
@@ -264,6 +257,8 @@ int join_lanes(rtk_accel *a, int lanes, hipStream_t s) {
     for (int j = 1; j < lanes; ++j) RTK_HIP(hipStreamWaitEvent(s, a->lane_done[j].get(), 0));
     return RTK_OK;
 }
+
+namespace {
 
 // fresh queues: their first use is not what a frame costs -- time the pipeline on the next frame instead
 void trial_abandon(rtk_accel *a, hipEvent_t trial[2]) { trial[0] = trial[1] = nullptr; a->trial.abandon(); }
@@ -447,7 +442,10 @@ int render_megakernel(rtk_accel *a, rtk_cost_feedback &fb, const rtk_render_para
     return rc;
 }
 
+}  // namespace
+
 // what every engine's launch arguments hold for a frame of shape `g` seen from `cam` into `d_out`
+// (api_frame_noise.hip's as well: accel.hpp)
 dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out) {
     dev::RenderArgs A = scene_args(a, p->collect_stats);
     camera_args(cam, p, g, A);
@@ -461,6 +459,8 @@ dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const
     A.out = d_out; A.counters = counters_now(a);
     return A;
 }
+
+namespace {
 
 // `steady`: a frame of its own (not a view of a views call, whose counters are folded part by part): a megakernel frame without
 // statistics then counts into the block the frame before it cleared and clears the other one for the next (frame_plan.hpp CounterState).

@@ -665,7 +665,8 @@ void launch_shadow(const dev::StreamArgs &S, bool stats, unsigned units, hipStre
 // from `deep_level` on `deep_mode` (RTK_TRACE_AUTO / _LANE / _WAVE) applies.  From depth `sort_from_level` on, the
 // level's rays and shading points are counting-sorted for coherence before they are cut into 64-ray work units.
 hipError_t launch_stream_sample(const dev::StreamArgs &base, bool stats, int deep_level, int deep_mode, int sort_from_level,
-                                hipStream_t s, hipEvent_t wait_before_emit, hipEvent_t done, const StreamSide *side, int slices) {
+                                hipStream_t s, hipEvent_t wait_before_emit, hipEvent_t done, const StreamSide *side, int slices,
+                                const StreamMoments &moments) {
     dev::StreamArgs S = base;
     const dev::RenderArgs &A = S.r;
     if (S.n_root == 0) return hipSuccess;
@@ -742,6 +743,11 @@ hipError_t launch_stream_sample(const dev::StreamArgs &base, bool stats, int dee
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(dev::k_combine, dim3(level == 0 ? 2048 : 1024), dim3(256), 0, s, S);
+    }
+    if (moments.s1 != nullptr) {                                 // the batch's sample colours are final: their statistic, in front of `done`
+        S.level = 0u;
+        e = launch_frame_moments(S, moments, s);
+        if (e != hipSuccess) return e;
     }
     if (done != nullptr) {
         e = hipEventRecord(done, s);

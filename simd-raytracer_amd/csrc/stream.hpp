@@ -117,11 +117,23 @@ struct StreamSide {
     hipEvent_t ready[2];     // recorded on the lane's stream when a level's shading points are sorted: k_shadow may start
     hipEvent_t done[2];      // recorded on the side stream behind its last k_shadow of the sample
 };
+// The luminance statistic of a frame's samples beside its pixel sums (rtk_render_frame_noise; frame_noise.hip): two running sums per
+// pixel, and where the batch that ends at spp writes the standard error of the pixel's mean luminance.  Default: none.
+struct StreamMoments {
+    double *s1 = nullptr, *s2 = nullptr;   // [n_pixels] each; null: no statistic
+    float *noise = nullptr;                // [n_pixels]
+    uint32_t n_pixels = 0;                 // width * height of the frame: a pixel index read from a node is checked against it
+};
 // `wait_before_emit` (may be null): the depth-0 k_combine waits for it (the previous sample's `done`); `done` (may be null) is
 // recorded behind it.  `side` (may be null): run the k_shadow kernels there.
 // `slices`: waves per 64-ray work unit of the queue-driven levels (4: an owner and three helpers that share its large leaves; 2; 1: no helpers)
+// `moments` with sums: k_frame_moments runs behind the depth-0 k_combine and in front of the `done` record, so the statistics of
+// successive batches are taken in sample order like the pixel sums.
 hipError_t launch_stream_sample(const dev::StreamArgs &base, bool stats, int deep_level, int deep_mode, int sort_from_level,
-                                hipStream_t s, hipEvent_t wait_before_emit, hipEvent_t done, const StreamSide *side, int slices = 4);
+                                hipStream_t s, hipEvent_t wait_before_emit, hipEvent_t done, const StreamSide *side, int slices = 4,
+                                const StreamMoments &moments = StreamMoments());
+// frame_noise.hip: the statistic of the batch S describes (S.sample, S.n_batch, S.n_root; S.ws the lane's queues), on `s`
+hipError_t launch_frame_moments(const dev::StreamArgs &S, const StreamMoments &M, hipStream_t s);
 // rtk_accel_radiance (radiance.hip), behind a chunk's pipeline on the chunk's stream.  `lane_counters` is the kCounterWords
 // block the chunk's pipeline counted in (S.r.counters), `total` = {rays of the call, chunks redone}:
 // launch_radiance_fold adds the chunk's rays to total[0] if its queues held, else 1 to total[1];

@@ -423,6 +423,28 @@ int rtk_render_last_critical_path(rtk_accel *accel, double *ms);
 /* Diagnostic, not part of the rendering contract: how many times frames, views and regions calls of this accel have zeroed its
  * counters with a fill of their own since it was built.  A steady megakernel frame issues none.  Needs no device. */
 int rtk_debug_counter_fills(rtk_accel *accel, uint64_t *fills);
+/* Diagnostics, not part of the rendering contract, of the launch order of this accel's FRAMES (rtk_render_frame*; not views or
+ * regions calls).  The order is re-sorted from the blocks' measured costs every few frames; a new order (the challenger) is judged
+ * behind its first frame against the one before it (the champion) by the device time of one frame under each, and the slower
+ * one is dropped.  No pixel depends on any of this.  Both calls synchronise the stream of the most recent frame.
+ * rtk_debug_order_judge: of one table -- the frames' (RTK_ORDER_TABLE_FRAMES, index 0), or that of launch `index` of a views call or
+ * of a regions call (a call is one launch unless it is cut) -- the sorts and judges enqueued since the accel was built, the verdicts given on the device (`taken`: the
+ * challenger became the champion; `rejected`: the champion's lists were copied back), and the two stored scores in ticks of the
+ * device's 100 MHz clock (0: none).  An accel that has rendered no megakernel frame reports zeros.
+ * RTK_COST_JUDGE_FORCE (read when the accel is built): 1 every challenger is taken, 2 none is. */
+typedef struct rtk_order_judge_stats {
+    uint64_t sorts, judges;
+    uint64_t taken, rejected;
+    uint32_t champion_ticks, challenger_ticks;
+    uint32_t units;                     /* units (8x8 pixel blocks) of the lists of the most recent frame */
+    int32_t read_set;                   /* which of the two sets of lists the next frame reads: 0 or 1 */
+} rtk_order_judge_stats;
+enum { RTK_ORDER_TABLE_FRAMES = 0, RTK_ORDER_TABLE_VIEWS = 1, RTK_ORDER_TABLE_REGIONS = 2 };
+int rtk_debug_order_judge(rtk_accel *accel, int32_t table, int32_t index, rtk_order_judge_stats *stats);
+/* One set of lists as the device holds it: order [units], header [4] = {workgroups, units, -, -}, workgroup list [units] (its first
+ * header[0] words are in use: a unit, or 0x80000000 | index into order of the first of four packed units).  `set`: 0 or 1.
+ * *n_words = 2 * units + 4; `words` is filled when it is non-null and `capacity` (in words) suffices, else RTK_ERR_INVALID. */
+int rtk_debug_order_lists(rtk_accel *accel, int32_t set, uint32_t *words, size_t capacity, size_t *n_words);
 /* after the all-gather: d_gathered = [world][buckets_per_rank][bucket][bucket][3] -> d_rgb [h][w][3] */
 int rtk_tiles_assemble_device(const rtk_accel *accel, const rtk_render_params *p, const float *d_gathered,
                               float *d_rgb, void *hip_stream);

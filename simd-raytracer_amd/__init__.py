@@ -33,6 +33,7 @@ TRACE_REPACK = 8        # batched intersect only: rays sorted by origin / direct
 OCC_CLEAR, OCC_OCCLUDED, OCC_STEP_LIMIT = 0, 1, 2     # rtk.h RTK_OCC_*: answers of the batched occlusion query
 OCCLUDED_MAX_STEPS = 1024                             # rtk.h RTK_OCCLUDED_MAX_STEPS
 REGIONS_IN_FRAME, REGIONS_PACKED = 0, 1               # rtk.h RTK_REGIONS_*: where render_regions puts a rectangle's pixels
+ORDER_TABLE_FRAMES, ORDER_TABLE_VIEWS, ORDER_TABLE_REGIONS = 0, 1, 2   # rtk.h RTK_ORDER_TABLE_*: whose launch order rtk_debug_order_judge reports
 MAX_REGIONS = 65536                                   # rectangles of one render_regions call at most
 
 # every symbol include/rtk.h declares (checked by tests/test_abi.py)
@@ -48,7 +49,7 @@ ABI_SYMBOLS = [
     "rtk_accel_update_vertices", "rtk_accel_update_vertices_device",
     "rtk_accel_update_geometry", "rtk_accel_update_geometry_device",
     "rtk_render_output_floats", "rtk_render_frame", "rtk_render_frame_device", "rtk_render_last_counters",
-    "rtk_render_last_critical_path", "rtk_debug_counter_fills",
+    "rtk_render_last_critical_path", "rtk_debug_counter_fills", "rtk_debug_order_judge", "rtk_debug_order_lists",
     "rtk_tiles_assemble_device", "rtk_camera_rays", "rtk_camera_rays_device",
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_render_regions", "rtk_render_regions_device",
@@ -142,6 +143,15 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class OrderJudgeStats(C.Structure):
+    """rtk.h rtk_order_judge_stats; 48 bytes."""
+    _fields_ = [("sorts", C.c_uint64), ("judges", C.c_uint64), ("taken", C.c_uint64), ("rejected", C.c_uint64),
+                ("champion_ticks", C.c_uint32), ("challenger_ticks", C.c_uint32), ("units", C.c_uint32), ("read_set", C.c_int32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class GBuffer(C.Structure):
     """rtk.h rtk_gbuffer: one pointer per plane, NULL = plane not wanted; 64 bytes."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "albedo", "bary", "tri", "mesh", "material")]
@@ -215,6 +225,9 @@ _L.rtk_render_last_counters.argtypes = [_vp, C.POINTER(Counters)]
 _L.rtk_render_last_critical_path.argtypes = [_vp, C.POINTER(C.c_double)]
 if hasattr(_L, "rtk_debug_counter_fills"):            # (an older build loaded through RTK_LIB_OVERRIDE for an A/B run has no such diagnostic)
     _L.rtk_debug_counter_fills.argtypes = [_vp, C.POINTER(C.c_uint64)]
+if hasattr(_L, "rtk_debug_order_judge"):              # (likewise)
+    _L.rtk_debug_order_judge.argtypes = [_vp, C.c_int32, C.c_int32, C.POINTER(OrderJudgeStats)]
+    _L.rtk_debug_order_lists.argtypes = [_vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
 _L.rtk_tiles_assemble_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]
 _L.rtk_camera_rays.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp]
 _L.rtk_camera_rays_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, _vp]
@@ -1004,6 +1017,26 @@ class KdTreeSimdAccel:
         n = C.c_uint64(0)
         _check(_L.rtk_debug_counter_fills(self._h, C.byref(n)))
         return int(n.value)
+
+    def order_judge(self, table: int = ORDER_TABLE_FRAMES, index: int = 0) -> dict:
+        """Diagnostic (rtk.h rtk_debug_order_judge): sorts and judges so far of this accel's frames (or of launch `index` of its views
+        / regions calls: ORDER_TABLE_VIEWS / _REGIONS), challengers taken and rejected, the champion's and the newest challenger's
+        score in 100 MHz ticks, the units of the lists and the set the next launch reads."""
+        st = OrderJudgeStats()
+        _check(_L.rtk_debug_order_judge(self._h, table, index, C.byref(st)))
+        return st.as_dict()
+
+    def order_lists(self, which: int):
+        """Diagnostic (rtk.h rtk_debug_order_lists): set `which` (0 or 1) of the frames' launch lists as the device holds it ->
+        (order [units], header [4], workgroup list [units]) as uint32 arrays, or None before any list exists."""
+        n = C.c_size_t(0)
+        _check(_L.rtk_debug_order_lists(self._h, which, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        words = np.empty(n.value, np.uint32)
+        _check(_L.rtk_debug_order_lists(self._h, which, words.ctypes.data, words.size, C.byref(n)))
+        units = (n.value - 4) // 2
+        return words[:units], words[units:units + 4], words[units + 4:]
 
     def assemble_device(self, cfg: RenderConfig, d_gathered_ptr: int, d_rgb_ptr: int, stream: int = 0) -> None:
         p = cfg.to_c()

@@ -18,6 +18,7 @@
 #include "build.hpp"
 #include "dev_mem.hpp"
 #include "frame_plan.hpp"
+#include "order_judge.hpp"
 #include "update_plan.hpp"
 
 // Environment knobs (all optional).  Read ONCE, when an accel is built: nothing on the launch path
@@ -30,6 +31,9 @@ struct rtk_knobs {
     bool auto_trials = true;                                // RTK_AUTO_TRIALS
     bool cost_feedback = true;                              // RTK_COST_FEEDBACK
     unsigned resort_every = 16;                             // RTK_COST_RESORT_EVERY
+    unsigned resort_max = 128;                              // RTK_COST_RESORT_MAX: the interval doubles from a shape's third sort on, up to this (0: never; frame_plan.hpp)
+    bool judge = true;                                      // RTK_COST_JUDGE: a newly sorted launch order is kept only if its first frame was not slower (order_judge.hpp)
+    int judge_force = rtk::kJudgeByScore;                   // RTK_COST_JUDGE_FORCE: 1 every new order is taken, 2 the champion is always kept (the tests)
     uint32_t light_cycles = 140000u;                        // RTK_LIGHT_BELOW_CYCLES
     uint32_t order_floor_cycles = 20000u;                   // RTK_ORDER_FLOOR_CYCLES
     bool batch_scalar_surv = false;                         // RTK_BATCH_SCALAR_SURV: the same in the batched intersect
@@ -70,7 +74,11 @@ struct rtk_knobs {
         if (geti("RTK_BUNDLE_CULL", v)) k.bundle_cull = v != 0;
         if (geti("RTK_AUTO_TRIALS", v)) k.auto_trials = v != 0;
         if (geti("RTK_COST_FEEDBACK", v)) k.cost_feedback = v != 0;
-        if (geti("RTK_COST_RESORT_EVERY", v) && v > 0) k.resort_every = unsigned(v);
+        // (an interval that is asked for is kept as it is asked for: no stretching, unless a cap is asked for as well)
+        if (geti("RTK_COST_RESORT_EVERY", v) && v > 0) { k.resort_every = unsigned(v); k.resort_max = 0; }
+        if (geti("RTK_COST_RESORT_MAX", v) && v >= 0 && v <= (1l << 30)) k.resort_max = unsigned(v);
+        if (geti("RTK_COST_JUDGE", v)) k.judge = v != 0;
+        if (geti("RTK_COST_JUDGE_FORCE", v) && v >= rtk::kJudgeByScore && v <= rtk::kJudgeAlwaysKeep) k.judge_force = int(v);
         if (geti("RTK_LIGHT_BELOW_CYCLES", v) && v >= 0) k.light_cycles = uint32_t(v);
         if (geti("RTK_ORDER_FLOOR_CYCLES", v) && v >= 0) k.order_floor_cycles = uint32_t(v);
         if (geti("RTK_REPACK", v)) k.repack = v != 0;
@@ -220,6 +228,10 @@ struct rtk_cost_feedback {
     // number of workgroups in order's workgroup list, read back behind the sort that made it (pinned host word + event)
     rtk::PinBuf<uint32_t> nwgs_host;
     rtk::DevEvent nwgs_ev;
+    // [kJudgeWords] order_judge.hpp: the newest frame's stamp, the champion's and the challenger's score, the counts; zeroed when made
+    rtk::DevBuf<uint32_t> judge;
+    size_t list_units = 0;           // units of the lists as the newest launch laid them out (the header sits behind `list_units` words of order)
+    uint64_t sorts = 0, judges = 0;  // k_order_by_cost / k_judge_order launches enqueued for this table so far (rtk_debug_order_judge)
 
     void forget() { state.forget(); }
 };
@@ -448,6 +460,14 @@ inline void forget_orders(rtk_accel *a, unsigned keep = 0u) {
     if (!(keep & kKeepViewOrders)) for (rtk_cost_feedback &f : a->fb_views) f.forget();
     for (rtk_cost_feedback &f : a->fb_regions) f.forget();
     if (!(keep & kKeepTrial)) a->trial.abandon();
+}
+
+// The blocks' costs have changed but the picture's silhouettes have not: the orders stay, their re-sort schedules start over.
+inline void restart_order_schedules(rtk_accel *a) {
+    const unsigned every = a->knobs.resort_every;
+    a->fb.state.restart_schedule(every);
+    for (rtk_cost_feedback &f : a->fb_views) f.state.restart_schedule(every);
+    for (rtk_cost_feedback &f : a->fb_regions) f.state.restart_schedule(every);
 }
 
 // api_update.hip

@@ -23,9 +23,12 @@ int reserve_lights(rtk_accel *a, size_t n) {
     return RTK_OK;
 }
 
-// every block's cost scales with the number of lights; their positions leave the silhouettes where they are (rtk.h)
+// every block's cost scales with the number of lights; their positions leave the silhouettes where they are (rtk.h), but move the
+// shadow edges and with them the costs of the blocks they cross: the orders stay in use, and their schedules start over, so that
+// the list in use is re-sorted and judged again within RTK_COST_RESORT_EVERY frames of its last sort (behind the next frame if it is
+// older already) and not up to RTK_COST_RESORT_MAX later -- however often the call comes, it never puts a sort off
 void lights_changed(rtk_accel *a, size_t n_before) {
-    if (a->scene.lights.size() == n_before) return;
+    if (a->scene.lights.size() == n_before) { restart_order_schedules(a); return; }
     forget_orders(a, kKeepTrial);
 }
 

@@ -61,11 +61,17 @@ struct EngineTrial {
 
 // The HIP-free half of a set of cost-feedback tables (rtk_cost_feedback): what they hold and how old it is.
 struct OrderState {
-    struct Knobs { bool first_frame_prior; unsigned resort_every; };
+    // resort_max: the largest number of frames between two sorts.  Above resort_every, the interval doubles with every sort from the
+    // shape's third on until it gets there (resort_every 16: sorts at frames 2, 18, 34, 66, 130, ...): the first lists of a shape are
+    // made from the costs of its first frames, a list that has been judged against its successors a few times is worth keeping
+    // longer (order_judge.hpp).  0, or not above resort_every: every resort_every frames, as before.
+    struct Knobs { bool first_frame_prior; unsigned resort_every; unsigned resort_max = 0; };
     // prior: launch k_block_prior (into set 0).  resort: this frame is the first of a new list -- k_order_by_cost is launched in front of
     // it into read_set (sort_front), unless the frame before launched it behind itself.  use_order: give the kernel set read_set's lists.
     // sort_behind: the next frame of this shape starts a new list: launch k_order_by_cost behind this frame's kernel, into write_set.
-    struct Step { bool prior, resort, use_order, sort_front, sort_behind; int read_set, write_set; };
+    // judge: this frame is the first of a list that was sorted behind the frame before (the challenger), and the other set still holds
+    // the list that frame ran (the champion): the caller launches the judge behind this frame (order_judge.hpp) and calls rearm_count().
+    struct Step { bool prior, resort, use_order, sort_front, sort_behind; int read_set, write_set; bool judge = false; };
     size_t units = 0;                  // capacity of the tables, never shrunk
     uint64_t sig[5] = {0, 0, 0, 0, 0};
     bool valid = false;                // cost holds the costs of a frame of shape sig
@@ -79,8 +85,26 @@ struct OrderState {
     // its kernel is done no longer waits for a sort first).  Only a shape's first sort, which has no list to go on with, is in front.
     int set = 0;                       // the set the frames read
     bool presorted = false;            // the other set's list was launched behind the previous frame
+    unsigned sorts = 0;                // sorts of this shape since its schedule started over (forget(), another shape)
 
-    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; set = 0; presorted = false; }
+    void forget() { valid = false; order_valid = false; age = 0; nwgs_pending = false; nwgs_known = false; set = 0; presorted = false; sorts = 0; }
+
+    // The costs have changed under a list that stays in use (lights moved or re-coloured at an equal count: api_state.hip): the
+    // intervals start over at resort_every, but nothing is forgotten: the order, the sets and the known count stay.  The call can
+    // bring a sort nearer and never puts one off, however often it comes (an animated light calls it before every frame): the
+    // list's age stays, and a list already older than resort_every is sorted behind the very next frame, from the costs that
+    // frame stores under the new lights.  (A sort already launched behind the previous frame is taken by the next frame as planned.)
+    void restart_schedule(unsigned resort_every) {
+        sorts = 0;
+        if (!presorted && resort_every > 0 && age >= resort_every) age = resort_every - 1;
+    }
+
+    // frames the current list is used for
+    unsigned interval(const Knobs &k) const {
+        uint64_t iv = k.resort_every;
+        for (unsigned i = 3; i <= sorts && iv < k.resort_max; ++i) iv *= 2;
+        return (k.resort_max > k.resort_every && iv > k.resort_max) ? k.resort_max : unsigned(iv);
+    }
 
     // RTK_TRACE_AUTO for the megakernel: four waves per pixel block when there are enough blocks to fill the chip several times
     // over, eight when there are few (a rank of a sharded frame, a small image: the frame is then as long as its most expensive block).
@@ -112,19 +136,21 @@ struct OrderState {
     // A caller whose launches then fail calls forget().
     Step step(const uint64_t s[5], int mode, bool stats, bool regions, const Knobs &k) {
         const bool same_shape = valid && std::memcmp(s, sig, sizeof(sig)) == 0;
-        if (!same_shape) { order_valid = false; set = 0; presorted = false; }
-        Step r = {!same_shape && k.first_frame_prior && mode == RTK_TRACE_GROUP4 && !stats && !regions, false, false, false, false, 0, 0};
+        if (!same_shape) { order_valid = false; set = 0; presorted = false; sorts = 0; }
+        Step r = {!same_shape && k.first_frame_prior && mode == RTK_TRACE_GROUP4 && !stats && !regions, false, false, false, false, 0, 0, false};
         if (same_shape) {
-            r.resort = !order_valid || age >= k.resort_every;
+            r.resort = !order_valid || age >= interval(k);
             // (how many workgroups the new list has is known on the host a frame or two later)
             if (r.resort) {
                 r.sort_front = !presorted;
+                r.judge = presorted;
                 if (presorted) set ^= 1;
                 presorted = false;
                 order_valid = true; age = 0; nwgs_known = false; nwgs_pending = true;
+                sorts += 1;
             }
             age += 1;
-            r.sort_behind = age >= k.resort_every;      // (the next frame of this shape re-sorts: its list is made behind this one)
+            r.sort_behind = age >= interval(k);      // (the next frame of this shape re-sorts: its list is made behind this one)
             presorted = r.sort_behind;
         }
         r.use_order = r.prior || same_shape;
@@ -133,6 +159,11 @@ struct OrderState {
         valid = true;
         return r;
     }
+
+    // A judge has been enqueued behind this frame: it may put the champion's list, of another length, back into the set the frames
+    // read, so the length read back behind the sort says nothing any more.  The caller enqueues a fresh read-back behind the judge;
+    // until that one is seen complete the launches cover every block again -- a launch shorter than the list would skip blocks.
+    void rearm_count() { if (order_valid) { nwgs_pending = true; nwgs_known = false; } }
 
     // a frame that uses the order: is the read-back of its workgroup count still to be seen complete (one event query)?
     bool awaits_count() const { return order_valid && nwgs_pending; }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "order_judge.hpp"
 #include "trace.hip.hpp"
 #include "shade.hip.hpp"
 
@@ -1059,7 +1060,14 @@ __device__ __forceinline__ uint32_t cost_bin(uint32_t c) {                 // 8 
 }
 __global__ __launch_bounds__(1024) void k_order_by_cost(const uint32_t *cost, uint8_t *bins, uint32_t *order, uint32_t *wg_list,
                                                         uint32_t *hdr, uint32_t n, uint32_t light_below, uint32_t floor_below,
-                                                        uint32_t pack) {
+                                                        uint32_t pack, uint32_t *judge, int champion) {
+    // The frame in front of this launch ran the list in use, the champion: from its stamp to now is that list's score (order_judge.hpp),
+    // refreshed by every sort.  A shape's first sort has no list behind it: no champion.
+    if (judge != nullptr && threadIdx.x == 0u) {
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long t0 = *reinterpret_cast<const unsigned long long *>(judge + kJudgeStampLo);
+        if (champion != kChampionLeave) judge[kJudgeChampion] = champion == kChampionScore ? judge_score(t0, now) : 0u;
+    }
     __shared__ uint32_t hist[256];
     __shared__ uint32_t start[256];
     __shared__ uint32_t wg_hist[2][256], wg_base[2][256];
@@ -1169,10 +1177,73 @@ __global__ __launch_bounds__(1024) void k_order_by_cost(const uint32_t *cost, ui
 }  // namespace dev
 
 hipError_t launch_order_by_cost(const uint32_t *cost, uint8_t *bins, uint32_t *order, uint32_t *wg_list, uint32_t *hdr, uint32_t n,
-                                uint32_t light_below, uint32_t floor_below, uint32_t pack, hipStream_t s) {
+                                uint32_t light_below, uint32_t floor_below, uint32_t pack, hipStream_t s, uint32_t *judge, int champion) {
     if (n == 0u) return hipSuccess;
     if (pack == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dev::k_order_by_cost, dim3(1), dim3(1024), 0, s, cost, bins, order, wg_list, hdr, n, light_below, floor_below, pack);
+    hipLaunchKernelGGL(dev::k_order_by_cost, dim3(1), dim3(1024), 0, s, cost, bins, order, wg_list, hdr, n, light_below, floor_below, pack,
+                       judge, champion);
+    return hipGetLastError();
+}
+
+namespace dev {
+__global__ __launch_bounds__(64) void k_stamp(unsigned long long *stamp) {
+    if (threadIdx.x == 0u) *stamp = __builtin_amdgcn_s_memrealtime();
+}
+}  // namespace dev
+
+hipError_t launch_stamp(uint32_t *judge, hipStream_t s) {
+    if (judge == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_stamp, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned long long *>(judge + kJudgeStampLo));
+    return hipGetLastError();
+}
+
+// Keep or take (order_judge.hpp), behind the first frame of a newly sorted list.  One workgroup: the two sets of lists of a 1080p
+// frame are 260 KB each, and a rejected challenger is the rarer case.  Thread 0 reads the clock before anything else, so the score
+// ends where the champion's does: at the start of the kernel behind the frame.
+namespace dev {
+__global__ __launch_bounds__(1024) void k_judge_order(uint32_t *judge, uint32_t *read_set, const uint32_t *other_set, uint32_t words, int force) {
+    __shared__ uint32_t take_sh;
+    if (threadIdx.x == 0u) {
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long t0 = *reinterpret_cast<const unsigned long long *>(judge + kJudgeStampLo);
+        const Verdict v = judge_order({judge[kJudgeChampion], judge_score(t0, now)}, force);
+        judge[kJudgeChampion] = v.after.champion;
+        judge[kJudgeChallenger] = v.after.challenger;
+        judge[v.take ? kJudgeTaken : kJudgeRejected] += 1u;
+        take_sh = v.take ? 1u : 0u;
+    }
+    __syncthreads();
+    if (take_sh != 0u) return;
+    // the champion's lists back into the set the frames read: 16 bytes per thread and step where both runs allow it
+    uint32_t done = 0u;
+    if (((reinterpret_cast<uintptr_t>(read_set) | reinterpret_cast<uintptr_t>(other_set)) & 15u) == 0u) {
+        const uint32_t quads = words >> 2;
+        const uint4 *src = reinterpret_cast<const uint4 *>(other_set);
+        uint4 *dst = reinterpret_cast<uint4 *>(read_set);
+        constexpr uint32_t kBatch = 4;                                      // loads in flight per thread: one workgroup waits for latency
+        for (uint32_t base = 0; base < quads; base += blockDim.x * kBatch) {
+            uint4 v[kBatch];
+#pragma unroll
+            for (uint32_t k = 0; k < kBatch; ++k) {
+                const uint32_t i = base + k * blockDim.x + threadIdx.x;
+                if (i < quads) v[k] = src[i];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kBatch; ++k) {
+                const uint32_t i = base + k * blockDim.x + threadIdx.x;
+                if (i < quads) dst[i] = v[k];
+            }
+        }
+        done = quads << 2;
+    }
+    for (uint32_t i = done + threadIdx.x; i < words; i += blockDim.x) read_set[i] = other_set[i];
+}
+}  // namespace dev
+
+hipError_t launch_judge_order(uint32_t *judge, uint32_t *read_set, const uint32_t *other_set, uint32_t words, int force, hipStream_t s) {
+    if (judge == nullptr || read_set == nullptr || other_set == nullptr || read_set == other_set) return hipErrorInvalidValue;
+    if (words == 0u) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_judge_order, dim3(1), dim3(1024), 0, s, judge, read_set, other_set, words, force);
     return hipGetLastError();
 }
 

@@ -135,9 +135,21 @@ hipError_t launch_render(const dev::RenderArgs &A, int mode, bool stats, bool fo
 // blocks cheaper than floor_below are not ordered among themselves).  Blocks costlier than light_below (units of 16 cycles;
 // 0 = all) get a workgroup each, the rest are packed `pack` to a workgroup; wg_list[0..hdr[0]) = the workgroups by expected
 // duration, longest first (see RenderArgs::wg_list); hdr[1] = n
+// judge (null, or the table's judge block, order_judge.hpp): `champion` says what becomes of the
+// champion's score: cleared (there is no champion), the device time of the frame in front of this launch (from its stamp to now), or left
+enum : int { kChampionNone = 0, kChampionScore = 1, kChampionLeave = 2 };
 hipError_t launch_order_by_cost(const uint32_t *cost, uint8_t *bins /* [n] scratch */, uint32_t *order, uint32_t *wg_list /* [n] */,
                                 uint32_t *hdr /* [2] */, uint32_t n, uint32_t light_below, uint32_t floor_below, uint32_t pack,
-                                hipStream_t s);
+                                hipStream_t s, uint32_t *judge = nullptr, int champion = kChampionNone);
+// In front of a frame whose list is scored (the last frame of a segment, the first of a challenger): one thread stores the 100 MHz
+// device clock into the judge block's stamp.  The kernel behind the frame -- the re-sort or the judge -- reads its own clock and has
+// the device time of a frame under the list in use.  (The same store by workgroup 0 of k_render itself costs the lean GROUP4 build
+// a spilled VGPR and 8 B of scratch per lane: DESIGN.md 4.3.)
+hipError_t launch_stamp(uint32_t *judge, hipStream_t s);
+// Behind the first frame of a newly sorted list (the challenger, in `read_set`): one workgroup scores that frame, asks
+// order_judge.hpp's rule and, if the champion stays, copies the champion's `words` words (order, header, workgroup list: one run)
+// from `other_set` over the challenger's.  `force`: kJudgeByScore, or the verdict to give whatever the scores say.
+hipError_t launch_judge_order(uint32_t *judge, uint32_t *read_set, const uint32_t *other_set, uint32_t words, int force, hipStream_t s);
 // first frame of a shape: the launch list (order, wg_list, hdr as launch_order_by_cost leaves them) from the camera rays alone:
 // blocks whose centre ray hits a reflective / refractive surface, then blocks that enter the tree, then background blocks `pack`
 // to a workgroup.  cls [n_units] and scratch [6] are work space.

@@ -60,7 +60,7 @@ struct rtk_knobs {
     bool first_frame_prior = true;                          // RTK_FIRST_FRAME_PRIOR: launch order of a shape's first frame from k_block_prior
     bool fast_occluders = true;                             // RTK_FAST_OCCLUDERS: RTK_TRAVERSAL_FAST answers occlusion through transmissive surfaces from the opaque triangles alone
     bool camera_keeps_order = false;                        // RTK_CAMERA_KEEPS_ORDER: rtk_accel_set_camera leaves the cost-feedback launch order of the previous camera in place
-    size_t views_launch_units = 131072;                     // RTK_VIEWS_LAUNCH_UNITS: pixel blocks of one rtk_render_views launch (api_frame.hip; a test lowers it)
+    size_t views_launch_units = 131072;                     // RTK_VIEWS_LAUNCH_UNITS: pixel blocks of one rtk_render_views launch (api_views.hip; a test lowers it)
     bool traversal_fast = false;                            // RTK_TRAVERSAL_FAST: front-to-back leaf order (rtk.h; NOT the parity mode)
     size_t adaptive_chunk_pixels = size_t(1) << 20;         // RTK_ADAPTIVE_CHUNK_PIXELS: pixels of one chunk of an adaptive round (adaptive_plan.hpp; a test lowers it)
 
@@ -218,6 +218,22 @@ struct StreamBufs {
     DevBuf<uint32_t> ctrl, node_bins, hit_bins, node_order, hit_order;
     void reset() { rays.reset(); nodes.reset(); hits.reset(); contrib.reset(); ctrl.reset(); node_bins.reset(); hit_bins.reset(); node_order.reset(); hit_order.reset(); }
 };
+// The streaming pipeline's workspace of an accel (rtk_accel::stream), grown on demand; its operations are api_stream.hip's
+// (render_internal.hpp).  One set of queues per sample lane (stream.hpp kStreamLanes); `ws` = lane 0; all lanes share lane 0's
+// sumbuf.  bufs / sumbuf own the memory, ws / lane_ws are the views of it that the kernels take by value.
+struct StreamWorkspace {
+    StreamBufs bufs[dev::kStreamLanes];
+    DevBuf<float> sumbuf;
+    dev::StreamWs ws = {};
+    dev::StreamWs lane_ws[dev::kStreamLanes] = {};
+    StreamWsShape shape;                                   // what they have room for (frame_plan.hpp)
+    hipStream_t lane_stream[dev::kStreamLanes] = {};       // the process's (api_stream.hip LaneStreams): not freed with an accel
+    DevEvent lane_done[dev::kStreamLanes];
+    DevEvent lane_fork;
+    struct SideEvents { DevEvent ready[2], done[2]; } lane_side_ev[dev::kStreamLanes];
+    StreamSide lane_side[dev::kStreamLanes] = {};          // k_shadow side streams of every lane (the process's) and views of lane_side_ev
+    LastUse last;                                          // of a STREAM frame or a radiance batch
+};
 }  // namespace rtk
 
 // Per-pixel-block cost of the last frame of shape `state.sig`, and the launch order made from it.
@@ -266,30 +282,18 @@ struct rtk_accel {
     uint64_t counter_fills = 0;                    // fills of the block in use issued so far (rtk_debug_counter_fills)
     uint32_t occl_n_leaves = 0;
     bool occl_on = false;
-    // ---- ws_* / lane_*: streaming-pipeline workspace (api_frame.hip ensure_stream_ws; grown on demand)
-    // one per sample lane (stream.hpp kStreamLanes); `ws` = lane 0; all lanes share lane 0's sumbuf.  ws_bufs / ws_sumbuf own the
-    // memory, ws / ws_lane are the views of it that the kernels take by value.
-    rtk::StreamBufs ws_bufs[rtk::dev::kStreamLanes];
-    rtk::DevBuf<float> ws_sumbuf;
-    rtk::dev::StreamWs ws = {};
-    rtk::dev::StreamWs ws_lane[rtk::dev::kStreamLanes] = {};
-    rtk::StreamWsShape ws_shape;                                // what they have room for (frame_plan.hpp)
-    hipStream_t lane_stream[rtk::dev::kStreamLanes] = {};       // the process's (api_frame.hip LaneStreams): not freed with an accel
-    rtk::DevEvent lane_done[rtk::dev::kStreamLanes];
-    rtk::DevEvent lane_fork;
-    struct SideEvents { rtk::DevEvent ready[2], done[2]; } lane_side_ev[rtk::dev::kStreamLanes];
-    rtk::StreamSide lane_side[rtk::dev::kStreamLanes] = {};     // k_shadow side streams of every lane (the process's) and views of lane_side_ev
-    rtk::LastUse ws_last;                                       // of a STREAM frame or a radiance batch
-    // ---- fb / fb_views: cost feedback (megakernel frames, api_frame.hip render_megakernel).  Frames have one set of tables;
+    // ---- stream: the streaming pipeline's queues, lanes and events (api_stream.hip ensure_stream_ws)
+    rtk::StreamWorkspace stream;
+    // ---- fb / fb_views: cost feedback (megakernel frames, api_order.hip render_megakernel).  Frames have one set of tables;
     // rtk_render_views has one per launch of a call (a call is cut into launches of whole views), so that a caller who
     // alternates frames and views calls keeps the order of both.
     rtk_cost_feedback fb;
     std::vector<rtk_cost_feedback> fb_views;
-    // ---- views_*: rtk_render_views (api_frame.hip).  The host variant's staging (view table, output) grows and never shrinks.
+    // ---- views_*: rtk_render_views (api_views.hip).  The host variant's staging (view table, output) grows and never shrinks.
     rtk::DevBuf<rtk_view> views_tab;
     rtk::DevBuf<float> views_out;
     rtk::DevBuf<unsigned long long> d_views_counters;   // [kCounterWords] the call's totals while its frames / launches run
-    // ---- rg_* / fb_regions: rtk_render_regions (api_frame.hip).  One set of cost tables per launch of a call, as for views; they are
+    // ---- rg_* / fb_regions: rtk_render_regions (api_regions.hip).  One set of cost tables per launch of a call, as for views; they are
     // reused only by a call whose rectangle list, layout and frame width equal the previous call's (rg_rects, rg_layout, rg_width), and
     // then the table on the device is that call's too and is not uploaded again.
     std::vector<rtk_cost_feedback> fb_regions;
@@ -339,7 +343,7 @@ struct rtk_accel {
     rtk::DevBuf<rtk_ray> oc_rays;
     rtk::DevBuf<float> oc_max_t;
     rtk::DevBuf<uint8_t> oc_out;
-    // ---- rad_*: batched radiance (rtk_accel_radiance, api_frame.hip)
+    // ---- rad_*: batched radiance (rtk_accel_radiance, api_radiance.hip)
     // one counter block per lane for a chunk's pipeline, then {rays, chunks redone} of the call (counters.hpp)
     rtk::DevBuf<unsigned long long> d_rad_counters;
     // staging of the host variant: grows, never shrinks
@@ -483,30 +487,5 @@ int ensure_update_static(rtk_accel *a);
 void dense_texture_slots(rtk_accel *a);
 const std::vector<float> &host_vert_uv(rtk_accel *a);
 int ensure_vert_uv_dev(rtk_accel *a);
-// api_frame.hip
-int frame_geom(const rtk_accel *a, const rtk_render_params *p, FrameGeom &g);
-rtk_view accel_camera(const rtk_accel *a);                                                       // the camera later frames are rendered from
-void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A);   // the camera half of the launch arguments
-int ensure_stream_ws(rtk_accel *a, size_t pixels, size_t nodes, size_t lights, bool need_sum, int lanes);
-hipError_t zero_counters(rtk_accel *a, hipStream_t s);                                           // the block in use starts at zero; no steady frame behind it
-void record_last(rtk_accel *a, hipStream_t s, bool stats, uint64_t primary);                     // what rtk_render_last_counters goes by
-int radiance_device_impl(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *p,
-                         float *d_rgb, hipStream_t s, uint32_t *n_chunks_out);                   // rtk_accel_radiance_device behind its checks
-void free_stream_ws(rtk_accel *a);
-// (the streaming pipeline's setup and its lanes are api_frame_noise.hip's as well)
-struct StreamSetup {
-    dev::StreamArgs S;
-    int deep_level, deep_mode, sort_from, slices;      // launch_stream_sample's
-    size_t factor, node_bytes, budget;                 // stream_plan.hpp's
-};
-StreamSetup stream_args(const rtk_accel *a, const dev::RenderArgs &A, int diffuse_rays, bool forks);
-int claim_stream_ws(rtk_accel *a, hipStream_t s);                                                // the queues' previous user finishes first, on the device
-int release_stream_ws(rtk_accel *a, hipStream_t s);
-int fork_lanes(rtk_accel *a, int lanes, hipStream_t s);                                          // lanes 1.. start behind everything enqueued on `s`
-int join_lanes(rtk_accel *a, int lanes, hipStream_t s);                                          // `s` continues behind every lane's last launch
-dev::RenderArgs frame_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, const rtk_view &cam, float *d_out);
-// api_adaptive.hip
-int adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,
-                         uint32_t *d_samples, float *d_noise, hipStream_t s);                    // rtk_render_adaptive_device behind its checks
 
 }  // namespace rtk

@@ -1,13 +1,13 @@
 // C-ABI, rtk_render_adaptive: a frame whose 8x8 pixel blocks stop taking samples once their noise estimate is under the caller's
 // threshold.  The arithmetic of the call -- refusals, checkpoints, the chunk walk, the count word -- is adaptive_plan.hpp; the
-// kernels are adaptive.hip; the colours come from the streaming pipeline of rtk_accel_radiance (radiance_device_impl), as on the
+// kernels are adaptive.hip; the colours come from the streaming pipeline of rtk_accel_radiance (radiance_frame_chunk), as on the
 // streaming path of rtk_render_regions.  Nothing here touches the accel's camera, its cost tables, the regions table or
 // RTK_TRACE_AUTO's verdict; the counters are the call's, as after a regions call.
 #include <cstring>
 #include <mutex>
 
-#include "accel.hpp"
 #include "adaptive.hpp"
+#include "render_internal.hpp"
 
 using namespace rtk;
 
@@ -41,7 +41,7 @@ int ensure_adaptive_ws(rtk_accel *a, size_t pixels, size_t blocks, size_t chunk)
 }  // namespace
 
 // The rounds of a call.  Everything is enqueued on `s`; the host waits once per round that is not the last, for the count word.
-// (api_frame_noise.hip's as well, for the call it redoes after a queue overflow: accel.hpp)
+// (api_frame_noise.hip redoes a call whose queues overflowed through this)
 int rtk::adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,
                          uint32_t *d_samples, float *d_noise, hipStream_t s) {
     const uint64_t pixels = uint64_t(g.width) * g.height, blocks = adaptive_blocks(g.width, g.height);
@@ -53,10 +53,7 @@ int rtk::adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rt
     dev::RenderArgs A;
     std::memset(&A, 0, sizeof(A));
     camera_args(accel_camera(a), p, g, A);
-    rtk_radiance_params rp;
-    rp.max_ray_depth = p->max_ray_depth; rp.diffuse_rays = p->diffuse_rays; rp.seed = p->seed; rp.sample = 0;
-    rp.shadow_bias = p->shadow_bias; rp.reflection_bias = p->reflection_bias; rp.refraction_bias = p->refraction_bias;
-    rp.cull = 1; rp.trace_mode = RTK_TRACE_STREAM;
+    rtk_radiance_params rp = frame_radiance_params(p);
 
     uint32_t *const list[2] = {a->ad_list.get(), a->ad_list.get() + pixels};
     uint32_t *const blist[2] = {a->ad_blocks.get(), a->ad_blocks.get() + blocks};
@@ -82,8 +79,7 @@ int rtk::adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rt
             for (int32_t smp = done; smp < next; ++smp) {
                 RTK_HIP_AS(launch_adaptive_rays(A, smp, ids, cn, a->ad_rays.get(), s), "launch k_adaptive_rays");
                 rp.sample = smp;
-                RTK_TRY(radiance_device_impl(a, a->ad_rays.get(), ids, cn, &rp, a->ad_rgb.get(), s, nullptr));
-                RTK_HIP_AS(launch_add_word(counters_now(a), a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes) + kRadianceRays, s), "launch k_add_word");
+                RTK_TRY(radiance_frame_chunk(a, a->ad_rays.get(), ids, cn, &rp, a->ad_rgb.get(), s));
                 RTK_HIP_AS(launch_adaptive_accumulate(ids, cn, a->ad_rgb.get(), d_rgb, a->ad_s1.get(), a->ad_s2.get(), pixels, smp == 0, s),
                            "launch k_adaptive_accumulate");
             }

@@ -1,5 +1,5 @@
 // C-ABI, rtk_render_frame_noise: a frame of a fixed sample count together with the noise plane rtk_denoise_frame weights by.  The
-// frame is an RTK_TRACE_STREAM frame (render_stream's plan, lanes, fork and join: api_frame.hip), with k_frame_moments
+// frame is an RTK_TRACE_STREAM frame (launch_stream_frame, the launches render_stream makes: api_stream.hip), with k_frame_moments
 // (frame_noise.hip) behind every batch's depth-0 k_combine; the refusals and the workspace are frame_noise_plan.hpp.  A frame whose
 // queues overflowed is not handed to the megakernel, which has no statistic: the call reads the overflow word back and redoes
 // itself as an adaptive render that never stops early (api_adaptive.hip), which gives the same rgb, noise, rays and primary.
@@ -7,9 +7,8 @@
 // are left as an RTK_TRACE_STREAM frame leaves them.
 #include <mutex>
 
-#include "accel.hpp"
 #include "frame_noise_plan.hpp"
-#include "stream_plan.hpp"
+#include "render_internal.hpp"
 
 using namespace rtk;
 
@@ -40,50 +39,17 @@ int stream_frame_noise(rtk_accel *a, const rtk_render_params *p, const FrameGeom
                        bool *overflowed) {
     const size_t pixels = size_t(g.width) * g.height;
     RTK_TRY(ensure_moments_ws(a, pixels));
-    const bool forks = scene_forks(a, p->diffuse_rays);
     // the counters: what an RTK_TRACE_STREAM frame does with them (render_frame_body): no steady frame behind it, one fill
     (void)a->cnt.frame(s, false);
     RTK_HIP(zero_counters(a, s));
-    const dev::RenderArgs A = frame_args(a, p, g, accel_camera(a), d_rgb);
-    StreamSetup u = stream_args(a, A, p->diffuse_rays, forks);
-    const size_t n_root = g.blocks() * 64;
-    const size_t nodes_per_sample = n_root * u.factor + 4096;
-    const FramePlan plan = plan_frame_batches(g.sample_end - g.sample_begin, nodes_per_sample, u.node_bytes, u.budget,
-                                              a->knobs.stream_lanes, a->knobs.stream_batch);
-    const int batch = plan.batch, lanes = plan.lanes;
-    RTK_TRY(ensure_stream_ws(a, pixels, nodes_per_sample * size_t(batch), a->scene.lights.size(), true, lanes));
-    dev::StreamArgs &S = u.S;
-    S.ws = a->ws; S.n_root = uint32_t(n_root); S.n_level0 = uint32_t(n_root);
-    S.n_lanes = uint32_t(lanes);
-    for (int j = 0; j < dev::kStreamLanes; ++j) S.lane_overflow[j] = a->ws_lane[j < lanes ? j : 0].ctrl + dev::kCtrlOverflow;
     StreamMoments M;
     M.s1 = a->ad_s1.get(); M.s2 = a->ad_s2.get(); M.noise = d_noise; M.n_pixels = uint32_t(pixels);
-    // the queues and the sums belong to the accel: their previous users finish first, on the device, before the lanes fork from `s`
-    RTK_TRY(claim_stream_ws(a, s));
+    // the sums belong to the accel, as the queues do: their previous user finishes first, on the device, before the lanes fork from `s`
     RTK_HIP(a->ad_last.wait_previous(s));
-    for (int j = 0; j < lanes; ++j) RTK_HIP(hipMemsetAsync(a->ws_lane[j].ctrl, 0, dev::kCtrlWords * sizeof(uint32_t), s));
-    RTK_TRY(fork_lanes(a, lanes, s));
-    const bool side = a->knobs.stream_side && lanes <= 2 && batch * lanes <= a->knobs.stream_side_below;
-    for (int i = 0; i < plan.n_launch; ++i) {
-        const int j = i % lanes;
-        S.sample = g.sample_begin + i * batch;
-        S.n_batch = uint32_t(g.sample_end - S.sample < batch ? g.sample_end - S.sample : batch);
-        S.n_level0 = uint32_t(n_root) * S.n_batch;
-        S.ws = a->ws_lane[j];
-        const hipStream_t ls = j == 0 ? s : a->lane_stream[j];
-        // ordering events: a batch's depth-0 k_combine and k_frame_moments wait for the previous batch's, so sums and statistic stay in sample order
-        const hipEvent_t wait = (lanes > 1 && i > 0) ? a->lane_done[(i - 1) % lanes].get() : nullptr;
-        const hipEvent_t done = lanes > 1 ? a->lane_done[j].get() : nullptr;
-        RTK_HIP_AS(launch_stream_sample(S, false, u.deep_level, u.deep_mode, u.sort_from, ls, wait, done, side ? &a->lane_side[j] : nullptr,
-                                        u.slices, M), "launch streaming pipeline");
-    }
-    RTK_TRY(join_lanes(a, lanes, s));
-    S.ws = a->ws;
-    // tail: the lanes' overflow words folded into lane 0's (the counters of an overflowed frame mean nothing and are zeroed), and that
-    // word on its way to the host.  No megakernel behind it: it has no statistic.
-    RTK_HIP_AS(launch_stream_overflow_reset(S, s), "launch overflow reset");
-    RTK_HIP(hipMemcpyAsync(a->fn_overflow_host.get(), a->ws.ctrl + dev::kCtrlOverflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    RTK_TRY(release_stream_ws(a, s));
+    RTK_TRY(launch_stream_frame(a, p, g, frame_args(a, p, g, accel_camera(a), d_rgb), scene_forks(a, p->diffuse_rays), true, nullptr, M, s));
+    // tail: lane 0's overflow word, which now stands for all lanes, on its way to the host.  No megakernel behind it: it has no statistic.
+    RTK_HIP(hipMemcpyAsync(a->fn_overflow_host.get(), a->stream.ws.ctrl + dev::kCtrlOverflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RTK_TRY(release_stream_ws(a->stream, s));
     RTK_HIP(a->ad_last.record(s));
     record_last(a, s, false, uint64_t(pixels) * uint64_t(g.sample_end - g.sample_begin));
     RTK_HIP(hipStreamSynchronize(s));

@@ -4,8 +4,8 @@
 #include <cstring>
 #include <mutex>
 
-#include "accel.hpp"
 #include "gbuffer.hpp"
+#include "render_internal.hpp"
 
 using namespace rtk;
 

@@ -1,4 +1,4 @@
-// The launch decisions of a frame (api_frame.hip): which engine RTK_TRACE_AUTO times and picks, when the launch order gets the
+// The launch decisions of a frame (api_frame.hip, api_stream.hip, api_order.hip, api_views.hip): which engine RTK_TRACE_AUTO times and picks, when the launch order gets the
 // camera-ray prior, is re-sorted and may shorten the launch, how a views call is cut, when the streaming workspace is re-made.
 // None of them changes a pixel, so no frame test sees them: tests/cpp/frame_plan_check.cpp pins them.  Plain structs and
 // integers, no HIP, no accel, no heap: the launch path asks these, then issues what they say.

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(SLICES > 1 ? 64 * SLICES : 256, SLICES == 16 ? 1 : 
     const auto view_out = [&]() { return VIEWS ? A.out + (size_t)view * A.view_stride : A.out; };
     // one parking area per wave that can own rays: every wave of a light or SLICES == 1 workgroup, one otherwise -- the
     // others then hold the answers of a light burst's jobs (ShadowBurstService)
-    constexpr int kParkSlots = 4;                        // light workgroups exist for SLICES == 4 only (api_frame.hip)
+    constexpr int kParkSlots = 4;                        // light workgroups exist for SLICES == 4 only (api_order.hip)
     __shared__ __attribute__((aligned(16))) float park_lds[kParkSlots][18][64];
     float4 *const burst_res = reinterpret_cast<float4 *>(&park_lds[1][0][0]);
     // one job per wave: twice as many, handed out as waves fall idle, came out slower (each job pays its own ray setup,

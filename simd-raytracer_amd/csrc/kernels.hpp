@@ -89,7 +89,7 @@ struct RenderArgs {
     // move by 1 to 3 instructions.  With the pad (zero_next took its first word) every field below stays where it was.
     unsigned long long keep_offsets_[5];
     const uint32_t *only_if;          // non-null: the kernel does nothing unless this word is non-zero (overflow fallback)
-    // frame-to-frame scheduling feedback (api_frame.hip render_megakernel): every pixel block reports what it cost; the next
+    // frame-to-frame scheduling feedback (api_order.hip render_megakernel): every pixel block reports what it cost; the next
     // frame of the same shape starts its blocks most-expensive-first (results do not depend on the order)
     uint32_t n_units;                 // pixel blocks (8x8) of this rank = buckets_per_rank * blocks_per_bucket_side^2
     uint32_t *cost_out;               // [n_units] or null
@@ -104,12 +104,12 @@ struct RenderArgs {
     // query of the streaming pipeline (k_shadow) is ONE any-hit query against it instead of is_occluded's stepping loop (rtk.h)
     int occl_on;
     TreeView occl;
-    // rtk_render_views as ONE launch (k_render<..., VIEWS>; api_frame.hip render_views_impl / render_megakernel): the launch's units are (view, pixel
+    // rtk_render_views as ONE launch (k_render<..., VIEWS>; api_views.hip render_views_impl / api_order.hip render_megakernel): the launch's units are (view, pixel
     // block) pairs, unit = view * units_per_view + block, and n_units counts them all.  Null / 0 for a frame.
     const float *views;               // [n_views][12] position, matrix (rtk_view), on the device
     uint32_t n_views, units_per_view;
     size_t view_stride;               // floats from one view's output to the next (width * height * 3)
-    // rtk_render_regions as ONE launch (k_render<..., REGIONS>; api_frame.hip): the launch's units are (rectangle, 8x8 block) pairs, the
+    // rtk_render_regions as ONE launch (k_render<..., REGIONS>; api_regions.hip): the launch's units are (rectangle, 8x8 block) pairs, the
     // blocks anchored at the rectangle's own corner; unit = regions[r].first_unit + block.  Null / 0 for a frame.
     const RegionEntry *regions;       // [n_regions] regions_plan.hpp, on the device; every entry has pixels
     uint32_t n_regions;

@@ -1,4 +1,4 @@
-// Host plan of rtk_render_regions (api_frame.hip): what the rectangles of a call are allowed to be, which of them overlap,
+// Host plan of rtk_render_regions (api_regions.hip): what the rectangles of a call are allowed to be, which of them overlap,
 // where each one's 8x8 pixel blocks sit among the units of a launch, where its pixels sit in the output, and how a call of many
 // units is cut into launches of whole rectangles.  Plain integers, no HIP, no accel: tests/cpp/regions_plan_check.cpp runs it.
 #pragma once

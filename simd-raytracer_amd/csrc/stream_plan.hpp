@@ -1,4 +1,4 @@
-// Queue sizing of the streaming pipeline's two clients (api_frame.hip): a frame's samples in batches, a radiance call's rays in
+// Queue sizing of the streaming pipeline's two clients (api_stream.hip, api_radiance.hip): a frame's samples in batches, a radiance call's rays in
 // chunks, and how many of either are in flight.  Plain integers, no HIP, no accel: tests/cpp/stream_plan_check.cpp runs it.
 #pragma once
 

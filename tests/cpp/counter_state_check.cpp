@@ -1,6 +1,6 @@
 // frame_plan.hpp CounterState on the host (tests/test_cpp_counter_state.py): which of an accel's two counter blocks a frame counts
 // into, whether a fill is issued in front of it and whether its kernel is handed the other block to clear.  The sequences are the
-// launch path's (api_frame.hip render_frame_impl, order_launch; api_batch.hip): a steady frame is frame(stream, true), every other
+// launch path's (api_frame.hip render_frame_impl, api_order.hip order_launch; api_batch.hip): a steady frame is frame(stream, true), every other
 // user of the counters is forget() or frame(stream, false), an error is forget() behind the frame, and a frame of a new shape
 // forgets behind itself (CounterState::after_order, given OrderState's step).  Then OrderState's two sets of launch lists across the
 // re-sorts: which set a frame reads, which a sort writes, and whether that sort is in front of the frame or behind it.  Plain g++, no HIP.  One "... ok" line per group; a failure

@@ -37,7 +37,7 @@ using Ev = Event<CountEv>;
 int failures = 0;
 #define CHECK(cond) do { if (!(cond)) { std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
 
-constexpr size_t kCap = size_t(1) << 20;           // api_frame.hip kRegionChunkPixels
+constexpr size_t kCap = size_t(1) << 20;           // api_regions.hip kRegionChunkPixels
 
 void rules() {
     const size_t need[5] = {0, 1, 255, 256, 4096};

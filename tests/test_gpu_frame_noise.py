@@ -146,6 +146,34 @@ def test_batch_shapes_keep_the_bits(rtk, monkeypatch, batch, lanes):
     assert acc.noise_fallbacks() == 0 and _accel(rtk, SCENE2).noise_fallbacks() == 0
 
 
+def test_frames_and_noise_calls_alternate_on_one_accel(rtk, monkeypatch):
+    """Both clients of the streamed-frame launcher on ONE accel, one sample per launch over two lanes: a frame at spp 1 (the
+    workspace is made without a sum buffer), the noise call at spp 3 (three launches, and the workspace grows to hold the sum
+    buffer), a frame at spp 1 again, a frame at spp 3.  Each is the same call on the shared default-knob accel, bit for bit."""
+    shared = _accel(rtk, SCENE2)
+    want_noise = _base(rtk, "hw15", 3, 5, 3)
+    want_frame = {spp: shared.render_frame(_cfg(rtk, spp, 5, 3, **HW15)) for spp in (1, 3)}
+    monkeypatch.setenv("RTK_STREAM_BATCH", "1")                     # (read when an accel is built)
+    monkeypatch.setenv("RTK_STREAM_LANES", "2")
+    acc = rtk.KdTreeSimdAccel(rtk.parse_scene_file(SCENE2))
+    monkeypatch.delenv("RTK_STREAM_BATCH")
+    monkeypatch.delenv("RTK_STREAM_LANES")
+
+    def frame(spp):
+        rgb, cn = acc.render_frame(_cfg(rtk, spp, 5, 3, **HW15))
+        ref, fcn = want_frame[spp]
+        assert np.array_equal(_bits(rgb), _bits(ref)), spp
+        assert (cn["rays"], cn["primary"]) == (fcn["rays"], fcn["primary"]) and cn["primary"] == spp * 5 * 3, spp
+
+    frame(1)
+    got = acc.render_frame_noise(_cfg(rtk, 3, 5, 3, **HW15))
+    assert np.array_equal(_bits(got[0]), _bits(want_noise[0])) and np.array_equal(_bits(got[1]), _bits(want_noise[1]))
+    assert (got[2]["rays"], got[2]["primary"]) == (want_noise[2]["rays"], want_noise[2]["primary"])
+    frame(1)
+    frame(3)
+    assert acc.noise_fallbacks() == 0 and shared.noise_fallbacks() == 0
+
+
 # ---------------------------------------------------------------- 4. overflow
 
 def test_a_queue_overflow_redoes_the_call_with_the_same_results(rtk, monkeypatch):

@@ -365,7 +365,7 @@ def test_sharded_frames_assemble_to_the_unsharded_frame(rtk, ora, scene, w, h, w
 @pytest.mark.parametrize("mode", ["group4", "wave", "lane", "group16"])
 def test_cost_feedback_reorders_blocks_but_not_results(rtk, ora, mode):
     """From the second frame of a shape on, the megakernel starts its pixel blocks most-expensive-first, using the cycle
-    counts the previous frame reported (api_frame.hip render_megakernel).  Frames 1, 2, 3 must all be the oracle's frame, also when
+    counts the previous frame reported (api_order.hip render_megakernel).  Frames 1, 2, 3 must all be the oracle's frame, also when
     another shape is rendered in between, and for a rank of a sharded frame."""
     import torch
 

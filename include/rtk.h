@@ -739,6 +739,74 @@ int rtk_denoise_frame_device(const rtk_denoise_params *p, int32_t n_images,
                              const rtk_denoise_inputs *in /* struct on the HOST, DEVICE planes */, float *d_rgb_out,
                              void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* ---- temporal accumulation: reproject and blend a frame's history ----
+ * The temporal step between rtk_render_frame_noise / rtk_render_gbuffer and rtk_denoise_frame: the new frame `cur` is blended with
+ * the accumulated frame `prev` of the previous camera, fetched where each pixel's world position `P` lay in that camera's image.
+ * Only camera motion is reprojected: the planes hold world positions, so a static scene under a moving camera needs no motion
+ * vectors.  The reference has no such step; the arithmetic is spelt out here and pinned, bit for bit, by tests/temporal_model.py.
+ * The calls take no accel: they depend on no scene state.  One image per call; both frames have the size and the fov of *p.
+ * Planes: rgb, position and normal are [h][w][3]; noise, depth, length and mesh are [h][w], in the layouts rtk_gbuffer and
+ * rtk_render_frame_noise write.  out->rgb, out->noise and out->length of one call are prev->rgb, prev->noise and prev->length of
+ * the next; the caller keeps the guides (position, normal, depth, mesh) and the view of the last frame.  prev == NULL starts a history.
+ * Optional planes come as families: cur->noise, out->noise and (with a prev) prev->noise are all set or all NULL; cur->mesh and
+ * (with a prev) prev->mesh are both set or both NULL.
+ * Aliasing: out->rgb may be cur->rgb and out->noise may be cur->noise (they are read only at the pixel that is written).  Any
+ * overlap of an output with a plane of prev is the caller's fault, because neighbours are read there: callers ping-pong two sets.
+ * All arithmetic is float, in the order written, without contraction.  max(x, f) = x > f ? x : f.  A pixel is a HIT iff
+ * `depth >= 0.0f` evaluates true.  Host-side scalars, computed as for a frame's camera rays: aspect = (float)w / (float)h;
+ * th = tanf((float)(fov_degrees * (pi / 180)) / 2.0f); wf = (float)w, hf = (float)h, nmax = (float)max_history.
+ * Per pixel p with colour c, var_c = noise_p * noise_p (1.0f without noise planes), P, n and depth_p:
+ *   1. No history -- prev == NULL, p is no hit, or step 2 or 3 finds nothing: out.rgb = c and out.noise = noise_p (the bits pass
+ *      through), out.length = 1.0f.
+ *   2. Project P into the previous view (C = prev->view->position, M = its matrix, row-major): D = P - C;
+ *      cx = (M0 * D.x + M1 * D.y) + M2 * D.z, cy likewise with M3..M5, cz with M6..M8.  (The inverse of the camera rays'
+ *      transpose(M) * dir for an orthonormal M; for any other M an approximation that the tests of step 3 still guard.)
+ *      Require `cz < 0.0f` to evaluate true.  iz = -cz; qx = cx / iz; qy = cy / iz; ux = (qx / th) / aspect; uy = qy / th;
+ *      fx = ((ux + 1.0f) * 0.5f) * wf - 0.5f; fy = ((1.0f - uy) * 0.5f) * hf - 0.5f.  Require
+ *      `fx > -1.0f && fx < wf && fy > -1.0f && fy < hf` to evaluate true (a NaN or an infinity fails).  Only then:
+ *      x0f = floorf(fx), y0f = floorf(fy), x0 = (int)x0f, y0 = (int)y0f, tx = fx - x0f, ty = fy - y0f.
+ *   3. Four taps q = (x0 + i, y0 + j), j = 0, 1 the outer and i = 0, 1 the inner loop, w = (j ? ty : 1.0f - ty) * (i ? tx : 1.0f - tx).
+ *      A tap is skipped when it lies outside the image; when `prev.depth_q >= 0.0f` is not true; when `prev.length_q >= 1.0f` is not
+ *      true (zero-filled or NaN history); when mesh planes are given and prev.mesh_q != cur.mesh_p; when
+ *      t = (n.x * nq.x + n.y * nq.y) + n.z * nq.z fails `t >= normal_min_dot`; when pd = (n.x * E.x + n.y * E.y) + n.z * E.z with
+ *      E = Pq - P fails `fabsf(pd) <= plane_tolerance * depth_p`.  An accepted tap adds, with vq = noise_q * noise_q (or 1.0f):
+ *      sum_c += w * c_q per channel; sum_v += (w * w) * vq; sum_l += w * length_q; sum_w += w.  History exists iff sum_w > 0.0f.
+ *   4. Blend: hc = sum_c / sum_w; hv = sum_v / (sum_w * sum_w); N = sum_l / sum_w + 1.0f, then N = N < nmax ? N : nmax;
+ *      a = max(1.0f / N, alpha_min); om = 1.0f - a; out.rgb = (om * hc) + (a * c) per channel;
+ *      var = ((om * om) * hv) + ((a * a) * var_c); out.noise = (float)sqrt((double)var); out.length = N.
+ * Non-finite colours in the history are the caller's business and propagate.  The positions should be those of the pixel centres:
+ * a g-buffer of spp = 1 (with spp > 1 the ray of sample 0 is jittered inside its pixel, and a camera standing still would blend
+ * every pixel with its neighbours).
+ * What runs (csrc/temporal.hip): one launch of k_temporal_accumulate, one 256-thread workgroup per 16x16 pixel tile, the workgroups
+ * striding over the tiles.  No workspace, no LDS, no atomics.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL p, cur or out; the parameters in the struct's order (width, height outside
+ * [1, 16384]; a fov_degrees that is not finite or not inside (0, 180); alpha_min not finite or outside (0, 1]; plane_tolerance not
+ * finite or not positive; normal_min_dot not finite or outside [-1, 1]; max_history outside [1, 1048576]); a NULL cur->rgb,
+ * position, normal or depth, or a NULL out->rgb or out->length; with a prev, a NULL rgb, length, position, normal, depth or view
+ * of it; a broken noise family, then a broken mesh family; (device variant) a plane that is not 4-byte aligned.  Then
+ * RTK_ERR_NO_DEVICE.
+ * The device variant is stream-ordered on the current device, allocates nothing, never blocks the host and is one launch; the
+ * structs, prev->view among them, are read on the host before it returns.  Stream capture is neither claimed nor tested.  The host
+ * variant stages the planes in device buffers of its own, which it frees, and is synchronous. */
+typedef struct {
+    int32_t width, height;     /* 1..16384 each */
+    double  fov_degrees;       /* of BOTH frames, as rtk_render_params.fov_degrees */
+    float   alpha_min;         /* finite, 0 < alpha_min <= 1: lower bound of the new frame's weight */
+    float   plane_tolerance;   /* finite, > 0: |n_p . (P_q - P_p)| <= plane_tolerance * depth_p */
+    float   normal_min_dot;    /* finite, in [-1, 1]: n_p . n_q >= normal_min_dot */
+    int32_t max_history;       /* 1..1048576: cap of the history length */
+} rtk_temporal_params;         /* 32 bytes */
+typedef struct { const float *rgb, *noise, *position, *normal, *depth; const uint32_t *mesh; } rtk_temporal_frame;   /* 48 bytes: the new frame */
+typedef struct { const float *rgb, *noise, *length, *position, *normal, *depth; const uint32_t *mesh;
+                 const rtk_view *view; /* HOST in both variants: the camera the history was rendered from */ } rtk_temporal_history;   /* 64 bytes */
+typedef struct { float *rgb, *noise, *length; } rtk_temporal_outputs;                                                /* 24 bytes */
+
+int rtk_temporal_accumulate(const rtk_temporal_params *p, const rtk_temporal_frame *cur /* host planes */,
+                            const rtk_temporal_history *prev /* NULL: start a history */, const rtk_temporal_outputs *out);
+int rtk_temporal_accumulate_device(const rtk_temporal_params *p, const rtk_temporal_frame *cur, const rtk_temporal_history *prev,
+                                   const rtk_temporal_outputs *out /* structs on the HOST, DEVICE planes, 4-byte aligned */,
+                                   void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "rtk_render_adaptive", "rtk_render_adaptive_device",
     "rtk_render_frame_noise", "rtk_render_frame_noise_device", "rtk_debug_noise_fallbacks",
     "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
+    "rtk_temporal_accumulate", "rtk_temporal_accumulate_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
@@ -173,6 +174,27 @@ class DenoiseInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "albedo", "normal", "position", "depth")]
 
 
+class TemporalParams(C.Structure):
+    """rtk.h rtk_temporal_params; 32 bytes."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_degrees", C.c_double), ("alpha_min", C.c_float),
+                ("plane_tolerance", C.c_float), ("normal_min_dot", C.c_float), ("max_history", C.c_int32)]
+
+
+class TemporalFrame(C.Structure):
+    """rtk.h rtk_temporal_frame: the new frame, one pointer per plane; noise and mesh may be NULL; 48 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "position", "normal", "depth", "mesh")]
+
+
+class TemporalHistory(C.Structure):
+    """rtk.h rtk_temporal_history: the accumulated frame, the guides and the view (HOST, an rtk_view) of the previous camera; 64 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "length", "position", "normal", "depth", "mesh", "view")]
+
+
+class TemporalOutputs(C.Structure):
+    """rtk.h rtk_temporal_outputs; 24 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "length")]
+
+
 # the planes of a g-buffer in the struct's order: name -> (trailing shape, dtype); miss values in rtk.h
 GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
@@ -248,6 +270,11 @@ if hasattr(_L, "rtk_render_frame_noise"):             # (as above: an older buil
 _L.rtk_denoise_workspace_bytes.argtypes =[C.POINTER(DenoiseParams), C.c_int32, C.POINTER(C.c_size_t)]
 _L.rtk_denoise_frame.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp]
 _L.rtk_denoise_frame_device.argtypes = [C.POINTER(DenoiseParams), C.c_int32, C.POINTER(DenoiseInputs), _vp, _vp, C.c_size_t, _vp]
+if hasattr(_L, "rtk_temporal_accumulate"):            # (as above: an older build under RTK_LIB_OVERRIDE has no such call)
+    _L.rtk_temporal_accumulate.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory),
+                                           C.POINTER(TemporalOutputs)]
+    _L.rtk_temporal_accumulate_device.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory),
+                                                  C.POINTER(TemporalOutputs), _vp]
 _L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
@@ -457,6 +484,20 @@ class DenoiseConfig:
     def to_c(self, width: int, height: int) -> DenoiseParams:
         return DenoiseParams(width, height, self.iterations, self.normal_power_log2, np.float32(self.sigma_luminance),
                              np.float32(self.sigma_plane), np.float32(self.albedo_floor), 0)
+
+
+@dataclass
+class TemporalConfig:
+    """rtk.h rtk_temporal_params without the image size: how temporal_accumulate() accepts and weighs a frame's history."""
+    fov_degrees: float = 90.0      # of both frames, as RenderConfig.fov_degrees
+    alpha_min: float = 0.05        # in (0, 1]: lower bound of the new frame's weight
+    plane_tolerance: float = 0.01  # a tap must lie within this x depth of the pixel's tangent plane
+    normal_min_dot: float = 0.9    # in [-1, 1]: the least n_p . n_q of an accepted tap
+    max_history: int = 32          # 1..1048576: cap of the history length
+
+    def to_c(self, width: int, height: int) -> TemporalParams:
+        return TemporalParams(width, height, float(self.fov_degrees), np.float32(self.alpha_min), np.float32(self.plane_tolerance),
+                              np.float32(self.normal_min_dot), self.max_history)
 
 
 @dataclass(frozen=True)
@@ -1124,6 +1165,82 @@ def denoise_device(width: int, height: int, d_rgb_ptr: int, d_normal_ptr: int, d
     p = (cfg or DenoiseConfig()).to_c(width, height)
     _check(_L.rtk_denoise_frame_device(C.byref(p), n_images, C.byref(inputs), d_out_ptr or None, d_workspace_ptr or None,
                                        workspace_bytes, stream or None))
+
+
+# ---- temporal accumulation: a frame blended with the reprojected history of the previous camera (rtk.h rtk_temporal_params)
+def _view_record(view) -> np.ndarray:
+    """(position[3], matrix[9] or [3, 3]) -> the 12 floats of an rtk_view"""
+    position, matrix = view
+    v = np.concatenate([np.asarray(position, np.float32).reshape(3), np.asarray(matrix, np.float32).reshape(9)])
+    return np.ascontiguousarray(v, np.float32)
+
+
+def temporal_accumulate(cur: dict, prev: dict | None, cfg: TemporalConfig | None = None) -> dict:
+    """The frame `cur` blended with the history `prev`, fetched where cur's world positions lay in prev's camera.  cur: rgb,
+    position, normal [h, w, 3] and depth [h, w] float32 (the planes render_frame_noise and render_gbuffer write), optionally noise
+    [h, w] float32 and mesh [h, w] uint32.  prev: None to start a history, else rgb, noise and length of the previous call's
+    result, position, normal, depth (and mesh) of the previous frame's g-buffer and view = (position[3], matrix[9]), its camera;
+    it has noise / mesh exactly when cur has.  -> dict rgb [h, w, 3], noise [h, w] or None, length [h, w].  The arithmetic is
+    spelt out in rtk.h; a pixel without history keeps its bits and gets length 1."""
+    rgb = np.ascontiguousarray(cur["rgb"], np.float32)
+    if rgb.ndim != 3 or rgb.shape[-1] != 3 or rgb.size == 0:
+        raise ValueError("rgb must be [h, w, 3] and not empty")
+    h, w = rgb.shape[:2]
+
+    def plane(d, name, trailing=(), dtype=np.float32, required=True):
+        a = d.get(name)
+        if a is None:
+            if required:
+                raise ValueError(f"{name} is required")
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != (h, w) + trailing:
+            raise ValueError(f"{name} must have shape {(h, w) + trailing}, not {a.shape}")
+        return a
+
+    def planes(d, history):
+        o = dict(rgb=plane(d, "rgb", (3,)), noise=plane(d, "noise", required=False), position=plane(d, "position", (3,)),
+                 normal=plane(d, "normal", (3,)), depth=plane(d, "depth"), mesh=plane(d, "mesh", dtype=np.uint32, required=False))
+        if history:
+            o["length"] = plane(d, "length")
+        return o
+
+    ptr = lambda a: None if a is None else a.ctypes.data
+    c = planes(cur, False)
+    frame = TemporalFrame(*(ptr(c[n]) for n, _ in TemporalFrame._fields_))
+    hist = keep = None
+    if prev is not None:
+        q = planes(prev, True)
+        if "view" not in prev or prev["view"] is None:
+            raise ValueError("prev needs view = (position, matrix)")
+        keep = _view_record(prev["view"])
+        q["view"] = keep
+        hist = TemporalHistory(*(ptr(q[n]) for n, _ in TemporalHistory._fields_))
+    out = dict(rgb=np.zeros((h, w, 3), np.float32), noise=None if c["noise"] is None else np.zeros((h, w), np.float32),
+               length=np.zeros((h, w), np.float32))
+    outs = TemporalOutputs(ptr(out["rgb"]), ptr(out["noise"]), ptr(out["length"]))
+    p = (cfg or TemporalConfig()).to_c(w, h)
+    _check(_L.rtk_temporal_accumulate(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs)))
+    return out
+
+
+def temporal_accumulate_device(width: int, height: int, cur: dict, prev: dict | None, out: dict, cfg: TemporalConfig | None = None,
+                               stream: int = 0) -> None:
+    """The same on raw device pointers (ints; 0 or a missing key = no such plane): cur with rgb, noise, position, normal, depth,
+    mesh; prev (or None) with rgb, noise, length, position, normal, depth, mesh and view = (position[3], matrix[9]) as HOST
+    values; out with rgb, noise, length.  out's rgb / noise may be cur's.  Stream-ordered on the current device, one launch,
+    allocates nothing, never blocks the host (rtk.h)."""
+    frame = TemporalFrame(*((cur.get(n) or None) for n, _ in TemporalFrame._fields_))
+    hist = keep = None
+    if prev is not None:
+        keep = _view_record(prev["view"]) if prev.get("view") is not None else None
+        vals = {n: (prev.get(n) or None) for n, _ in TemporalHistory._fields_ if n != "view"}
+        vals["view"] = None if keep is None else keep.ctypes.data
+        hist = TemporalHistory(*(vals[n] for n, _ in TemporalHistory._fields_))
+    outs = TemporalOutputs(*((out.get(n) or None) for n, _ in TemporalOutputs._fields_))
+    p = (cfg or TemporalConfig()).to_c(width, height)
+    _check(_L.rtk_temporal_accumulate_device(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs),
+                                             stream or None))
 
 
 def format_ppm_rgb8(rgb8: np.ndarray) -> bytes:

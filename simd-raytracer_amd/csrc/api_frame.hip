@@ -4,6 +4,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "camera_plan.hpp"
 #include "render_internal.hpp"
 
 namespace rtk {
@@ -121,14 +122,11 @@ void camera_args(const rtk_view &cam, const rtk_render_params *p, const FrameGeo
     std::memcpy(A.cam_pos, cam.position, sizeof(A.cam_pos));
     std::memcpy(A.cam_mat, cam.matrix, sizeof(A.cam_mat));
     A.width = g.width; A.height = g.height;
-    A.aspect = static_cast<float>(g.width) / static_cast<float>(g.height);                    // render.hpp:26
-    // render.hpp:55-57: `const F fov_radians = degrees_to_radians(fov_degrees)` is evaluated in double (fov_degrees is a
-    // double constant, utils/convert.hpp:4-6) and ROUNDED TO FLOAT by the declaration; `std::tan(fov_radians / F(2))` is
-    // then the float overload (tanf), and `screen_x *=` a float multiply (common.hip.hpp camera_ray).
-    const float fov_radians = static_cast<float>(p->fov_degrees * (3.14159265358979323846 / 180.0));
-    A.tan_half_fov = std::tan(fov_radians / 2.0f);
+    const CameraScalars c = camera_scalars(g.width, g.height, p->fov_degrees);               // (camera_plan.hpp: the one copy)
+    A.aspect = c.aspect;
+    A.tan_half_fov = c.tan_half_fov;
     A.spp = p->spp; A.seed = p->seed;
-    A.width_f = static_cast<float>(g.width); A.height_f = static_cast<float>(g.height); A.spp_f = static_cast<float>(p->spp);
+    A.width_f = c.width_f; A.height_f = c.height_f; A.spp_f = static_cast<float>(p->spp);
 }
 
 // what every engine's launch arguments hold for a frame of shape `g` seen from `cam` into `d_out`

@@ -553,6 +553,33 @@ class RadianceConfig:
                               self.trace_mode)
 
 
+def _views_array(views) -> np.ndarray:
+    """-> contiguous float32 [K, 12]: position and matrix of K cameras (rtk.h rtk_view)"""
+    views = np.asarray(views)
+    if views.dtype != np.float32 or views.ndim != 2 or views.shape[1] != 12:
+        raise ValueError("views must be float32 of shape (K, 12)")
+    return np.ascontiguousarray(views)
+
+
+def _first_pass_buffer(cfg: RenderConfig, shape) -> np.ndarray:
+    """the zeros a call renders into when it was given no buffer, which only the first pass of a progressive render can be"""
+    if cfg.sample_begin > 0:
+        raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
+    return np.zeros(shape, np.float32)
+
+
+def _plane(a, shape, name: str, dtype=np.float32, required: bool = False):
+    """a caller's plane as a contiguous array of `shape`; None for one that was not given and is not required"""
+    if a is None:
+        if required:
+            raise ValueError(f"{name} is required")
+        return None
+    a = np.ascontiguousarray(a, dtype)
+    if a.shape != shape:
+        raise ValueError(f"{name} must have shape {shape}, not {a.shape}")
+    return a
+
+
 class KdTreeSimdAccel:
     """kd_tree_simd_accel<float, eps, max_depth, max_leaf_size> (render/accel/kd_tree_simd.hpp:63-98).
 
@@ -692,6 +719,10 @@ class KdTreeSimdAccel:
         _check(_L.rtk_accel_update_geometry_device(self._h, d_vertices_ptr or None, d_indices_ptr or None, mesh_ntris.ctypes.data, stream))
 
     # ---- frames
+    def _frame_size(self, cfg: RenderConfig):
+        """(width, height) of a frame of cfg: 0 stands for the scene's own"""
+        return cfg.width or self.scene.info.width, cfg.height or self.scene.info.height
+
     def output_floats(self, cfg: RenderConfig) -> int:
         n = C.c_size_t(0)
         p = cfg.to_c()
@@ -701,15 +732,12 @@ class KdTreeSimdAccel:
     def render_frame(self, cfg: RenderConfig, rgb: np.ndarray | None = None):
         """Whole frame into host memory: ([h,w,3] float32, counters dict).  `rgb`: the buffer to render into -- for a later
         pass of a progressive frame (cfg.sample_begin > 0) it holds the running sums of the passes before."""
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         p = cfg.to_c()
         n = self.output_floats(cfg)
         assert n == w * h * 3
         if rgb is None:
-            if cfg.sample_begin > 0:
-                raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
-            rgb = np.zeros((h, w, 3), np.float32)
+            rgb = _first_pass_buffer(cfg, (h, w, 3))
         assert rgb.dtype == np.float32 and rgb.shape == (h, w, 3) and rgb.flags.c_contiguous
         c = Counters()
         _check(_L.rtk_render_frame(self._h, C.byref(p), rgb.ctypes.data, C.byref(c)))
@@ -726,8 +754,7 @@ class KdTreeSimdAccel:
 
     def camera_rays(self, cfg: RenderConfig, sample: int = 0) -> np.ndarray:
         """[h, w, 6] float32: origin + direction of every pixel's camera ray for sample `sample` (render.hpp:35-62)."""
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         rays = np.zeros((h, w, 6), np.float32)
         p = cfg.to_c()
         _check(_L.rtk_camera_rays(self._h, C.byref(p), sample, rays.ctypes.data))
@@ -755,17 +782,11 @@ class KdTreeSimdAccel:
     def render_views(self, cfg: RenderConfig, views: np.ndarray, rgb: np.ndarray | None = None):
         """views: [K, 12] float32 (position, matrix) in host memory -> ([K, h, w, 3] float32, counters summed over the views).
         View k is what set_camera(views[k]) + render_frame(cfg) gives; the accel's own camera stays.  `rgb`: as for render_frame."""
-        views = np.asarray(views)
-        if views.dtype != np.float32 or views.ndim != 2 or views.shape[1] != 12:
-            raise ValueError("views must be float32 of shape (K, 12)")
-        views = np.ascontiguousarray(views)
+        views = _views_array(views)
         k = views.shape[0]
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         if rgb is None:
-            if cfg.sample_begin > 0:
-                raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
-            rgb = np.zeros((k, h, w, 3), np.float32)
+            rgb = _first_pass_buffer(cfg, (k, h, w, 3))
         assert rgb.dtype == np.float32 and rgb.shape == (k, h, w, 3) and rgb.flags.c_contiguous
         p = cfg.to_c()
         c = Counters()
@@ -786,17 +807,14 @@ class KdTreeSimdAccel:
         (1-D, 3 * the sum of the areas), e.g. `views[0].base` of an earlier pass of a progressive render."""
         arr = _rects_array(rects)
         k = arr.shape[0]
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         if layout == REGIONS_PACKED:
             areas = (arr[:, 2].astype(np.int64) - arr[:, 0]) * (arr[:, 3].astype(np.int64) - arr[:, 1])
             shape = (int(np.maximum(areas, 0).sum()) * 3,)
         else:
             shape = (h, w, 3)
         if rgb is None:
-            if cfg.sample_begin > 0:
-                raise ValueError("a pass with sample_begin > 0 needs the buffer the previous passes rendered into")
-            rgb = np.zeros(shape, np.float32)
+            rgb = _first_pass_buffer(cfg, shape)
         if rgb.dtype != np.float32 or rgb.shape != shape or not rgb.flags.c_contiguous:
             raise ValueError(f"rgb must be contiguous float32 of shape {shape}")
         p = cfg.to_c()
@@ -831,16 +849,12 @@ class KdTreeSimdAccel:
         if views is None:
             k, vptr = 1, None
         else:
-            views = np.asarray(views)
-            if views.dtype != np.float32 or views.ndim != 2 or views.shape[1] != 12:
-                raise ValueError("views must be float32 of shape (K, 12)")
-            views = np.ascontiguousarray(views)
+            views = _views_array(views)
             k = views.shape[0]
             if k == 0:
                 views = np.zeros((1, 12), np.float32)               # (no views: a valid pointer nothing is read through)
             vptr = views.ctypes.data
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         out = {n: np.zeros((k, h, w) + GBUFFER_PLANES[n][0], GBUFFER_PLANES[n][1]) for n in GBUFFER_PLANES if n in planes}
         spare = np.zeros(1, np.uint32)                              # (likewise for planes without pixels)
         gb = GBuffer(**{n: a.ctypes.data if a.size else spare.ctypes.data for n, a in out.items()})
@@ -864,8 +878,7 @@ class KdTreeSimdAccel:
         """-> (rgb [h, w, 3] float32, samples [h, w] uint32, noise [h, w] float32, counters).  Every pixel is, bit for bit, the pixel
         of render_frame(cfg with spp = samples[pixel]); samples is constant over an 8x8 block; noise is the standard error of the
         pixel's mean luminance at its final count (the statistic is spelt out in rtk.h)."""
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         rgb = np.zeros((h, w, 3), np.float32)
         samples = np.zeros((h, w), np.uint32)
         noise = np.zeros((h, w), np.float32)
@@ -887,8 +900,7 @@ class KdTreeSimdAccel:
         """-> (rgb [h, w, 3] float32, noise [h, w] float32, counters).  rgb and counters are render_frame(cfg)'s, noise is, bit for bit,
         the noise plane of render_adaptive(cfg, min_samples = cfg.spp): the standard error of the pixel's mean luminance after all
         cfg.spp samples.  A streamed frame (TRACE_AUTO means TRACE_STREAM here), cfg.spp >= 2, not progressive, not sharded."""
-        w = cfg.width or self.scene.info.width
-        h = cfg.height or self.scene.info.height
+        w, h = self._frame_size(cfg)
         rgb = np.zeros((h, w, 3), np.float32)
         noise = np.zeros((h, w), np.float32)
         p = cfg.to_c()
@@ -1131,17 +1143,9 @@ def denoise(rgb: np.ndarray, normal: np.ndarray, position: np.ndarray, depth: np
     k = 1 if rgb.ndim == 3 else lead[0]
     h, w = lead[-2], lead[-1]
 
-    def plane(a, shape, name):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, np.float32)
-        if a.shape != shape:
-            raise ValueError(f"{name} must have shape {shape}, not {a.shape}")
-        return a
-
-    normal, position = plane(normal, rgb.shape, "normal"), plane(position, rgb.shape, "position")
-    albedo = plane(albedo, rgb.shape, "albedo")
-    depth, noise = plane(depth, lead, "depth"), plane(noise, lead, "noise")
+    normal, position = _plane(normal, rgb.shape, "normal"), _plane(position, rgb.shape, "position")
+    albedo = _plane(albedo, rgb.shape, "albedo")
+    depth, noise = _plane(depth, lead, "depth"), _plane(noise, lead, "noise")
     if normal is None or position is None or depth is None:
         raise ValueError("normal, position and depth are required")
     out = np.zeros_like(rgb)
@@ -1188,15 +1192,7 @@ def temporal_accumulate(cur: dict, prev: dict | None, cfg: TemporalConfig | None
     h, w = rgb.shape[:2]
 
     def plane(d, name, trailing=(), dtype=np.float32, required=True):
-        a = d.get(name)
-        if a is None:
-            if required:
-                raise ValueError(f"{name} is required")
-            return None
-        a = np.ascontiguousarray(a, dtype)
-        if a.shape != (h, w) + trailing:
-            raise ValueError(f"{name} must have shape {(h, w) + trailing}, not {a.shape}")
-        return a
+        return _plane(d.get(name), (h, w) + trailing, name, dtype, required)
 
     def planes(d, history):
         o = dict(rgb=plane(d, "rgb", (3,)), noise=plane(d, "noise", required=False), position=plane(d, "position", (3,)),

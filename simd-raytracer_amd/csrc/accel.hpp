@@ -17,6 +17,7 @@
 #include "stream.hpp"
 #include "build.hpp"
 #include "dev_mem.hpp"
+#include "stage_plan.hpp"
 #include "frame_plan.hpp"
 #include "order_judge.hpp"
 #include "update_plan.hpp"
@@ -132,6 +133,31 @@ template <typename T> using DevBuf = Buf<T, DeviceMem>;
 template <typename T> using PinBuf = Buf<T, PinnedMem>;
 using DevEvent = Event<EventSrc<hipEventDisableTiming>>;
 using TimedEvent = Event<EventSrc<hipEventDefault>>;
+
+// What a host variant of the C-ABI stages on the device: the caller's arrays on their way up and the answers on their way down, laid
+// out by stage_plan.hpp in ONE buffer.  It grows by grow_bytes and never shrinks; growing frees the old allocation, which waits for
+// the device.  Either the call's own (freed when the call returns) or rtk_accel::stage.  Statuses are RTK_MEM's and RTK_HIP's.
+class HostStage {
+    DevBuf<uint32_t> buf_;
+    StageLayout lay_;
+    uint32_t *words(int i) const { return lay_.present(i) ? buf_.get() + lay_.off[i] : nullptr; }
+public:
+    // room for the planes of L; a layout whose bytes are no size_t fails like an allocation that cannot succeed
+    int reserve(const StageLayout &L) {
+        if (!L.fits()) return int(hipErrorOutOfMemory);
+        lay_ = L;
+        return buf_.reserve(size_t(L.total), grow_bytes());
+    }
+    // plane i on the device, null for an absent one
+    template <typename T> T *at(int i) const { return reinterpret_cast<T *>(words(i)); }
+    // blocking copies of a whole plane; nothing moves for an absent one
+    hipError_t upload(int i, const void *src) const {
+        return lay_.present(i) ? hipMemcpy(words(i), src, size_t(lay_.bytes[i]), hipMemcpyHostToDevice) : hipSuccess;
+    }
+    hipError_t download(int i, void *dst) const {
+        return lay_.present(i) ? hipMemcpy(dst, words(i), size_t(lay_.bytes[i]), hipMemcpyDeviceToHost) : hipSuccess;
+    }
+};
 
 // A workspace of the accel that calls on different streams share: its last user recorded `done` behind its last kernel, the next
 // user, on any stream, waits for that on the device before it touches the workspace.
@@ -289,9 +315,12 @@ struct rtk_accel {
     // alternates frames and views calls keeps the order of both.
     rtk_cost_feedback fb;
     std::vector<rtk_cost_feedback> fb_views;
-    // ---- views_*: rtk_render_views (api_views.hip).  The host variant's staging (view table, output) grows and never shrinks.
-    rtk::DevBuf<rtk_view> views_tab;
-    rtk::DevBuf<float> views_out;
+    // ---- stage: what the host variants of the calls that take an accel stage on the device (HostStage above), shared by all of them.
+    // Invariant: a host variant holds `mu` from its reserve() to its last blocking copy, and no _device variant ever touches the
+    // stage; so the planes of one call are never in use when the next call lays out its own, and the accel keeps the largest
+    // stage any call needed, not the sum.
+    rtk::HostStage stage;
+    // ---- views: rtk_render_views (api_views.hip)
     rtk::DevBuf<unsigned long long> d_views_counters;   // [kCounterWords] the call's totals while its frames / launches run
     // ---- rg_* / fb_regions: rtk_render_regions (api_regions.hip).  One set of cost tables per launch of a call, as for views; they are
     // reused only by a call whose rectangle list, layout and frame width equal the previous call's (rg_rects, rg_layout, rg_width), and
@@ -308,13 +337,9 @@ struct rtk_accel {
     rtk::DevBuf<rtk_ray> rg_rays;              // streaming path: rays, frame pixel indices and colours of one chunk of pixels
     rtk::DevBuf<uint32_t> rg_ids;
     rtk::DevBuf<float> rg_rgb;
-    rtk::DevBuf<float> rg_out;                 // staging of the host variant
-    // ---- gb_*: staging of the host variant of rtk_render_gbuffer (api_gbuffer.hip): grows with head room, never shrinks
-    rtk::DevBuf<rtk_view> gb_views;
-    rtk::DevBuf<uint32_t> gb_out;              // the wanted planes one behind the other, dwords
     // ---- ad_*: rtk_render_adaptive (api_adaptive.hip, adaptive.hip).  24 B per pixel of the largest frame so far: the luminance sums,
     // the two lists of active pixels a round reads and writes; beside them the two block lists, the count word with its pinned host
-    // copy, the rays and colours of one chunk, and the staging of the host variant.  All grow with head room and never shrink.
+    // copy, and the rays and colours of one chunk.  All grow with head room and never shrink.
     rtk::DevBuf<double> ad_s1, ad_s2;
     rtk::DevBuf<uint32_t> ad_list;             // [2][pixels]
     rtk::DevBuf<uint32_t> ad_blocks;           // [2][blocks]
@@ -322,12 +347,10 @@ struct rtk_accel {
     rtk::PinBuf<unsigned long long> ad_count_host;
     rtk::DevBuf<rtk_ray> ad_rays;
     rtk::DevBuf<float> ad_rgb;
-    rtk::DevBuf<uint32_t> ad_out;              // host variant: rgb, samples and noise one behind the other, dwords
     rtk::LastUse ad_last;                      // of the workspace by a call's kernels: a call on another stream waits for it
     // ---- fn_*: rtk_render_frame_noise (api_frame_noise.hip, frame_noise.hip).  Its running sums are ad_s1 / ad_s2, behind ad_last;
-    // its own are the pinned word the overflow flag is read back into, the staging of the host variant and the count of redone calls.
+    // its own are the pinned word the overflow flag is read back into and the count of redone calls.
     rtk::PinBuf<uint32_t> fn_overflow_host;
-    rtk::DevBuf<float> fn_out;                 // host variant: rgb and noise one behind the other
     uint64_t noise_fallbacks = 0;              // calls redone through the adaptive path because a queue overflowed (rtk_debug_noise_fallbacks)
     // ---- trial*: RTK_TRACE_AUTO on forking scenes: which engine is faster for the current shape (api_frame.hip choose_engine)
     rtk::TimedEvent trial_ev[4];
@@ -339,17 +362,9 @@ struct rtk_accel {
     rtk::PinBuf<uint32_t> rp_host;   // pinned: the probe's words as the host sees them
     rtk::DevEvent rp_probe_ev;
     rtk::LastUse rp_last;            // of rp_idx by the k_intersect that walks it: the next repack waits for it
-    // ---- oc_*: staging of the host variant of the occlusion batch (rtk_accel_occluded, api_batch.hip): grows, never shrinks
-    rtk::DevBuf<rtk_ray> oc_rays;
-    rtk::DevBuf<float> oc_max_t;
-    rtk::DevBuf<uint8_t> oc_out;
     // ---- rad_*: batched radiance (rtk_accel_radiance, api_radiance.hip)
     // one counter block per lane for a chunk's pipeline, then {rays, chunks redone} of the call (counters.hpp)
     rtk::DevBuf<unsigned long long> d_rad_counters;
-    // staging of the host variant: grows, never shrinks
-    rtk::DevBuf<rtk_ray> rad_rays;
-    rtk::DevBuf<uint32_t> rad_ids;
-    rtk::DevBuf<float> rad_rgb;
     // ---- up_*: rtk_accel_update_vertices (api_update.hip, build.hip): scratch of a build; buffers grow, never shrink
     bool refs_on_device = false;               // tree.leaf_refs (and every per-triangle host array) lives on the device only
     int32_t n_leaf_refs_dev = 0;
@@ -403,6 +418,13 @@ struct rtk_accel {
 namespace rtk {
 
 inline int fail(int code, const std::string &msg) { set_error(msg); return code; }
+
+// a call that takes no accel (and so never goes through ensure_device) is about to use the device
+inline int need_device() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RTK_ERR_NO_DEVICE, "no usable HIP device (this engine has no CPU path)");
+    return RTK_OK;
+}
 
 inline int hip_fail(hipError_t e, const char *what) {
     set_error(std::string(what) + ": " + hipGetErrorString(e));

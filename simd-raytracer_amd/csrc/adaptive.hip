@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "adaptive.hpp"
+#include "frame_noise_math.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"    // (det_sincos: the GI rays' helper, static in the shared header)
 #include "common.hip.hpp"
@@ -27,7 +28,7 @@ __global__ __launch_bounds__(256) void k_adaptive_rays(RenderArgs A, int sample,
 }
 
 // pixel_sum += colour as k_region_accumulate does it (in sample order: all launches of a pixel are on one stream; a colour arrives
-// as +0 + c), and beside it the statistic of rtk.h: y in float without contraction, S1 and S2 in double.
+// as +0 + c), and beside it the statistic of rtk.h (frame_noise_math.hpp): y in float without contraction, S1 and S2 in double.
 __global__ __launch_bounds__(256) void k_adaptive_accumulate(const uint32_t *list, uint32_t n, const float *colours, float *rgb, double *s1,
                                                              double *s2, int start) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,10 +40,8 @@ __global__ __launch_bounds__(256) void k_adaptive_accumulate(const uint32_t *lis
     V3 sum = start ? mk(0.f, 0.f, 0.f) : mk(o[0], o[1], o[2]);
     sum = sum + col;
     o[0] = sum.x; o[1] = sum.y; o[2] = sum.z;
-    const float y = (0.2126f * col.x + 0.7152f * col.y) + 0.0722f * col.z;
     double a = start ? 0.0 : s1[pixel], b = start ? 0.0 : s2[pixel];
-    a += (double)y;
-    b += (double)y * (double)y;
+    fn_add(a, b, fn_lum(col.x, col.y, col.z));
     s1[pixel] = a; s2[pixel] = b;
 }
 
@@ -80,9 +79,7 @@ __global__ __launch_bounds__(256) void k_adaptive_decide(AdaptiveDecide D) {
         if (valid) {
             const double S1 = D.s1[pixel], S2 = D.s2[pixel];
             m = S1 / n;
-            const double x = (S2 - S1 * S1 / n) / (n - 1.0);
-            const double v = (x < 0.0 ? 0.0 : x) / n;                            // max(0, x): a NaN stays one
-            e = __builtin_sqrt(v);
+            e = fn_error(S1, S2, D.n);
         }
         double se = 0.0, sm = 0.0;
         for (int i = 0; i < 64; ++i) { se += lane_double(e, i); sm += lane_double(m, i); }

@@ -123,15 +123,17 @@ int rtk_render_adaptive(rtk_accel *a, const rtk_render_params *p, const rtk_adap
         {
             std::lock_guard<std::mutex> lock(a->mu);
             RTK_TRY(ensure_device(a));
-            // rgb, samples and noise one behind the other in one staging buffer of dwords
-            const size_t n = size_t(g.width) * g.height;
-            RTK_MEM(a->ad_out.reserve(n * 5, grow_bytes()));
-            uint32_t *const base = a->ad_out.get();
-            RTK_TRY(adaptive_device_impl(a, p, ap, g, reinterpret_cast<float *>(base), base + n * 3, reinterpret_cast<float *>(base + n * 4), nullptr));
+            // rgb, samples and noise: all three are written on the device, whichever of them the caller wants back
+            const uint64_t n = uint64_t(g.width) * g.height;
+            HostStage &st = a->stage;
+            StageLayout L;
+            const int o_rgb = L.add(n * 3), o_samples = L.add(n), o_noise = L.add(n);
+            RTK_MEM(st.reserve(L));
+            RTK_TRY(adaptive_device_impl(a, p, ap, g, st.at<float>(o_rgb), st.at<uint32_t>(o_samples), st.at<float>(o_noise), nullptr));
             // (a copy on the null stream is behind the kernels and blocks the host)
-            RTK_HIP(hipMemcpy(rgb, base, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-            if (samples) RTK_HIP(hipMemcpy(samples, base + n * 3, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (noise) RTK_HIP(hipMemcpy(noise, base + n * 4, n * sizeof(float), hipMemcpyDeviceToHost));
+            RTK_HIP(st.download(o_rgb, rgb));
+            if (samples) RTK_HIP(st.download(o_samples, samples));
+            if (noise) RTK_HIP(st.download(o_noise, noise));
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;

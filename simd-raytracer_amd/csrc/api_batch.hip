@@ -128,13 +128,13 @@ int rtk_accel_intersect(rtk_accel *a, const rtk_ray *rays, size_t n, int cull, i
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
         if (n == 0) return RTK_OK;
-        DevBuf<rtk_ray> d_rays;                      // (the call's own: freed when it returns)
-        DevBuf<rtk_hit> d_out;
-        RTK_MEM(d_rays.reserve(n));
-        RTK_HIP_AS(static_cast<hipError_t>(d_out.reserve(n)), "hipMalloc hits");
-        RTK_HIP_AS(hipMemcpy(d_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice), "intersect copy");
-        RTK_TRY(intersect_device_impl(a, d_rays.get(), n, cull, mode, d_out.get(), nullptr, false));
-        RTK_HIP_AS(hipMemcpy(out, d_out.get(), n * sizeof(rtk_hit), hipMemcpyDeviceToHost), "intersect copy");
+        HostStage stage;                             // (the call's own: freed when it returns)
+        StageLayout L;
+        const int i_rays = L.add(uint64_t(n) * (sizeof(rtk_ray) / 4)), o_hits = L.add(uint64_t(n) * (sizeof(rtk_hit) / 4));
+        RTK_MEM(stage.reserve(L));
+        RTK_HIP_AS(stage.upload(i_rays, rays), "intersect copy");
+        RTK_TRY(intersect_device_impl(a, stage.at<rtk_ray>(i_rays), n, cull, mode, stage.at<rtk_hit>(o_hits), nullptr, false));
+        RTK_HIP_AS(stage.download(o_hits, out), "intersect copy");
         return RTK_OK;
     });
 }
@@ -188,17 +188,18 @@ int rtk_accel_occluded(rtk_accel *a, const rtk_ray *rays, const float *max_t, si
         }
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        RTK_MEM(a->oc_rays.reserve(n));
-        RTK_MEM(a->oc_max_t.reserve(n));
-        RTK_MEM(a->oc_out.reserve(n));
-        RTK_HIP(hipMemcpy(a->oc_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-        RTK_HIP(hipMemcpy(a->oc_max_t.get(), max_t, n * sizeof(float), hipMemcpyHostToDevice));
+        HostStage &st = a->stage;
+        StageLayout L;
+        const int i_rays = L.add(uint64_t(n) * (sizeof(rtk_ray) / 4)), i_max_t = L.add(n), o_out = L.add_bytes(n);
+        RTK_MEM(st.reserve(L));
+        RTK_HIP(st.upload(i_rays, rays));
+        RTK_HIP(st.upload(i_max_t, max_t));
         if (n_intersections) {
             a->cnt.forget();
             RTK_HIP(hipMemsetAsync(counters_now(a) + kOccludedCountWord, 0, sizeof(unsigned long long), nullptr));
         }
-        RTK_TRY(occluded_launch(a, a->oc_rays.get(), a->oc_max_t.get(), n, shadow_bias, mode, a->oc_out.get(), nullptr, n_intersections != nullptr));
-        RTK_HIP(hipMemcpy(out, a->oc_out.get(), n, hipMemcpyDeviceToHost));
+        RTK_TRY(occluded_launch(a, st.at<rtk_ray>(i_rays), st.at<float>(i_max_t), n, shadow_bias, mode, st.at<uint8_t>(o_out), nullptr, n_intersections != nullptr));
+        RTK_HIP(st.download(o_out, out));
         if (n_intersections) {
             unsigned long long h = 0;
             RTK_HIP(hipMemcpy(&h, counters_now(a) + kOccludedCountWord, sizeof(h), hipMemcpyDeviceToHost));

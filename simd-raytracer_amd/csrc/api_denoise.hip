@@ -17,12 +17,6 @@ int denoise_check(const rtk_denoise_params *p, int32_t n_images, const void *thi
     return RTK_OK;
 }
 
-int denoise_need_device() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RTK_ERR_NO_DEVICE, "no usable HIP device (this engine has no CPU path)");
-    return RTK_OK;
-}
-
 // RTK_DENOISE_LDS_MAX_STEP, read once per process
 int lds_max_step() {
     static const int v = denoise_lds_max_step(std::getenv("RTK_DENOISE_LDS_MAX_STEP"));
@@ -80,7 +74,7 @@ int rtk_denoise_frame_device(const rtk_denoise_params *p, int32_t n_images, cons
         if (const char *why = denoise_missing_plane(*in, d_rgb_out)) return fail(RTK_ERR_INVALID, why);
         const uint64_t need = denoise_workspace(uint64_t(p->width) * uint64_t(p->height) * uint64_t(n_images), p->iterations).bytes;
         if (const char *why = denoise_device_refusal(*in, d_rgb_out, d_workspace, workspace_bytes, need)) return fail(RTK_ERR_INVALID, why);
-        RTK_TRY(denoise_need_device());
+        RTK_TRY(need_device());
         return denoise_device_impl(*p, n_images, *in, d_rgb_out, d_workspace, static_cast<hipStream_t>(stream));
     });
 }
@@ -90,30 +84,26 @@ int rtk_denoise_frame(const rtk_denoise_params *p, int32_t n_images, const rtk_d
         RTK_TRY(denoise_check(p, n_images, in));
         if (n_images == 0) return RTK_OK;
         if (const char *why = denoise_missing_plane(*in, rgb_out)) return fail(RTK_ERR_INVALID, why);
-        RTK_TRY(denoise_need_device());
-        // the planes one behind the other in one staging buffer of floats (output last), the workspace in a second one; both are
-        // the call's own and are freed when it returns
-        const size_t n = size_t(p->width) * size_t(p->height) * size_t(n_images);
+        RTK_TRY(need_device());
+        // the planes and the output in one staging buffer, the workspace in a second one; both are the call's own and are freed
+        // when it returns
+        const uint64_t n = uint64_t(p->width) * uint64_t(p->height) * uint64_t(n_images);
         const float *const host[6] = {in->rgb, in->noise, in->albedo, in->normal, in->position, in->depth};
-        const size_t each[6] = {3, 1, 3, 3, 3, 1};
-        size_t off[8] = {0};
-        for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + (host[i] ? each[i] * n : 0u);
-        off[7] = off[6] + 3u * n;
+        const uint64_t each[6] = {3, 1, 3, 3, 3, 1};
+        StageLayout L;
+        for (int i = 0; i < 6; ++i) L.add(each[i] * n, host[i] != nullptr);
+        const int o_rgb = L.add(3 * n);
         const DnWorkspace ws = denoise_workspace(n, p->iterations);
-        DevBuf<float> stage;
+        HostStage stage;
         DevBuf<float4> work;
-        RTK_MEM(stage.reserve(off[7]));
+        RTK_MEM(stage.reserve(L));
         RTK_MEM(work.reserve(size_t(ws.bytes / sizeof(float4))));
-        const float *d[6];
-        for (int i = 0; i < 6; ++i) {
-            d[i] = host[i] ? stage.get() + off[i] : nullptr;
-            if (host[i]) RTK_HIP(hipMemcpy(stage.get() + off[i], host[i], each[i] * n * sizeof(float), hipMemcpyHostToDevice));
-        }
-        rtk_denoise_inputs din;
-        din.rgb = d[0]; din.noise = d[1]; din.albedo = d[2]; din.normal = d[3]; din.position = d[4]; din.depth = d[5];
-        RTK_TRY(denoise_device_impl(*p, n_images, din, stage.get() + off[6], work.get(), nullptr));
+        for (int i = 0; i < 6; ++i) RTK_HIP(stage.upload(i, host[i]));
+        const rtk_denoise_inputs din = {stage.at<float>(0), stage.at<float>(1), stage.at<float>(2), stage.at<float>(3), stage.at<float>(4),
+                                        stage.at<float>(5)};
+        RTK_TRY(denoise_device_impl(*p, n_images, din, stage.at<float>(o_rgb), work.get(), nullptr));
         // (a copy on the null stream is behind the kernels and blocks the host)
-        RTK_HIP(hipMemcpy(rgb_out, stage.get() + off[6], 3u * n * sizeof(float), hipMemcpyDeviceToHost));
+        RTK_HIP(stage.download(o_rgb, rgb_out));
         return RTK_OK;
     });
 }

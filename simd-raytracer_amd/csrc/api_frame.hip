@@ -294,12 +294,14 @@ int rtk_render_frame(rtk_accel *a, const rtk_render_params *p, float *rgb, rtk_c
         {
             std::lock_guard<std::mutex> lock(a->mu);
             RTK_TRY(ensure_device(a));
-            DevBuf<float> d_out;                     // (the call's own: freed when the block is left)
-            RTK_MEM(d_out.reserve(nf));
+            HostStage stage;                         // (the call's own: freed when the block is left)
+            StageLayout L;
+            const int o_rgb = L.add(nf);
+            RTK_MEM(stage.reserve(L));
             // a later pass of a progressive frame continues the running per-pixel sums the previous pass left in `rgb`
-            if (p->sample_begin > 0) RTK_HIP_AS(hipMemcpy(d_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice), "upload of the running sums");
-            RTK_TRY(render_device_impl(a, p, d_out.get(), nullptr));
-            RTK_HIP_AS(hipMemcpy(rgb, d_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost), "frame copy");
+            if (p->sample_begin > 0) RTK_HIP_AS(stage.upload(o_rgb, rgb), "upload of the running sums");
+            RTK_TRY(render_device_impl(a, p, stage.at<float>(o_rgb), nullptr));
+            RTK_HIP_AS(stage.download(o_rgb, rgb), "frame copy");
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;
@@ -342,15 +344,16 @@ int rtk_camera_rays(rtk_accel *a, const rtk_render_params *p, int32_t sample, rt
         if (!a || !p || !rays) return fail(RTK_ERR_INVALID, "null accel, params or ray buffer");
         FrameGeom g;
         RTK_TRY(frame_geom(a, p, g));
-        const size_t n = size_t(g.width) * g.height;
-        DevBuf<rtk_ray> d;
+        HostStage stage;                             // (the call's own: freed when it returns)
+        StageLayout L;
+        const int o_rays = L.add(uint64_t(g.width) * g.height * (sizeof(rtk_ray) / 4));
         {
             std::lock_guard<std::mutex> lock(a->mu);
             RTK_TRY(ensure_device(a));
-            RTK_MEM(d.reserve(n));
+            RTK_MEM(stage.reserve(L));
         }
-        RTK_TRY(rtk_camera_rays_device(a, p, sample, d.get(), nullptr));
-        RTK_HIP_AS(hipMemcpy(rays, d.get(), n * sizeof(rtk_ray), hipMemcpyDeviceToHost), "camera ray copy");
+        RTK_TRY(rtk_camera_rays_device(a, p, sample, stage.at<rtk_ray>(o_rays), nullptr));
+        RTK_HIP_AS(stage.download(o_rays, rays), "camera ray copy");
         return RTK_OK;
     });
 }

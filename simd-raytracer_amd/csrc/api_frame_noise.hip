@@ -90,14 +90,15 @@ int rtk_render_frame_noise(rtk_accel *a, const rtk_render_params *p, float *rgb,
         {
             std::lock_guard<std::mutex> lock(a->mu);
             RTK_TRY(ensure_device(a));
-            // rgb and noise one behind the other in one staging buffer
-            const size_t n = size_t(g.width) * g.height;
-            RTK_MEM(a->fn_out.reserve(n * 4, grow_bytes()));
-            float *const base = a->fn_out.get();
-            RTK_TRY(render_frame_noise_impl(a, p, g, base, base + n * 3, nullptr));
+            const uint64_t n = uint64_t(g.width) * g.height;
+            HostStage &st = a->stage;
+            StageLayout L;
+            const int o_rgb = L.add(n * 3), o_noise = L.add(n);
+            RTK_MEM(st.reserve(L));
+            RTK_TRY(render_frame_noise_impl(a, p, g, st.at<float>(o_rgb), st.at<float>(o_noise), nullptr));
             // (a copy on the null stream is behind the kernels and blocks the host)
-            RTK_HIP(hipMemcpy(rgb, base, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-            RTK_HIP(hipMemcpy(noise, base + n * 3, n * sizeof(float), hipMemcpyDeviceToHost));
+            RTK_HIP(st.download(o_rgb, rgb));
+            RTK_HIP(st.download(o_noise, noise));
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;

@@ -80,25 +80,19 @@ int rtk_render_gbuffer(rtk_accel *a, const rtk_render_params *p, int32_t sample,
         if (n_views == 0) return RTK_OK;
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        // the wanted planes one behind the other in one staging buffer of dwords
+        // the wanted planes (plane i of rtk_gbuffer is plane i of the stage), then the view table
         const uint64_t n = uint64_t(n_views);
-        uint64_t off[kGbPlanes + 1] = {0};
-        for (int i = 0; i < kGbPlanes; ++i) off[i + 1] = off[i] + ((mask >> i & 1u) ? gbuffer_plane_elems(i, n, g.width, g.height) : 0u);
-        RTK_MEM(a->gb_out.reserve(size_t(off[kGbPlanes]), grow_bytes()));
-        if (views) {
-            RTK_MEM(a->gb_views.reserve(size_t(n), grow_half<4>()));
-            RTK_HIP(hipMemcpy(a->gb_views.get(), views, size_t(n) * sizeof(rtk_view), hipMemcpyHostToDevice));
-        }
-        uint32_t *const base = a->gb_out.get();
-        const auto at = [&](int i) -> uint32_t * { return (mask >> i & 1u) ? base + off[i] : nullptr; };
-        rtk_gbuffer d;
-        d.depth = reinterpret_cast<float *>(at(0)); d.position = reinterpret_cast<float *>(at(1)); d.normal = reinterpret_cast<float *>(at(2));
-        d.albedo = reinterpret_cast<float *>(at(3)); d.bary = reinterpret_cast<float *>(at(4));
-        d.tri = at(5); d.mesh = at(6); d.material = at(7);
-        RTK_TRY(gbuffer_device_impl(a, p, g, sample, views ? a->gb_views.get() : nullptr, n_views, d, mask, nullptr));
+        HostStage &st = a->stage;
+        StageLayout L;
+        for (int i = 0; i < kGbPlanes; ++i) L.add(gbuffer_plane_elems(i, n, g.width, g.height), (mask >> i & 1u) != 0u);
+        const int tab = L.add(n * (sizeof(rtk_view) / 4), views != nullptr);
+        RTK_MEM(st.reserve(L));
+        RTK_HIP(st.upload(tab, views));
+        const rtk_gbuffer d = {st.at<float>(0), st.at<float>(1), st.at<float>(2), st.at<float>(3), st.at<float>(4),
+                               st.at<uint32_t>(5), st.at<uint32_t>(6), st.at<uint32_t>(7)};
+        RTK_TRY(gbuffer_device_impl(a, p, g, sample, st.at<rtk_view>(tab), n_views, d, mask, nullptr));
         void *const host[kGbPlanes] = {out->depth, out->position, out->normal, out->albedo, out->bary, out->tri, out->mesh, out->material};
-        for (int i = 0; i < kGbPlanes; ++i)                              // (a copy on the null stream is behind the kernel and blocks the host)
-            if (mask >> i & 1u) RTK_HIP(hipMemcpy(host[i], base + off[i], size_t(off[i + 1] - off[i]) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < kGbPlanes; ++i) RTK_HIP(st.download(i, host[i]));   // (a copy on the null stream is behind the kernel and blocks the host)
         return RTK_OK;
     });
 }

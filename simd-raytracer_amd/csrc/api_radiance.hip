@@ -125,14 +125,15 @@ int rtk_accel_radiance(rtk_accel *a, const rtk_ray *rays, const uint32_t *ids, s
         }
         std::lock_guard<std::mutex> lock(a->mu);
         RTK_TRY(ensure_device(a));
-        RTK_MEM(a->rad_rays.reserve(n));
-        RTK_MEM(a->rad_ids.reserve(n));
-        RTK_MEM(a->rad_rgb.reserve(n * 3));
-        RTK_HIP(hipMemcpy(a->rad_rays.get(), rays, n * sizeof(rtk_ray), hipMemcpyHostToDevice));
-        if (ids) RTK_HIP(hipMemcpy(a->rad_ids.get(), ids, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HostStage &st = a->stage;
+        StageLayout L;
+        const int i_rays = L.add(uint64_t(n) * (sizeof(rtk_ray) / 4)), i_ids = L.add(n, ids != nullptr), o_rgb = L.add(uint64_t(n) * 3);
+        RTK_MEM(st.reserve(L));
+        RTK_HIP(st.upload(i_rays, rays));
+        RTK_HIP(st.upload(i_ids, ids));
         uint32_t n_chunks = 0;
-        RTK_TRY(radiance_device_impl(a, a->rad_rays.get(), ids ? a->rad_ids.get() : nullptr, n, p, a->rad_rgb.get(), nullptr, &n_chunks));
-        RTK_HIP(hipMemcpy(rgb, a->rad_rgb.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        RTK_TRY(radiance_device_impl(a, st.at<rtk_ray>(i_rays), st.at<uint32_t>(i_ids), n, p, st.at<float>(o_rgb), nullptr, &n_chunks));
+        RTK_HIP(st.download(o_rgb, rgb));
         unsigned long long h[kRadianceTotalWords] = {};
         RTK_HIP(hipMemcpy(h, a->d_rad_counters.get() + radiance_total_word(dev::kStreamLanes), sizeof(h), hipMemcpyDeviceToHost));
         if (counters) {

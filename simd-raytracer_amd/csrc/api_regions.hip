@@ -142,11 +142,13 @@ int rtk_render_regions(rtk_accel *a, const rtk_render_params *p, const rtk_rect 
             // what the layout needs: the packed buffer, or the whole frame up and down, so that the caller's pixels outside the
             // rectangles come back with the bits they went up with
             const bool packed = layout == RTK_REGIONS_PACKED;
-            const size_t nf = packed ? size_t(pixels) * 3 : size_t(g.width) * g.height * 3;
-            RTK_MEM(a->rg_out.reserve(nf));
-            if (!packed || p->sample_begin > 0) RTK_HIP(hipMemcpy(a->rg_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
-            RTK_TRY(render_regions_impl(a, p, g, rects, n_rects, layout, a->rg_out.get(), nullptr));
-            RTK_HIP(hipMemcpy(rgb, a->rg_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
+            HostStage &st = a->stage;
+            StageLayout L;
+            const int o_rgb = L.add(packed ? pixels * 3 : uint64_t(g.width) * g.height * 3);
+            RTK_MEM(st.reserve(L));
+            if (!packed || p->sample_begin > 0) RTK_HIP(st.upload(o_rgb, rgb));
+            RTK_TRY(render_regions_impl(a, p, g, rects, n_rects, layout, st.at<float>(o_rgb), nullptr));
+            RTK_HIP(st.download(o_rgb, rgb));
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;

@@ -16,12 +16,6 @@ int temporal_check(const rtk_temporal_params *p, const rtk_temporal_frame *cur, 
     return RTK_OK;
 }
 
-int temporal_need_device() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RTK_ERR_NO_DEVICE, "no usable HIP device (this engine has no CPU path)");
-    return RTK_OK;
-}
-
 // The one launch of a call, on `s`: device planes that have passed the checks; prev->view is read here, on the host.
 int temporal_device_impl(const rtk_temporal_params &p, const rtk_temporal_frame &cur, const rtk_temporal_history *prev,
                          const rtk_temporal_outputs &out, hipStream_t s) {
@@ -46,7 +40,7 @@ int rtk_temporal_accumulate_device(const rtk_temporal_params *p, const rtk_tempo
     return abi_guard([&]() -> int {
         RTK_TRY(temporal_check(p, cur, prev, out));
         if (const char *why = temporal_device_refusal(*cur, prev, *out)) return fail(RTK_ERR_INVALID, why);
-        RTK_TRY(temporal_need_device());
+        RTK_TRY(need_device());
         return temporal_device_impl(*p, *cur, prev, *out, static_cast<hipStream_t>(stream));
     });
 }
@@ -55,41 +49,31 @@ int rtk_temporal_accumulate(const rtk_temporal_params *p, const rtk_temporal_fra
                             const rtk_temporal_outputs *out) {
     return abi_guard([&]() -> int {
         RTK_TRY(temporal_check(p, cur, prev, out));
-        RTK_TRY(temporal_need_device());
-        // the planes one behind the other in one staging buffer of 4-byte words (the mesh ids are words too), the three outputs
-        // last; the buffer is the call's own and is freed when it returns
-        const size_t n = size_t(p->width) * size_t(p->height);
+        RTK_TRY(need_device());
+        // every plane of the frame, of the history and of the outputs in one staging buffer (the mesh ids are words too); the buffer is
+        // the call's own and is freed when it returns
+        const uint64_t n = uint64_t(p->width) * uint64_t(p->height);
+        const rtk_temporal_history none = {};
+        const rtk_temporal_history &h = prev ? *prev : none;
         const void *const host[13] = {cur->rgb, cur->noise, cur->position, cur->normal, cur->depth, cur->mesh,
-                                      prev ? prev->rgb : nullptr, prev ? prev->noise : nullptr, prev ? prev->length : nullptr,
-                                      prev ? prev->position : nullptr, prev ? prev->normal : nullptr, prev ? prev->depth : nullptr,
-                                      prev ? prev->mesh : nullptr};
-        const size_t each[13] = {3, 1, 3, 3, 1, 1, 3, 1, 1, 3, 3, 1, 1};
-        size_t off[17] = {0};
-        for (int i = 0; i < 13; ++i) off[i + 1] = off[i] + (host[i] ? each[i] * n : 0u);
-        off[14] = off[13] + 3u * n;                                    // out rgb at off[13]
-        off[15] = off[14] + (out->noise ? n : 0u);                     // out noise at off[14]
-        off[16] = off[15] + n;                                         // out length at off[15]
-        DevBuf<float> stage;
-        RTK_MEM(stage.reserve(off[16]));
-        const float *d[13];
-        for (int i = 0; i < 13; ++i) {
-            d[i] = host[i] ? stage.get() + off[i] : nullptr;
-            if (host[i]) RTK_HIP(hipMemcpy(stage.get() + off[i], host[i], each[i] * n * sizeof(float), hipMemcpyHostToDevice));
-        }
-        rtk_temporal_frame dcur;
-        dcur.rgb = d[0]; dcur.noise = d[1]; dcur.position = d[2]; dcur.normal = d[3]; dcur.depth = d[4];
-        dcur.mesh = reinterpret_cast<const uint32_t *>(d[5]);
-        rtk_temporal_history dprev;
-        dprev.rgb = d[6]; dprev.noise = d[7]; dprev.length = d[8]; dprev.position = d[9]; dprev.normal = d[10]; dprev.depth = d[11];
-        dprev.mesh = reinterpret_cast<const uint32_t *>(d[12]);
-        dprev.view = prev ? prev->view : nullptr;
-        rtk_temporal_outputs dout;
-        dout.rgb = stage.get() + off[13]; dout.noise = out->noise ? stage.get() + off[14] : nullptr; dout.length = stage.get() + off[15];
+                                      h.rgb, h.noise, h.length, h.position, h.normal, h.depth, h.mesh};
+        const uint64_t each[13] = {3, 1, 3, 3, 1, 1, 3, 1, 1, 3, 3, 1, 1};
+        StageLayout L;
+        for (int i = 0; i < 13; ++i) L.add(each[i] * n, host[i] != nullptr);
+        const int o_rgb = L.add(3 * n), o_noise = L.add(n, out->noise != nullptr), o_length = L.add(n);
+        HostStage stage;
+        RTK_MEM(stage.reserve(L));
+        for (int i = 0; i < 13; ++i) RTK_HIP(stage.upload(i, host[i]));
+        const rtk_temporal_frame dcur = {stage.at<float>(0), stage.at<float>(1), stage.at<float>(2), stage.at<float>(3), stage.at<float>(4),
+                                         stage.at<uint32_t>(5)};
+        const rtk_temporal_history dprev = {stage.at<float>(6), stage.at<float>(7), stage.at<float>(8), stage.at<float>(9), stage.at<float>(10),
+                                            stage.at<float>(11), stage.at<uint32_t>(12), h.view};
+        const rtk_temporal_outputs dout = {stage.at<float>(o_rgb), stage.at<float>(o_noise), stage.at<float>(o_length)};
         RTK_TRY(temporal_device_impl(*p, dcur, prev ? &dprev : nullptr, dout, nullptr));
         // (a copy on the null stream is behind the kernel and blocks the host)
-        RTK_HIP(hipMemcpy(out->rgb, dout.rgb, 3u * n * sizeof(float), hipMemcpyDeviceToHost));
-        if (out->noise) RTK_HIP(hipMemcpy(out->noise, dout.noise, n * sizeof(float), hipMemcpyDeviceToHost));
-        RTK_HIP(hipMemcpy(out->length, dout.length, n * sizeof(float), hipMemcpyDeviceToHost));
+        RTK_HIP(stage.download(o_rgb, out->rgb));
+        RTK_HIP(stage.download(o_noise, out->noise));
+        RTK_HIP(stage.download(o_length, out->length));
         return RTK_OK;
     });
 }

@@ -117,14 +117,16 @@ int rtk_render_views(rtk_accel *a, const rtk_render_params *p, const rtk_view *v
         {
             std::lock_guard<std::mutex> lock(a->mu);
             RTK_TRY(ensure_device(a));
-            const size_t n = size_t(n_views), nf = n * g.width * g.height * 3;
-            RTK_MEM(a->views_tab.reserve(n));
-            RTK_MEM(a->views_out.reserve(nf));
-            RTK_HIP(hipMemcpy(a->views_tab.get(), views, n * sizeof(rtk_view), hipMemcpyHostToDevice));
+            const uint64_t n = uint64_t(n_views);
+            HostStage &st = a->stage;
+            StageLayout L;
+            const int tab = L.add(n * (sizeof(rtk_view) / 4)), o_rgb = L.add(n * g.width * g.height * 3);
+            RTK_MEM(st.reserve(L));
+            RTK_HIP(st.upload(tab, views));
             // a later pass of progressive views continues the running per-pixel sums the previous pass left in `rgb`
-            if (p->sample_begin > 0) RTK_HIP(hipMemcpy(a->views_out.get(), rgb, nf * sizeof(float), hipMemcpyHostToDevice));
-            RTK_TRY(render_views_impl(a, p, g, views, a->views_tab.get(), n_views, a->views_out.get(), nullptr));
-            RTK_HIP(hipMemcpy(rgb, a->views_out.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
+            if (p->sample_begin > 0) RTK_HIP(st.upload(o_rgb, rgb));
+            RTK_TRY(render_views_impl(a, p, g, views, st.at<rtk_view>(tab), n_views, st.at<float>(o_rgb), nullptr));
+            RTK_HIP(st.download(o_rgb, rgb));
         }
         if (counters) return rtk_render_last_counters(a, counters);
         return RTK_OK;

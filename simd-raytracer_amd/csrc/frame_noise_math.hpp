@@ -1,8 +1,8 @@
 // The statistic of rtk_render_frame_noise (rtk.h; item 3 of rtk_render_adaptive's contract at n = spp), once for host and device:
 // the luminance of a sample colour, the update of a pixel's two running sums, and the standard error of its mean luminance.
-// k_frame_moments (frame_noise.hip) and tests/cpp/frame_noise_plan_check.cpp both compile exactly these expressions; the library
-// and the check are built with -ffp-contract=off, so neither side fuses a product into a sum.
-// (k_adaptive_accumulate / k_adaptive_decide of adaptive.hip keep their own copies of the same expressions.)
+// k_frame_moments (frame_noise.hip), k_adaptive_accumulate / k_adaptive_decide (adaptive.hip) and
+// tests/cpp/frame_noise_plan_check.cpp all compile exactly these expressions; the library and the check are built with
+// -ffp-contract=off, so no side fuses a product into a sum.
 #pragma once
 
 #if defined(__HIPCC__)

@@ -3,49 +3,27 @@ program (tests/cpp/temporal_plan_check.cpp), plain and with the host sanitizers,
 tests/ref_camera.py makes camera rays from."""
 import os
 import re
-import subprocess
 
 import numpy as np
 
+import plan_check
 import temporal_model as tm
 from conftest import ROOT
 
-PKG = os.path.join(ROOT, "simd-raytracer_amd")
-BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
 PLAN_SRC = os.path.join(ROOT, "tests", "cpp", "temporal_plan_check.cpp")
 PLAN_DEPS = [PLAN_SRC, os.path.join(ROOT, "include", "rtk.h")] + \
-    [os.path.join(PKG, "csrc", f) for f in ("temporal_plan.hpp", "temporal_math.hpp", "camera_plan.hpp", "denoise_plan.hpp")]
+    plan_check.csrc("temporal_plan.hpp", "temporal_math.hpp", "camera_plan.hpp", "denoise_plan.hpp")
+FLAGS = ("-ffp-contract=off",)
 LINES = ("refusals ok", "planes ok", "scalars ok", "grid ok", "all ok")
 SHAPES = ((37, 19, 60.0), (5, 3, 60.0), (1, 1, 90.0), (70, 36, 40.0), (130, 70, 60.0), (1920, 1080, 73.5), (16384, 16384, 179.0), (3, 1000, 1.0))
-
-
-def _stale(exe, deps):
-    return not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)
-
-
-def _build_plan_check(name, extra):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    if _stale(exe, PLAN_DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra,
-                               "-I" + os.path.join(PKG, "csrc"), PLAN_SRC, "-o", exe])
-    return exe
-
-
-def _run_plan_check(exe):
-    args = [str(v) for shape in SHAPES for v in shape]
-    res = subprocess.run([exe, *args], capture_output=True, text=True)
-    assert res.returncode == 0 and "FAILED" not in res.stdout, res.stdout + res.stderr
-    for line in LINES:
-        assert line in res.stdout, res.stdout
-    return res
+ARGS = [str(v) for shape in SHAPES for v in shape]
 
 
 def test_temporal_plan_refusals_planes_scalars_and_grid():
     """The refusals in the header's order with the ends of every range; the planes a call needs and both families; the alignment of
     every plane of the device variant; tiles that give every pixel to one workgroup of a bounded grid, from 1x1 to 16384x16384.
     The scalars the kernel gets are, bit for bit, those the camera rays of ref_camera.py are made from."""
-    res = _run_plan_check(_build_plan_check("temporal_plan_check", []))
+    res = plan_check.run(plan_check.build("temporal_plan_check", PLAN_SRC, PLAN_DEPS, FLAGS), LINES, ARGS)
     got = {(int(w), int(h)): tuple(int(x, 16) for x in words.split())
            for w, h, words in re.findall(r"scalars (\d+) (\d+): ([0-9a-f ]+)", res.stdout)}
     assert len(got) == len(SHAPES)
@@ -56,5 +34,5 @@ def test_temporal_plan_refusals_planes_scalars_and_grid():
 
 def test_temporal_plan_under_host_sanitizers():
     """The same stand-alone host program built with AddressSanitizer and UndefinedBehaviorSanitizer, run once."""
-    res = _run_plan_check(_build_plan_check("temporal_plan_check_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]))
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
+    res = plan_check.run(plan_check.build("temporal_plan_check_san", PLAN_SRC, PLAN_DEPS, FLAGS, plan_check.SANITIZE), LINES, ARGS)
+    plan_check.assert_sanitizers_quiet(res)

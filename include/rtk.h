@@ -807,6 +807,51 @@ int rtk_temporal_accumulate_device(const rtk_temporal_params *p, const rtk_tempo
                                    const rtk_temporal_outputs *out /* structs on the HOST, DEVICE planes, 4-byte aligned */,
                                    void *hip_stream);
 
+/* ---- motion: where each pixel's surface point was in the previous pose ----
+ * rtk_temporal_accumulate reprojects camera motion only: it projects the g-buffer's world position through the previous view, and
+ * after rtk_accel_update_vertices a surface's world position has moved, so the history of every pixel on a moved mesh fails the
+ * tangent-plane test.  rtk_render_motion closes that: from a frame's `tri` and `bary` planes (rtk_gbuffer) and the vertices of the
+ * PREVIOUS pose it gives `prev_position`, the point of the previous pose that each pixel's surface point was.  Handed to
+ * rtk_temporal_accumulate as cur->position, the temporal contract runs unchanged in the previous frame's world: projection, mesh
+ * test and tangent-plane test against the previous guides.  On request it also gives `motion`, the screen-space vector external
+ * consumers expect.  Every mesh's vertex count is fixed for the accel's life, so a vertex array of any pose fits the accel's
+ * CURRENT topology; the caller keeps last frame's vertices and view.  One image per call.  The reference has no such step; the
+ * arithmetic is spelt out here and pinned, bit for bit, by tests/motion_model.py.
+ * Planes: tri [h][w] and bary [h][w][2] as rtk_gbuffer writes them; prev_vertices [n_vertices][3], all meshes concatenated in the
+ * layout of rtk_scene_desc.vertices; prev_position [h][w][3]; motion [h][w][2] (x, y).  Only the planes asked for are written.
+ * The outputs may not alias the inputs or each other.
+ * All arithmetic is float, in the order written, without contraction.  For each pixel (x, y), px = y * w + x:
+ *   1. id = tri[px].  The pixel is a MISS iff id >= n_triangles of the accel's current topology (that of the last
+ *      rtk_accel_update_geometry, else the scene's): this covers 0xFFFFFFFF and any stale or hostile id, and nothing is
+ *      dereferenced with such an id.  A miss writes prev_position = 0 0 0 and both words of motion as the bits 0x7FC00000.
+ *   2. i0, i1, i2 = the triangle's three global vertex ids; A, B, C = prev_vertices[i0], [i1], [i2]; u, v = bary[px];
+ *      w = (1.0f - u) - v; per component P' = ((w * A) + (u * B)) + (v * C) -- u weighs vertex 1, v vertex 2 and w vertex 0, the
+ *      reference's convention (kd_tree_simd.hpp:250).  A non-finite u or v propagates; it is not a miss.  prev_position = P'.
+ *   3. motion: P' goes through step 2 of the temporal contract above with C and M of *prev_view and the scalars of *p, up to fx
+ *      and fy.  If `cz < 0.0f` evaluates true, motion = (fx - (float)x, fy - (float)y): previous place minus present place, in
+ *      pixels.  There is no range test: off-screen values pass as computed.  Otherwise both words are the miss bits.
+ * The call reads the accel's live topology and nothing else of its state: the camera, the cost tables, the engine verdict and
+ * the counters stay as they are.
+ * What runs (csrc/motion.hip): one launch of k_motion, one thread per pixel, one 256-thread workgroup per 16x16 tile, the
+ * workgroups striding over the tiles.  No workspace, no LDS, no atomics.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL accel, p, tri, bary, prev_vertices or out; width or height outside
+ * [1, 16384]; a fov_degrees that is not finite or not inside (0, 180); both outputs NULL; motion wanted without prev_view; (device
+ * variant) a plane or the vertex array not 4-byte aligned.  Then RTK_ERR_NO_DEVICE.  A refused call changes nothing.
+ * The device variant is stream-ordered, waits on the device for the last update's event as every entry point does, and allocates
+ * nothing once the accel's topology tables exist: the first call on an accel that no update has touched makes them and may block
+ * the host there once; otherwise the host is never blocked.  The structs and *prev_view are read on the host before it returns.
+ * Stream capture is not claimed.  The host variant stages its planes on the device and is synchronous. */
+typedef struct { int32_t width, height; double fov_degrees; } rtk_motion_params;      /* 16 bytes */
+typedef struct { float *prev_position; /* [h][w][3] */ float *motion; /* [h][w][2] */ } rtk_motion_outputs;  /* 16 bytes; either may be NULL, not both */
+
+int rtk_render_motion(rtk_accel *accel, const rtk_motion_params *p, const uint32_t *tri, const float *bary /* host planes */,
+                      const float *prev_vertices /* host [n_vertices][3] */, const rtk_view *prev_view /* host; required iff out->motion */,
+                      const rtk_motion_outputs *out /* host planes */);
+int rtk_render_motion_device(rtk_accel *accel, const rtk_motion_params *p, const uint32_t *d_tri, const float *d_bary,
+                             const float *d_prev_vertices /* DEVICE planes and vertices, 4-byte aligned */,
+                             const rtk_view *prev_view /* HOST */, const rtk_motion_outputs *out /* struct on the HOST, DEVICE planes */,
+                             void *hip_stream);
+
 /* ---- lights, materials and background of a live accel ----
  * The reference keeps them plain mutable members of scene<F> (scene/scene.hpp:14-22, scene/light.hpp, scene/material/ *.hpp,
  * settings::background_color) and reads them when render_frame / color_hit run; so does the accel.  The two structs have the

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "rtk_render_frame_noise", "rtk_render_frame_noise_device", "rtk_debug_noise_fallbacks",
     "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
     "rtk_temporal_accumulate", "rtk_temporal_accumulate_device",
+    "rtk_render_motion", "rtk_render_motion_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
     "rtk_accel_get_textures", "rtk_accel_get_texture_pixels", "rtk_accel_set_textures", "rtk_accel_set_texture_pixels",
@@ -195,6 +196,18 @@ class TemporalOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "length")]
 
 
+class MotionParams(C.Structure):
+    """rtk.h rtk_motion_params; 16 bytes."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_degrees", C.c_double)]
+
+
+class MotionOutputs(C.Structure):
+    """rtk.h rtk_motion_outputs: either plane may be NULL, not both; 16 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("prev_position", "motion")]
+
+
+MOTION_MISS_BITS = 0x7FC00000                         # rtk.h: both words of a pixel's motion when there is none to report
+
 # the planes of a g-buffer in the struct's order: name -> (trailing shape, dtype); miss values in rtk.h
 GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
@@ -275,6 +288,9 @@ if hasattr(_L, "rtk_temporal_accumulate"):            # (as above: an older buil
                                            C.POINTER(TemporalOutputs)]
     _L.rtk_temporal_accumulate_device.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory),
                                                   C.POINTER(TemporalOutputs), _vp]
+if hasattr(_L, "rtk_render_motion"):                  # (as above: an older build under RTK_LIB_OVERRIDE has no such call)
+    _L.rtk_render_motion.argtypes = [_vp, C.POINTER(MotionParams), _vp, _vp, _vp, _vp, C.POINTER(MotionOutputs)]
+    _L.rtk_render_motion_device.argtypes = [_vp, C.POINTER(MotionParams), _vp, _vp, _vp, _vp, C.POINTER(MotionOutputs), _vp]
 _L.rtk_accel_get_lights.argtypes =[_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 _L.rtk_accel_set_lights.argtypes = [_vp, _vp, C.c_int32]
 _L.rtk_accel_set_lights_device.argtypes = [_vp, _vp, C.c_int32, _vp]
@@ -498,6 +514,15 @@ class TemporalConfig:
     def to_c(self, width: int, height: int) -> TemporalParams:
         return TemporalParams(width, height, float(self.fov_degrees), np.float32(self.alpha_min), np.float32(self.plane_tolerance),
                               np.float32(self.normal_min_dot), self.max_history)
+
+
+@dataclass
+class MotionConfig:
+    """rtk.h rtk_motion_params without the image size."""
+    fov_degrees: float = 90.0      # of the frame whose planes are handed in and of the previous view, as RenderConfig.fov_degrees
+
+    def to_c(self, width: int, height: int) -> MotionParams:
+        return MotionParams(width, height, float(self.fov_degrees))
 
 
 @dataclass(frozen=True)
@@ -872,6 +897,49 @@ class KdTreeSimdAccel:
         gb = GBuffer(**{n: (int(ptr) or None) for n, ptr in planes.items()})
         p = cfg.to_c()
         _check(_L.rtk_render_gbuffer_device(self._h, C.byref(p), sample, d_views_ptr or None, n_views, C.byref(gb), stream))
+
+    # ---- where each pixel's surface point was in the previous pose (rtk.h rtk_motion_params)
+    def render_motion(self, tri: np.ndarray, bary: np.ndarray, prev_vertices: np.ndarray, prev_view=None,
+                      cfg: MotionConfig | None = None, planes=("prev_position", "motion")) -> dict:
+        """tri [h, w] uint32 and bary [h, w, 2] float32: planes of render_gbuffer for ONE view; prev_vertices [n_vertices, 3] float32:
+        the previous pose, all meshes concatenated as in SceneDesc; prev_view = (position[3], matrix[9]), the previous camera,
+        needed for `motion`.  -> {"prev_position": [h, w, 3], "motion": [h, w, 2]} for the planes asked for: the point of the
+        previous pose under each pixel (0 on a miss; hand it to temporal_accumulate as cur's position) and previous place minus
+        present place in pixels (the bits MOTION_MISS_BITS where there is none).  The accel's current triangle lists are used."""
+        tri = np.ascontiguousarray(tri)
+        if tri.dtype != np.uint32 or tri.ndim != 2 or tri.size == 0:
+            raise ValueError("tri must be uint32 [h, w] and not empty")
+        h, w = tri.shape
+        bary = _plane(bary, (h, w, 2), "bary", required=True)
+        n = self.scene.info.n_vertices
+        prev_vertices = _plane(prev_vertices, (n, 3), "prev_vertices", required=True)
+        unknown = [p for p in planes if p not in ("prev_position", "motion")]
+        if unknown:
+            raise ValueError(f"unknown motion planes {unknown}: choose from prev_position, motion")
+        out = {}
+        if "prev_position" in planes:
+            out["prev_position"] = np.zeros((h, w, 3), np.float32)
+        if "motion" in planes:
+            out["motion"] = np.zeros((h, w, 2), np.float32)
+        keep = None if prev_view is None else _view_record(prev_view)
+        spare = np.zeros(1, np.float32)                              # (a scene without vertices: a valid pointer nothing is read through)
+        outs = MotionOutputs(*(out[k].ctypes.data if k in out else None for k, _ in MotionOutputs._fields_))
+        p = (cfg or MotionConfig()).to_c(w, h)
+        _check(_L.rtk_render_motion(self._h, C.byref(p), tri.ctypes.data, bary.ctypes.data,
+                                    prev_vertices.ctypes.data if prev_vertices.size else spare.ctypes.data,
+                                    None if keep is None else keep.ctypes.data, C.byref(outs)))
+        return out
+
+    def render_motion_device(self, width: int, height: int, d_tri_ptr: int, d_bary_ptr: int, d_prev_vertices_ptr: int, out: dict,
+                             prev_view=None, cfg: MotionConfig | None = None, stream: int = 0) -> None:
+        """The same on raw device pointers (ints): out = {"prev_position": ptr, "motion": ptr}, 0 or a missing key = plane not
+        wanted; prev_view = (position[3], matrix[9]) as HOST values.  Stream-ordered; allocates nothing and never blocks the host
+        once the accel's topology tables exist (the first call on an accel no update has touched makes them) (rtk.h)."""
+        keep = None if prev_view is None else _view_record(prev_view)
+        outs = MotionOutputs(*((out.get(k) or None) for k, _ in MotionOutputs._fields_))
+        p = (cfg or MotionConfig()).to_c(width, height)
+        _check(_L.rtk_render_motion_device(self._h, C.byref(p), d_tri_ptr or None, d_bary_ptr or None, d_prev_vertices_ptr or None,
+                                           None if keep is None else keep.ctypes.data, C.byref(outs), stream or None))
 
     # ---- a frame whose pixel blocks stop sampling once they have converged (rtk.h rtk_adaptive_params)
     def render_adaptive(self, cfg: RenderConfig, adaptive: AdaptiveConfig):

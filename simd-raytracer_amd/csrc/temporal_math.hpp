@@ -39,8 +39,9 @@ RTK_TP_FN bool is_hit(float depth) { return depth >= 0.0f; }   // (a NaN is no h
 RTK_TP_FN float max_of(float x, float f) { return x > f ? x : f; }
 RTK_TP_FN float abs_of(float x) { return __builtin_fabsf(x); }
 
-// step 2 of rtk.h: false = P does not land in the previous frame
-RTK_TP_FN bool project(const Consts &k, const float P[3], Foot &f) {
+// step 2 of rtk.h up to its range test: where P lies in the previous frame, in pixels; false = not in front of that camera.
+// (rtk_render_motion stops here: motion_math.hpp.)
+RTK_TP_FN bool place(const Consts &k, const float P[3], float &fx, float &fy) {
     const float dx = P[0] - k.cam[0], dy = P[1] - k.cam[1], dz = P[2] - k.cam[2];
     const float cx = (k.m[0] * dx + k.m[1] * dy) + k.m[2] * dz;
     const float cy = (k.m[3] * dx + k.m[4] * dy) + k.m[5] * dz;
@@ -49,8 +50,15 @@ RTK_TP_FN bool project(const Consts &k, const float P[3], Foot &f) {
     const float iz = -cz;
     const float qx = cx / iz, qy = cy / iz;
     const float ux = (qx / k.th) / k.aspect, uy = qy / k.th;
-    const float fx = ((ux + 1.0f) * 0.5f) * k.wf - 0.5f;
-    const float fy = ((1.0f - uy) * 0.5f) * k.hf - 0.5f;
+    fx = ((ux + 1.0f) * 0.5f) * k.wf - 0.5f;
+    fy = ((1.0f - uy) * 0.5f) * k.hf - 0.5f;
+    return true;
+}
+
+// step 2 of rtk.h: false = P does not land in the previous frame
+RTK_TP_FN bool project(const Consts &k, const float P[3], Foot &f) {
+    float fx, fy;
+    if (!place(k, P, fx, fy)) return false;
     if (!(fx > -1.0f && fx < k.wf && fy > -1.0f && fy < k.hf)) return false;      // (a NaN or an infinity fails)
     // only now: both lie in (-1, 16384), so the floors convert exactly
     const float x0f = __builtin_floorf(fx), y0f = __builtin_floorf(fy);

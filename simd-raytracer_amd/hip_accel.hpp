@@ -455,6 +455,42 @@ struct hip_accel {
         return r;
     }
 
+    // Where each pixel's surface point was in the previous pose (rtk_render_motion): from ONE view of a render_gbuffer result with
+    // its tri and bary planes, the vertices of the previous pose (all meshes concatenated in mesh order, as update_vertices takes
+    // them) and, for `motion`, the previous camera.  prev_position [h][w] x 3 floats (0 on a miss) is what rtk_temporal_accumulate
+    // takes as the new frame's position after an update; motion [h][w] x 2 floats is previous place minus present place in pixels
+    // (both words 0x7FC00000 where there is none).  Without a previous camera motion stays empty.
+    struct motion_result {
+        std::size_t width = 0, height = 0;
+        std::vector<float> prev_position, motion;
+    };
+    [[nodiscard]] motion_result render_motion(const gbuffer_result &g, std::size_t view, const std::vector<vec3<F>> &prev_vertices,
+                                              double fov_degrees, const camera<F> *prev_camera = nullptr) const {
+        const std::size_t pixels = g.width * g.height;
+        if (view >= g.views || g.tri.size() < (view + 1) * pixels || g.bary.size() < (view + 1) * pixels * 2)
+            throw std::invalid_argument("hip_accel::render_motion: the g-buffer has no tri and bary planes of that view");
+        std::size_t n = 0;
+        for (const auto &mesh : scene_ptr->meshes) n += mesh.vertices.size();
+        if (prev_vertices.size() != n) throw std::invalid_argument("hip_accel::render_motion: one position per vertex of the scene");
+        std::vector<float> flat;
+        flat.reserve(n * 3 + 3);
+        for (const auto &v : prev_vertices) { flat.push_back(v.x); flat.push_back(v.y); flat.push_back(v.z); }
+        flat.resize(n * 3 + 3);                                              // (a valid pointer for a scene without vertices)
+        motion_result r;
+        r.width = g.width; r.height = g.height;
+        r.prev_position.resize(pixels * 3 + 1);
+        if (prev_camera) r.motion.resize(pixels * 2 + 1);
+        const rtk_motion_params p{static_cast<std::int32_t>(g.width), static_cast<std::int32_t>(g.height), fov_degrees};
+        const rtk_motion_outputs out{r.prev_position.data(), prev_camera ? r.motion.data() : nullptr};
+        rtk_view pv{};
+        if (prev_camera) pv = to_view(*prev_camera);
+        check(rtk_render_motion(accel_.get(), &p, g.tri.data() + view * pixels, g.bary.data() + view * pixels * 2, flat.data(),
+                                prev_camera ? &pv : nullptr, &out));
+        r.prev_position.resize(pixels * 3);
+        if (prev_camera) r.motion.resize(pixels * 2);
+        return r;
+    }
+
     // Rectangles of the frame `params` describes, all in one call (rtk_render_regions).  Tile: anything with x0, y0, x1, y1 --
     // the reference's render_tile (render/tile/tile.hpp), what its single / region / bucket schedulers hand to tile_worker, or
     // rtk_rect.  Every pixel is what render_frame(params) gives there; counters: the call's totals.

@@ -141,6 +141,9 @@ def _lib(fast: bool = False, isa: str | None = None):
     L.ora_render_frame.argtypes = [vp, C.POINTER(_RenderParams), vp, vp]
     L.ora_camera_rays.restype = C.c_int
     L.ora_camera_rays.argtypes = [vp, C.POINTER(_RenderParams), C.c_int, vp]
+    L.ora_radiance.restype = C.c_int
+    L.ora_radiance.argtypes = [vp, C.POINTER(_RenderParams), vp, C.c_size_t, C.c_int, C.c_int, vp, vp]
+    L.ora_first_hit_albedo.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
     L.ora_write_ppm.restype = C.c_size_t
     L.ora_write_ppm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ora_root_key.restype = C.c_uint32
@@ -462,6 +465,26 @@ class Accel:
         if self.L.ora_camera_rays(self.h, C.byref(p), sample, rays.ctypes.data) != 0:
             raise ValueError("ora_camera_rays: bad parameters")
         return rays
+
+    def radiance(self, rays: np.ndarray, max_depth=5, diffuse_rays=0, seed=42, sample=0, cull=True, shadow_bias=1e-4,
+                 reflection_bias=1e-4, refraction_bias=1e-4):
+        """The colour caller-supplied rays [n, 6] see: intersect<cull> then color_hit, the background on a miss ->
+        (rgb float32 [n, 3], counters).  The RNG root key of ray i is that of pixel i of sample `sample`."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        p = _RenderParams(1, 1, 1, max_depth, diffuse_rays, seed, 90.0, np.float32(shadow_bias), np.float32(reflection_bias),
+                          np.float32(refraction_bias), 1, 1)
+        rgb = np.zeros((rays.shape[0], 3), np.float32)
+        cn = np.zeros((C_COUNT,), np.uint64)
+        self.L.ora_radiance(self.h, C.byref(p), rays.ctypes.data, rays.shape[0], 1 if cull else 0, sample, rgb.ctypes.data, cn.ctypes.data)
+        return rgb, dict(zip(COUNTER_NAMES, (int(x) for x in cn)))
+
+    def first_hit_albedo(self, rays: np.ndarray, cull: bool = True) -> np.ndarray:
+        """[n, 3]: sample(texture, hit, uvs) where a ray's first hit has a texture material (color_hit's own sampler), the
+        material's albedo on any other material, the background on a miss."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rgb = np.zeros((rays.shape[0], 3), np.float32)
+        self.L.ora_first_hit_albedo(self.h, rays.ctypes.data, rays.shape[0], 1 if cull else 0, rgb.ctypes.data)
+        return rgb
 
     def __del__(self):
         try:

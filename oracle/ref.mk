@@ -41,9 +41,11 @@ $(OUT)/ref_probe_w$(1)_d$(2)_$(3): $(SRC)
 	@mkdir -p $(OUT)
 	$(REFCXX) $(FLAGS) $(ISA_$(1)) -DRTK_REF_MAX_RAY_DEPTH=$(2) $(call tree_defs,$(3)) ref_probe.cpp -o $$@
 endef
-# every tree at every width with max_ray_depth 5; the default tree also with 10
+# every tree at every width with max_ray_depth 5; the default tree also with 10, and with 1 and 16 (the ends of the API's range)
 $(foreach w,$(WIDTHS),$(foreach t,$(TREES),$(eval $(call VARIANT,$(w),5,$(t)))))
 $(foreach w,$(WIDTHS),$(eval $(call VARIANT,$(w),10,default)))
+$(foreach w,$(WIDTHS),$(eval $(call VARIANT,$(w),1,default)))
+$(foreach w,$(WIDTHS),$(eval $(call VARIANT,$(w),16,default)))
 
 # kd_tree_accel (--scalar), leaf size 64
 ALL += $(OUT)/ref_probe_scalar_d5_default

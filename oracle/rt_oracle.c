@@ -959,6 +959,44 @@ int ora_render_frame(const ora_accel *a, const ora_render_params *p, float *rgb,
     return 0;
 }
 
+int ora_radiance(const ora_accel *a, const ora_render_params *p, const float *rays, size_t n, int cull, int sample, float *rgb,
+                 uint64_t *counters) {
+    frame_ctx f;
+    memset(&f, 0, sizeof(f));
+    f.accel = a; f.p = *p;
+    thread_ctx tc;
+    memset(&tc, 0, sizeof(tc));
+    tc.cn[ORA_C_COUNT] = p->count_work ? 1u : 0u;
+    const ora_scene *sc = a->scene;
+    const col background = mkcol(sc->background[0], sc->background[1], sc->background[2]);
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = rays + i * 6;
+        const ray3 ray = mkray(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]));
+        tc.cn[ORA_C_PRIMARY] += 1;
+        hit_rec h;
+        col c = background;
+        if (accel_intersect(a, &ray, cull, &h, tc.cn)) c = color_hit(&f, &tc, &h, 0, ora_root_key(p->seed, (uint32_t)i, (uint32_t)sample));
+        rgb[i * 3 + 0] = c.r; rgb[i * 3 + 1] = c.g; rgb[i * 3 + 2] = c.b;
+    }
+    if (counters) for (int k = 0; k < ORA_C_COUNT; ++k) counters[k] = tc.cn[k];
+    return 0;
+}
+
+void ora_first_hit_albedo(const ora_accel *a, const float *rays, size_t n, int cull, float *rgb) {
+    const ora_scene *sc = a->scene;
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = rays + i * 6;
+        const ray3 ray = mkray(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]));
+        hit_rec h;
+        col c = mkcol(sc->background[0], sc->background[1], sc->background[2]);
+        if (accel_intersect(a, &ray, cull, &h, NULL)) {
+            const material *m = &sc->materials[sc->meshes[h.mesh_idx].material_idx];
+            c = m->kind == ORA_MAT_TEXTURE ? sample_texture(&sc->textures[m->texture], &h) : mkcol(m->albedo[0], m->albedo[1], m->albedo[2]);
+        }
+        rgb[i * 3 + 0] = c.r; rgb[i * 3 + 1] = c.g; rgb[i * 3 + 2] = c.b;
+    }
+}
+
 /* io/image/ppm.hpp:7-25 */
 size_t ora_write_ppm(const float *rgb, int width, int height, char *buf, size_t cap) {
     size_t n = 0;

@@ -143,6 +143,17 @@ int ora_render_frame(const ora_accel *a, const ora_render_params *p, float *rgb,
  * rays [h][w][6] = origin xyz, direction xyz. */
 int ora_camera_rays(const ora_accel *a, const ora_render_params *p, int sample, float *rays);
 
+/* The colour caller-supplied rays see (render/render.hpp:64-69 for one ray each): intersect<cull>, then color_hit(.., 0), the
+ * background on a miss.  rays [n][6], rgb [n][3]; the RNG root key of ray i is ora_root_key(p->seed, i, sample).  Of `p` the
+ * depth, the GI rays, the seed and the biases are read.  One thread. */
+int ora_radiance(const ora_accel *a, const ora_render_params *p, const float *rays, size_t n, int cull, int sample, float *rgb,
+                 uint64_t *counters /* ORA_C_COUNT, overwritten; may be NULL */);
+
+/* What the light loop multiplies the light by at every ray's first hit (render/render.hpp:205, :235): sample(texture, hit, uvs)
+ * on a texture material (the sample_texture that color_hit calls), the material's albedo on any other, the background on a
+ * miss.  rays [n][6], rgb [n][3]. */
+void ora_first_hit_albedo(const ora_accel *a, const float *rays, size_t n, int cull, float *rgb);
+
 /* write_ppm (io/image/ppm.hpp:7-25): returns bytes written into buf (or needed if buf==NULL). */
 size_t ora_write_ppm(const float *rgb, int width, int height, char *buf, size_t cap);
 

@@ -1,4 +1,5 @@
-"""Inputs and comparisons shared by tests/test_ref_probe.py, tests/test_gpu_ref_probe.py and tools/make_ref_probe_fixtures.py.
+"""Inputs and comparisons shared by tests/test_ref_probe.py, tests/test_gpu_ref_probe.py, tests/test_material_scenes.py,
+tests/test_gpu_material_scenes.py and tools/make_ref_probe_fixtures.py.
 
 A helper, not a test.  The probe (oracle/ref_probe.cpp) is the reference's own code behind a file interface; what it wrote for
 the inputs below is recorded under tests/golden/ref_probe/ and must be reproduced bit for bit by the oracle, by the Python
@@ -145,6 +146,45 @@ def record(ora, flat, name, n_rays=224, n_seg=1024, views=(2, 32, 32)):
         out[f"rad_calls_d{d}"] = np.array([p.calls], np.int64)
         out[f"frame_d{d}"] = p.frame(); ran(p)
         out[f"frame_calls_d{d}"] = np.array([p.calls, p.hits], np.int64)
+    return {k: np.ascontiguousarray(v) for k, v in out.items()}, argv
+
+
+# ---------------------------------------------------------------- the generated material scenes (tests/material_scenes.py)
+
+MATERIAL_PREFIX = "material_"
+
+
+def material_fixture_names():
+    import material_scenes as ms
+    return {MATERIAL_PREFIX + v: v for v in ms.VARIANTS}
+
+
+def record_material(ora, flat):
+    """Run the probe (width 8; the packet counts at every width) on one variant of tests/material_scenes.py -> (arrays, command
+    lines): the tree, the 48 x 32 frame at max_ray_depth 1, 5, 10 and 16 with the probe's counts of intersect calls and hits,
+    the radiance of the special rays and of a 32 x 32 view at depths 5 and 16, the stacked-glass occlusion queries, and the
+    scene's own arrays."""
+    import material_scenes as ms
+    out, argv = {}, []
+    probes = {d: ora.RefProbe(flat, 8, d, size=ms.SIZE) for d in ms.DEPTHS}
+
+    def ran(p):
+        argv.append(" ".join(os.path.basename(a) for a in p.argv))
+
+    p5 = probes[5]
+    out["tree_box"], out["tree_link"], out["tree_refs"], _ = p5.tree(); ran(p5)
+    out["tree_packets"] = np.array([ora.RefProbe(flat, w).tree()[3] for w in WIDTHS], np.int64)
+    out["occ_rays"], out["occ_max_t"], _ = ms.stacked_glass_queries()
+    out["occ_answer"] = p5.occluded(out["occ_rays"], out["occ_max_t"]); ran(p5)
+    out["occ_calls"] = np.array([p5.calls], np.int64)
+    out["rad_rays"], _ = ms.radiance_rays(ora, flat)
+    for d in ms.RAD_DEPTHS:
+        out[f"rad_rgb_d{d}"] = probes[d].radiance(out["rad_rays"]); ran(probes[d])
+        out[f"rad_calls_d{d}"] = np.array([probes[d].calls], np.int64)
+    for d in ms.DEPTHS:
+        out[f"frame_d{d}"] = probes[d].frame(); ran(probes[d])
+        out[f"frame_calls_d{d}"] = np.array([probes[d].calls, probes[d].hits], np.int64)
+    out.update(ms.scene_arrays(flat))
     return {k: np.ascontiguousarray(v) for k, v in out.items()}, argv
 
 

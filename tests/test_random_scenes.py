@@ -1,6 +1,7 @@
 """Generated scenes through the C-ABI scene constructor (rtk_scene_create) against the oracle: triangle soups, a bumpy height
-field, axis-aligned quads (rays parallel to box planes -> inf / NaN slabs), zero-area and duplicated triangles, all four
-material kinds and textures, several lights, a light exactly on a surface.  Frames must be bit-identical through every engine."""
+field, axis-aligned quads (rays parallel to box planes -> inf / NaN slabs), zero-area and duplicated triangles, the four
+material kinds that need no texture (no texture is made here: tests/material_scenes.py has them), several lights, a light exactly
+on a surface.  Frames must be bit-identical through every engine."""
 import os
 
 import numpy as np

@@ -79,7 +79,7 @@ def test_variants_cover_the_tree_parameter_tests(ora):
 def test_manifest_matches_the_files():
     import hashlib
     man = rc.manifest()
-    assert set(man["scenes"]) == set(rc.FIXTURE_SCENES) | {rc.EPS_FIXTURE}
+    assert set(man["scenes"]) == set(rc.FIXTURE_SCENES) | {rc.EPS_FIXTURE} | set(rc.material_fixture_names())
     for name, e in man["scenes"].items():
         for fn, meta in e["files"].items():
             data = open(os.path.join(rc.FIXTURE_DIR, fn), "rb").read()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Record what the reference computes, as test fixtures: runs the probe (oracle/_ref/ref_probe_*, built by
 __graft_entry__.build() from a checkout of the reference) on the inputs of tests/ref_probe_cases.py and writes
-tests/golden/ref_probe/<scene>_{queries,frames}.npz, the exactly-eps fixture and MANIFEST.json.  The files hold arrays only.  Run again, it writes the same bytes.
+tests/golden/ref_probe/<scene>_{queries,frames}.npz (the scene files and the generated variants of tests/material_scenes.py),
+the exactly-eps fixture and MANIFEST.json.  The files hold arrays only.  Run again, it writes the same bytes.
 
     python tools/make_ref_probe_fixtures.py [--check]      (--check: write nothing, fail if a file would change)"""
 import hashlib
@@ -29,7 +30,7 @@ def compile_line(width, depth, tree="default"):
 def main():
     check = "--check" in sys.argv[1:]
     ora.build()
-    need = [(w, 5, "default") for w in rc.WIDTHS] + [(8, 10, "default"), (8, 5, "eps_0.25")]
+    need = [(w, 5, "default") for w in rc.WIDTHS] + [(8, 10, "default"), (8, 5, "eps_0.25"), (8, 1, "default"), (8, 16, "default")]
     missing = [ora.ref_binary(*v) for v in need if not ora.ref_available(*v)]
     if missing:
         sys.exit("missing or not runnable on this host (run __graft_entry__.build() with the reference present): " + ", ".join(missing))
@@ -38,9 +39,14 @@ def main():
            "frame": list(rc.FRAME), "variants": {os.path.basename(ora.ref_binary(*v)): compile_line(*v) for v in need},
            "scenes": {}}
     changed = []
+    import material_scenes as ms
+    cases = [(name, rel + ".crtscene", lambda name=name, rel=rel: rc.record(ora, ora.load_crtscene(rc.scene_path(rel)), name))
+             for name, rel in rc.FIXTURE_SCENES.items()]
+    cases += [(name, f"tests/material_scenes.py::make_scene(ora, {v!r})", lambda v=v: rc.record_material(ora, ms.make_scene(ora, v)))
+              for name, v in rc.material_fixture_names().items()]
     with tempfile.TemporaryDirectory() as tmp:
-        for name, rel in rc.FIXTURE_SCENES.items():
-            arrays, argv = rc.record(ora, ora.load_crtscene(rc.scene_path(rel)), name)
+        for name, scene, run in cases:
+            arrays, argv = run()
             files = {}
             for part in rc.PARTS:
                 new = os.path.join(tmp, f"{name}_{part}.npz")
@@ -52,7 +58,7 @@ def main():
                     if not check:
                         open(path, "wb").write(data)
                 files[os.path.basename(path)] = {"bytes": len(data), "sha256": hashlib.sha256(data).hexdigest()}
-            man["scenes"][name] = {"scene": rel + ".crtscene", "files": files,
+            man["scenes"][name] = {"scene": scene, "files": files,
                                    "arrays": {k: [str(v.dtype) if v.dtype.names is None else "REF_HIT_DTYPE", list(v.shape)] for k, v in sorted(arrays.items())},
                                    "commands": argv}
             print(name, {k: v["bytes"] for k, v in files.items()})

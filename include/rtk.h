@@ -807,6 +807,59 @@ int rtk_temporal_accumulate_device(const rtk_temporal_params *p, const rtk_tempo
                                    const rtk_temporal_outputs *out /* structs on the HOST, DEVICE planes, 4-byte aligned */,
                                    void *hip_stream);
 
+/* ---- temporal accumulation, clamped: the history bounded by the new frame's neighbourhood ----
+ * rtk_temporal_accumulate trusts any history that passes its geometric tests, whatever its colour: a shadow, a highlight or a
+ * mirror image that has moved is blended in at weight 1 - 1/N.  The clamped call pulls the history's colour into the colour
+ * statistics of the NEW frame around the pixel before it blends, raises the history's variance to that of the neighbourhood mean
+ * where it did so, and can shorten the history there.  Structs, planes, families, scalars and steps 1 to 3 are those of
+ * rtk_temporal_accumulate above, verbatim: the pass-through without history, the projection, the four guarded taps, sum_c, sum_v,
+ * sum_l, sum_w, and "history exists iff sum_w > 0.0f".  All arithmetic is float, in the order written, without contraction; pinned
+ * bit for bit by tests/temporal_clamp_model.py.  For a pixel p WITH history, with r = radius:
+ *   3a. The box: nf = 0.0f; per channel s1 = s2 = 0.0f; sv = 0.0f.  Taps q = p + (dx, dy) in the NEW frame, dy = -r..r the outer
+ *       and dx = -r..r the inner loop.  A tap is skipped when it lies outside the image (never clamped to the edge, never
+ *       wrapped); when `cur.depth_q >= 0.0f` is not true; when mesh planes are given and cur.mesh_q != cur.mesh_p.  The centre tap
+ *       always passes.  An accepted tap adds nf = nf + 1.0f; per channel s1 = s1 + c_q and s2 = s2 + c_q * c_q; sv = sv + var_q
+ *       with var_q = noise_q * noise_q (1.0f without noise planes).
+ *   3b. The bounds, per channel: m = s1 / nf; d = s2 / nf - m * m; d = d > 0.0f ? d : 0.0f; sg = (float)sqrt((double)d);
+ *       e = gamma * sg; lo = m - e; hi = m + e.
+ *   3c. The clamp, per channel: hc = sum_c / sum_w; hc' = hc < lo ? lo : (hc > hi ? hi : hc).  The pixel is CLAMPED iff in some
+ *       channel `hc < lo` or `hc > hi` evaluated true.  A non-finite colour in the box makes the bounds non-finite, and the
+ *       comparisons decide as written: a NaN bound clamps nothing.
+ *   3d. The variance: hv = sum_v / (sum_w * sum_w).  On a clamped pixel also vb = (sv / nf) / nf and hv = hv > vb ? hv : vb: a
+ *       history that was pulled to the neighbourhood mean is known no better than that mean, which reopens the luminance weight
+ *       of rtk_denoise_frame where the history was wrong.
+ *   4.  The blend of the plain call with hc' and that hv: L = sum_l / sum_w; on a clamped pixel L = L * history_keep;
+ *       N = L + 1.0f, then N = N < nmax ? N : nmax; a = max(1.0f / N, alpha_min); om = 1.0f - a; out.rgb = (om * hc') + (a * c);
+ *       var = ((om * om) * hv) + ((a * a) * var_c); out.noise = (float)sqrt((double)var); out.length = N.  history_keep = 1 gives
+ *       the length of the plain call, 0 makes a clamped pixel start over.
+ * A gamma so large that no comparison fires gives the plain call's bits.
+ * Aliasing: neighbours of the new frame are read, so unlike the plain call out->rgb == cur->rgb is refused, and so is
+ * out->noise == cur->noise when both are set.  Any other overlap of an output with a plane of cur or prev is the caller's fault.
+ * What runs (csrc/temporal_clamp.hip): one launch of k_temporal_accumulate_clamped<radius>, one 256-thread workgroup per 16x16
+ * pixel tile, the workgroups striding over the tiles; each stages its tile of the new frame with a halo of r pixels in
+ * (16 + 2r)^2 * 20 bytes of LDS.  No workspace, no atomics.
+ * Errors, in this order, all RTK_ERR_INVALID: a NULL p, k, cur or out; the checks of rtk_temporal_params in that struct's order;
+ * radius outside [1, 3]; gamma not finite or negative; history_keep not finite or outside [0, 1]; the plane and family checks of
+ * the plain call in its order; the two aliasing refusals; (device variant) a plane that is not 4-byte aligned.  Then
+ * RTK_ERR_NO_DEVICE.
+ * The device variant is stream-ordered on the current device, allocates nothing, never blocks the host and is one launch; the
+ * structs are read on the host before it returns.  Stream capture is not claimed.  The host variant stages the planes as the plain
+ * call's does and is synchronous. */
+typedef struct {
+    int32_t radius;        /* 1..3: the box is the (2r+1) x (2r+1) neighbourhood of the NEW frame */
+    float   gamma;         /* finite, >= 0: per channel the history is clamped to mean +- gamma * standard deviation */
+    float   history_keep;  /* finite, in [0, 1]: a clamped pixel keeps this share of its history length */
+    int32_t reserved;      /* ignored */
+} rtk_temporal_clamp;      /* 16 bytes */
+
+int rtk_temporal_accumulate_clamped(const rtk_temporal_params *p, const rtk_temporal_clamp *k,
+                                    const rtk_temporal_frame *cur /* host planes */, const rtk_temporal_history *prev,
+                                    const rtk_temporal_outputs *out);
+int rtk_temporal_accumulate_clamped_device(const rtk_temporal_params *p, const rtk_temporal_clamp *k, const rtk_temporal_frame *cur,
+                                           const rtk_temporal_history *prev,
+                                           const rtk_temporal_outputs *out /* structs on the HOST, DEVICE planes, 4-byte aligned */,
+                                           void *hip_stream);
+
 /* ---- motion: where each pixel's surface point was in the previous pose ----
  * rtk_temporal_accumulate reprojects camera motion only: it projects the g-buffer's world position through the previous view, and
  * after rtk_accel_update_vertices a surface's world position has moved, so the history of every pixel on a moved mesh fails the

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "rtk_render_frame_noise", "rtk_render_frame_noise_device", "rtk_debug_noise_fallbacks",
     "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
     "rtk_temporal_accumulate", "rtk_temporal_accumulate_device",
+    "rtk_temporal_accumulate_clamped", "rtk_temporal_accumulate_clamped_device",
     "rtk_render_motion", "rtk_render_motion_device",
     "rtk_accel_get_lights", "rtk_accel_set_lights", "rtk_accel_set_lights_device",
     "rtk_accel_get_materials", "rtk_accel_set_materials", "rtk_accel_get_background", "rtk_accel_set_background",
@@ -196,6 +197,11 @@ class TemporalOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rgb", "noise", "length")]
 
 
+class TemporalClamp(C.Structure):
+    """rtk.h rtk_temporal_clamp; 16 bytes."""
+    _fields_ = [("radius", C.c_int32), ("gamma", C.c_float), ("history_keep", C.c_float), ("reserved", C.c_int32)]
+
+
 class MotionParams(C.Structure):
     """rtk.h rtk_motion_params; 16 bytes."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_degrees", C.c_double)]
@@ -288,6 +294,11 @@ if hasattr(_L, "rtk_temporal_accumulate"):            # (as above: an older buil
                                            C.POINTER(TemporalOutputs)]
     _L.rtk_temporal_accumulate_device.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory),
                                                   C.POINTER(TemporalOutputs), _vp]
+if hasattr(_L, "rtk_temporal_accumulate_clamped"):    # (likewise)
+    _L.rtk_temporal_accumulate_clamped.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame),
+                                                   C.POINTER(TemporalHistory), C.POINTER(TemporalOutputs)]
+    _L.rtk_temporal_accumulate_clamped_device.argtypes = [C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame),
+                                                          C.POINTER(TemporalHistory), C.POINTER(TemporalOutputs), _vp]
 if hasattr(_L, "rtk_render_motion"):                  # (as above: an older build under RTK_LIB_OVERRIDE has no such call)
     _L.rtk_render_motion.argtypes = [_vp, C.POINTER(MotionParams), _vp, _vp, _vp, _vp, C.POINTER(MotionOutputs)]
     _L.rtk_render_motion_device.argtypes = [_vp, C.POINTER(MotionParams), _vp, _vp, _vp, _vp, C.POINTER(MotionOutputs), _vp]
@@ -514,6 +525,17 @@ class TemporalConfig:
     def to_c(self, width: int, height: int) -> TemporalParams:
         return TemporalParams(width, height, float(self.fov_degrees), np.float32(self.alpha_min), np.float32(self.plane_tolerance),
                               np.float32(self.normal_min_dot), self.max_history)
+
+
+@dataclass
+class ClampConfig:
+    """rtk.h rtk_temporal_clamp: how temporal_accumulate(..., clamp=) bounds the history by the new frame's neighbourhood."""
+    radius: int = 1                # 1..3: the box is (2 * radius + 1)^2 pixels of the new frame
+    gamma: float = 1.0             # >= 0: the history is clamped to mean +- gamma * standard deviation of the box, per channel
+    history_keep: float = 1.0      # in [0, 1]: the share of its history length a clamped pixel keeps
+
+    def to_c(self) -> TemporalClamp:
+        return TemporalClamp(self.radius, np.float32(self.gamma), np.float32(self.history_keep), 0)
 
 
 @dataclass
@@ -1247,13 +1269,14 @@ def _view_record(view) -> np.ndarray:
     return np.ascontiguousarray(v, np.float32)
 
 
-def temporal_accumulate(cur: dict, prev: dict | None, cfg: TemporalConfig | None = None) -> dict:
+def temporal_accumulate(cur: dict, prev: dict | None, cfg: TemporalConfig | None = None, clamp: ClampConfig | None = None) -> dict:
     """The frame `cur` blended with the history `prev`, fetched where cur's world positions lay in prev's camera.  cur: rgb,
     position, normal [h, w, 3] and depth [h, w] float32 (the planes render_frame_noise and render_gbuffer write), optionally noise
     [h, w] float32 and mesh [h, w] uint32.  prev: None to start a history, else rgb, noise and length of the previous call's
     result, position, normal, depth (and mesh) of the previous frame's g-buffer and view = (position[3], matrix[9]), its camera;
     it has noise / mesh exactly when cur has.  -> dict rgb [h, w, 3], noise [h, w] or None, length [h, w].  The arithmetic is
-    spelt out in rtk.h; a pixel without history keeps its bits and gets length 1."""
+    spelt out in rtk.h; a pixel without history keeps its bits and gets length 1.  clamp: None for rtk_temporal_accumulate, else
+    rtk_temporal_accumulate_clamped, which pulls the history into the colour statistics of cur's neighbourhood first."""
     rgb = np.ascontiguousarray(cur["rgb"], np.float32)
     if rgb.ndim != 3 or rgb.shape[-1] != 3 or rgb.size == 0:
         raise ValueError("rgb must be [h, w, 3] and not empty")
@@ -1284,16 +1307,22 @@ def temporal_accumulate(cur: dict, prev: dict | None, cfg: TemporalConfig | None
                length=np.zeros((h, w), np.float32))
     outs = TemporalOutputs(ptr(out["rgb"]), ptr(out["noise"]), ptr(out["length"]))
     p = (cfg or TemporalConfig()).to_c(w, h)
-    _check(_L.rtk_temporal_accumulate(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs)))
+    if clamp is None:
+        _check(_L.rtk_temporal_accumulate(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs)))
+    else:
+        k = clamp.to_c()
+        _check(_L.rtk_temporal_accumulate_clamped(C.byref(p), C.byref(k), C.byref(frame), None if hist is None else C.byref(hist),
+                                                  C.byref(outs)))
     return out
 
 
 def temporal_accumulate_device(width: int, height: int, cur: dict, prev: dict | None, out: dict, cfg: TemporalConfig | None = None,
-                               stream: int = 0) -> None:
+                               stream: int = 0, clamp: ClampConfig | None = None) -> None:
     """The same on raw device pointers (ints; 0 or a missing key = no such plane): cur with rgb, noise, position, normal, depth,
     mesh; prev (or None) with rgb, noise, length, position, normal, depth, mesh and view = (position[3], matrix[9]) as HOST
-    values; out with rgb, noise, length.  out's rgb / noise may be cur's.  Stream-ordered on the current device, one launch,
-    allocates nothing, never blocks the host (rtk.h)."""
+    values; out with rgb, noise, length.  out's rgb / noise may be cur's, unless clamp is given (then they are refused: the
+    clamped call reads cur's neighbours).  Stream-ordered on the current device, one launch, allocates nothing, never blocks the
+    host (rtk.h)."""
     frame = TemporalFrame(*((cur.get(n) or None) for n, _ in TemporalFrame._fields_))
     hist = keep = None
     if prev is not None:
@@ -1303,8 +1332,13 @@ def temporal_accumulate_device(width: int, height: int, cur: dict, prev: dict | 
         hist = TemporalHistory(*(vals[n] for n, _ in TemporalHistory._fields_))
     outs = TemporalOutputs(*((out.get(n) or None) for n, _ in TemporalOutputs._fields_))
     p = (cfg or TemporalConfig()).to_c(width, height)
-    _check(_L.rtk_temporal_accumulate_device(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs),
-                                             stream or None))
+    if clamp is None:
+        _check(_L.rtk_temporal_accumulate_device(C.byref(p), C.byref(frame), None if hist is None else C.byref(hist), C.byref(outs),
+                                                 stream or None))
+    else:
+        k = clamp.to_c()
+        _check(_L.rtk_temporal_accumulate_clamped_device(C.byref(p), C.byref(k), C.byref(frame), None if hist is None else C.byref(hist),
+                                                         C.byref(outs), stream or None))
 
 
 def format_ppm_rgb8(rgb8: np.ndarray) -> bytes:

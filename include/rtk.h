@@ -593,6 +593,74 @@ int rtk_render_gbuffer_device(rtk_accel *accel, const rtk_render_params *p, int3
                               const rtk_view *d_views /* DEVICE, 4-byte aligned; NULL as above */, int32_t n_views,
                               const rtk_gbuffer *out /* struct on the HOST, DEVICE plane pointers, 4-byte aligned */, void *hip_stream);
 
+/* ---- guides seen through mirrors and glass: the planes of the first surface that is actually SHADED ----
+ * rtk_render_gbuffer describes a mirror or glass pixel by the mirror's own surface; color_hit (render/render.hpp:239-301) shades
+ * what the mirror shows.  This call follows the specular chain of every camera ray -- the reflection ray off a reflective
+ * material (render.hpp:239-250), the refraction ray through a refractive one (:252-292; its weight 1 - fresnel is never below
+ * 1/2, :300-301) or its reflection ray under total internal reflection (:266-271) -- to the first surface of any other kind, and
+ * writes that surface's planes, placed in the "virtual" world in which it lies on a straight line behind the mirror.
+ * Contract, per pixel (px, py) of view v; all arithmetic is float, in the order written, without contraction:
+ *   ray = the pixel's camera ray (as rtk_render_gbuffer);  L = 0.0f;  M = identity (3x3);  k = 0;  mirrored = false
+ *   h = intersect<cull = true>(ray)
+ *   loop:
+ *     h is a miss                      -> end NO SURFACE
+ *     k == max_ray_depth               -> end NO SURFACE   (color_hit returns the background there, render.hpp:138-139)
+ *     L = L + h.t;  P = ray.o + (h.t * ray.d)
+ *     material kind of h.mesh:
+ *       RTK_MAT_REFLECTIVE: next = reflection of ray.d off hit_normal at P with reflection_bias (render.hpp:240-242);
+ *                           m = hit_normal;  fold(m)
+ *       RTK_MAT_REFRACTIVE: R = the refraction at P (render.hpp:252-292: i = normalized(ray.d), n = normalized(smooth_shading ?
+ *                           hit_normal : face_normal), the biases of *p)
+ *                           total internal reflection: next = R's reflection ray;  m = n;  fold(m)
+ *                           otherwise                : next = R's refraction ray;  M unchanged
+ *       anything else      -> end SURFACE
+ *     k = k + 1;  ray = next;  h = intersect<cull = false>(ray)
+ *   fold(m):  w_i = (M_i0 * m.x + M_i1 * m.y) + M_i2 * m.z;   M_ij = M_ij - ((2.0f * w_i) * m_j);   mirrored = true
+ * On SURFACE: depth = L;  position = o0 + (L * d0) over the CAMERA ray's origin and direction;  normal = the end hit's hit_normal,
+ * bit for bit, when `mirrored` is false, otherwise vn_i = (M_i0 * n.x + M_i1 * n.y) + M_i2 * n.z of it;  every other plane holds
+ * the end hit's fields exactly as rtk_render_gbuffer defines them for a first hit, over the chain's last ray (surface_position =
+ * ray.o + (h.t * ray.d)).  On NO SURFACE the planes take the miss values below.  bounces = k and last_ray are written either way
+ * (with max_ray_depth == 0 every pixel that hits anything is NO SURFACE, as color_hit shades it).
+ * What follows: for planar mirrors `position` and `normal` are exactly the mirror image of the shaded point, seen along a straight
+ * line -- a fixed world point whatever the camera does -- so rtk_temporal_accumulate[_clamped] and rtk_denoise_frame take depth,
+ * position, normal and mesh of this call in place of rtk_gbuffer's without any change; and a pixel with k == 0 holds
+ * rtk_render_gbuffer's bits in every shared plane.  For curved mirrors and for refraction it is the usual straight-line
+ * approximation: the virtual point moves with the camera, and the temporal step's mesh, normal and plane tests still guard it.
+ * last_ray with cull = (bounces == 0) reproduces the end hit through rtk_accel_intersect.
+ * Out of scope: moving geometry seen in a mirror (rtk_render_motion over the end hit's tri / bary gives a real, not a virtual,
+ * previous position), the reflection branch of a refracting surface and the Fresnel weight, more than one sample per call,
+ * sharding, rectangles.
+ * Views, sizes, `sample`, the cut into launches of whole views, the live state that is read and the state that is left alone, the
+ * stream order, the host variant's staging: rtk_render_gbuffer's, word for word.  The RTK_TRAVERSAL_FAST tie caveat compounds
+ * along the chain: only k == 0 pixels keep the parity mode's depth.  *p is validated as rtk_render_gbuffer validates it; beyond
+ * that max_ray_depth, reflection_bias and refraction_bias are CONSULTED (non-finite biases are not refused: they flow into the rays).
+ * What runs: one kernel (csrc/gbuffer_specular.hip), one wave per 8x8 pixel block of a view; a loop of at most max_ray_depth + 1
+ * wave-cooperative closest-hit queries, in which lanes whose chain has ended take no part.
+ * Errors, in this order: a NULL accel, p or out; what rtk_render_frame refuses for *p; sample outside [0, spp); world_size > 1,
+ * collect_stats != 0, n_views < 0; NULL views with n_views != 1; all twelve planes NULL; more than 2^56 pixels -> RTK_ERR_INVALID.
+ * Then n_views == 0 -> RTK_OK, nothing touched, device or not.  Then (device variant) a plane pointer or view table that is not 4-byte
+ * aligned -> RTK_ERR_INVALID.  Then RTK_ERR_NO_DEVICE. */
+typedef struct {               /* any pointer may be NULL = plane not wanted; at least one set.  [n_views][h][w] each */
+    float    *depth;           /* L, the path length (above); no surface: -1 */
+    float    *position;        /* [..][3] virtual position; no surface: 0 0 0 */
+    float    *normal;          /* [..][3] virtual normal; no surface: 0 0 0 */
+    float    *surface_position;/* [..][3] the end hit's real position; no surface: 0 0 0 */
+    float    *surface_normal;  /* [..][3] the end hit's hit_normal, as rtk_hit.normal; no surface: 0 0 0 */
+    float    *albedo;          /* [..][3] as rtk_gbuffer.albedo, of the end hit; no surface: the accel's background */
+    float    *bary;            /* [..][2] of the end hit; no surface: 0 0 */
+    uint32_t *tri, *mesh, *material;   /* of the end hit; no surface: 0xFFFFFFFF */
+    uint32_t *bounces;         /* k: secondary rays traced for this pixel, 0..max_ray_depth */
+    float    *last_ray;        /* [..][6] origin, direction of the chain's last ray (the camera ray when k == 0) */
+} rtk_gbuffer_specular;        /* 96 bytes */
+
+int rtk_render_gbuffer_specular(rtk_accel *accel, const rtk_render_params *p, int32_t sample,
+                                const rtk_view *views /* host; NULL = the accel's camera, n_views must be 1 */, int32_t n_views,
+                                const rtk_gbuffer_specular *out /* host planes */);
+int rtk_render_gbuffer_specular_device(rtk_accel *accel, const rtk_render_params *p, int32_t sample,
+                                       const rtk_view *d_views /* DEVICE, 4-byte aligned; NULL as above */, int32_t n_views,
+                                       const rtk_gbuffer_specular *out /* struct on the HOST, DEVICE plane pointers, 4-byte aligned */,
+                                       void *hip_stream);
+
 /* ---- a frame whose pixel blocks stop sampling once they have converged ----
  * The sample loop of tile_worker (render/render.hpp:30-77: for every pixel, for sample in [0, samples_per_pixel): camera ray,
  * intersect, color_hit, pixel_sum += colour; then pixel_sum / samples_per_pixel) cut short per 8x8 pixel block of the frame's own

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "rtk_accel_get_camera", "rtk_accel_set_camera", "rtk_render_views", "rtk_render_views_device",
     "rtk_render_regions", "rtk_render_regions_device",
     "rtk_render_gbuffer", "rtk_render_gbuffer_device",
+    "rtk_render_gbuffer_specular", "rtk_render_gbuffer_specular_device",
     "rtk_render_adaptive", "rtk_render_adaptive_device",
     "rtk_render_frame_noise", "rtk_render_frame_noise_device", "rtk_debug_noise_fallbacks",
     "rtk_denoise_workspace_bytes", "rtk_denoise_frame", "rtk_denoise_frame_device",
@@ -160,6 +161,12 @@ class GBuffer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "albedo", "bary", "tri", "mesh", "material")]
 
 
+class SpecularGBuffer(C.Structure):
+    """rtk.h rtk_gbuffer_specular: one pointer per plane, NULL = plane not wanted; 96 bytes."""
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "surface_position", "surface_normal", "albedo", "bary",
+                                          "tri", "mesh", "material", "bounces", "last_ray")]
+
+
 class AdaptiveParams(C.Structure):
     """rtk.h rtk_adaptive_params; 16 bytes."""
     _fields_ = [("min_samples", C.c_int32), ("step", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
@@ -218,6 +225,11 @@ MOTION_MISS_BITS = 0x7FC00000                         # rtk.h: both words of a p
 GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
                   "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
                   "material": ((), np.uint32)}
+
+SPECULAR_GBUFFER_PLANES = {"depth": ((), np.float32), "position": ((3,), np.float32), "normal": ((3,), np.float32),
+                           "surface_position": ((3,), np.float32), "surface_normal": ((3,), np.float32),
+                           "albedo": ((3,), np.float32), "bary": ((2,), np.float32), "tri": ((), np.uint32), "mesh": ((), np.uint32),
+                           "material": ((), np.uint32), "bounces": ((), np.uint32), "last_ray": ((6,), np.float32)}
 
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,))])
 LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("intensity", "<f4")])                     # rtk.h rtk_light
@@ -280,6 +292,9 @@ _L.rtk_render_regions.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, 
 _L.rtk_render_regions_device.argtypes = [_vp, C.POINTER(RenderParams), _vp, C.c_int32, C.c_int, _vp, _vp]
 _L.rtk_render_gbuffer.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer)]
 _L.rtk_render_gbuffer_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(GBuffer), _vp]
+if hasattr(_L, "rtk_render_gbuffer_specular"):        # (an older build loaded through RTK_LIB_OVERRIDE for an A/B run has no such call)
+    _L.rtk_render_gbuffer_specular.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(SpecularGBuffer)]
+    _L.rtk_render_gbuffer_specular_device.argtypes = [_vp, C.POINTER(RenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(SpecularGBuffer), _vp]
 _L.rtk_render_adaptive.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, C.POINTER(Counters)]
 _L.rtk_render_adaptive_device.argtypes = [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp]
 if hasattr(_L, "rtk_render_frame_noise"):             # (as above: an older build under RTK_LIB_OVERRIDE has no such call)
@@ -919,6 +934,44 @@ class KdTreeSimdAccel:
         gb = GBuffer(**{n: (int(ptr) or None) for n, ptr in planes.items()})
         p = cfg.to_c()
         _check(_L.rtk_render_gbuffer_device(self._h, C.byref(p), sample, d_views_ptr or None, n_views, C.byref(gb), stream))
+
+    # ---- the first surface that is shaded behind mirrors and glass, as planes (rtk.h rtk_gbuffer_specular)
+    def render_gbuffer_specular(self, cfg: RenderConfig, sample: int = 0, views: np.ndarray | None = None,
+                                planes=tuple(SPECULAR_GBUFFER_PLANES)) -> dict:
+        """The end of every pixel's specular chain at sample `sample` (reflections, refractions, total internal reflections, at most
+        cfg.max_ray_depth of them): {plane name: array [K, h, w(, c)]} for the planes asked for.  views as render_gbuffer.  depth,
+        position and normal describe the end hit in the virtual world behind the mirrors (what temporal_accumulate and denoise_frame
+        take in place of render_gbuffer's planes); the other planes are the end hit's own, bounces the secondary rays traced and
+        last_ray the ray that found it; the accel's camera, launch orders and counters stay as they are."""
+        unknown = [n for n in planes if n not in SPECULAR_GBUFFER_PLANES]
+        if unknown:
+            raise ValueError(f"unknown specular g-buffer planes {unknown}: choose from {list(SPECULAR_GBUFFER_PLANES)}")
+        if views is None:
+            k, vptr = 1, None
+        else:
+            views = _views_array(views)
+            k = views.shape[0]
+            if k == 0:
+                views = np.zeros((1, 12), np.float32)               # (no views: a valid pointer nothing is read through)
+            vptr = views.ctypes.data
+        w, h = self._frame_size(cfg)
+        out = {n: np.zeros((k, h, w) + shape, dtype) for n, (shape, dtype) in SPECULAR_GBUFFER_PLANES.items() if n in planes}
+        spare = np.zeros(1, np.uint32)                              # (likewise for planes without pixels)
+        gb = SpecularGBuffer(**{n: a.ctypes.data if a.size else spare.ctypes.data for n, a in out.items()})
+        p = cfg.to_c()
+        _check(_L.rtk_render_gbuffer_specular(self._h, C.byref(p), sample, vptr, k, C.byref(gb)))
+        return out
+
+    def render_gbuffer_specular_device(self, cfg: RenderConfig, planes: dict, sample: int = 0, d_views_ptr: int = 0, n_views: int = 1,
+                                       stream: int = 0) -> None:
+        """planes: {plane name: device pointer} of float32 / uint32 arrays [n_views, h, w(, c)], 4-byte aligned; d_views_ptr: device
+        float32 [n_views, 12], or 0 for the accel's own camera (n_views = 1); stream-ordered, allocates nothing (rtk.h)."""
+        unknown = [n for n in planes if n not in SPECULAR_GBUFFER_PLANES]
+        if unknown:
+            raise ValueError(f"unknown specular g-buffer planes {unknown}: choose from {list(SPECULAR_GBUFFER_PLANES)}")
+        gb = SpecularGBuffer(**{n: (int(ptr) or None) for n, ptr in planes.items()})
+        p = cfg.to_c()
+        _check(_L.rtk_render_gbuffer_specular_device(self._h, C.byref(p), sample, d_views_ptr or None, n_views, C.byref(gb), stream))
 
     # ---- where each pixel's surface point was in the previous pose (rtk.h rtk_motion_params)
     def render_motion(self, tri: np.ndarray, bary: np.ndarray, prev_vertices: np.ndarray, prev_view=None,

@@ -27,13 +27,7 @@ int gbuffer_device_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
     dev::GbufferArgs G;
     std::memset(&G, 0, sizeof(G));
     dev::RenderArgs &A = G.r;
-    A.tree = tree_view(a);
-    A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;            // (as the batched intersect walks it)
-    A.materials = a->d_materials.get();
-    A.textures = a->d_textures.get(); A.tri_uv = a->topo.tri_uv.get(); A.tex_pixels = a->d_tex_pixels.get();
-    std::memcpy(A.background, a->scene.background, sizeof(A.background));
-    camera_args(accel_camera(a), p, g, A);                              // (with views the camera in the arguments is not read)
-    A.world = 1;
+    gbuffer_scene_args(a, p, g, A);
     G.sample = sample; G.mask = mask;
     const GbufferPlan plan = plan_gbuffer(uint64_t(n_views), g.width, g.height);
     const uint64_t view_pixels = uint64_t(g.width) * g.height;
@@ -55,6 +49,20 @@ int gbuffer_device_impl(rtk_accel *a, const rtk_render_params *p, const FrameGeo
 }
 
 }  // namespace
+
+namespace rtk {
+
+void gbuffer_scene_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A) {
+    A.tree = tree_view(a);
+    A.tree.scalar_surv = a->knobs.batch_scalar_surv ? 1 : 0;            // (as the batched intersect walks it)
+    A.materials = a->d_materials.get();
+    A.textures = a->d_textures.get(); A.tri_uv = a->topo.tri_uv.get(); A.tex_pixels = a->d_tex_pixels.get();
+    std::memcpy(A.background, a->scene.background, sizeof(A.background));
+    camera_args(accel_camera(a), p, g, A);                              // (with views the camera in the arguments is not read)
+    A.world = 1;
+}
+
+}  // namespace rtk
 
 int rtk_render_gbuffer_device(rtk_accel *a, const rtk_render_params *p, int32_t sample, const rtk_view *d_views, int32_t n_views,
                               const rtk_gbuffer *out, void *stream) {

@@ -1,5 +1,5 @@
 // Internal to the host files that shade (api_frame, api_stream, api_order, api_views, api_regions, api_radiance, api_gbuffer,
-// api_adaptive, api_frame_noise .hip): what one of them defines and another calls, grouped by the file that defines it.
+// api_gbuffer_specular, api_adaptive, api_frame_noise .hip): what one of them defines and another calls, grouped by the file that defines it.
 #pragma once
 
 #include "accel.hpp"
@@ -94,6 +94,11 @@ rtk_radiance_params frame_radiance_params(const rtk_render_params *p);
 // one sample of one chunk of such a call: the batch, then its rays added to the call's counters
 int radiance_frame_chunk(rtk_accel *a, const rtk_ray *d_rays, const uint32_t *d_ids, size_t n, const rtk_radiance_params *rp, float *d_rgb,
                          hipStream_t s);
+
+// ---- api_gbuffer.hip
+// what a g-buffer kernel reads of zeroed launch arguments besides its units (gbuffer.hpp GbufferArgs::r): the tree as the batched
+// intersect walks it, materials, textures, background and the camera half; for rtk_render_gbuffer and rtk_render_gbuffer_specular
+void gbuffer_scene_args(const rtk_accel *a, const rtk_render_params *p, const FrameGeom &g, dev::RenderArgs &A);
 
 // ---- api_adaptive.hip
 int adaptive_device_impl(rtk_accel *a, const rtk_render_params *p, const rtk_adaptive_params *ap, const FrameGeom &g, float *d_rgb,

@@ -455,6 +455,49 @@ struct hip_accel {
         return r;
     }
 
+    // The first surface that is shaded behind mirrors and glass, as planes (rtk_render_gbuffer_specular): the end of every camera
+    // ray's specular chain under params.max_ray_depth and its biases.  depth, position and normal place the end hit in the virtual
+    // world behind the mirrors; surface_position, surface_normal, albedo, bary and the ids are the end hit's own; bounces the
+    // secondary rays traced; last_ray (6 floats per pixel) the ray that found it.  Planes, views and layout as render_gbuffer.
+    enum : unsigned {
+        specular_depth = 1u, specular_position = 2u, specular_normal = 4u, specular_surface_position = 8u, specular_surface_normal = 16u,
+        specular_albedo = 32u, specular_bary = 64u, specular_tri = 128u, specular_mesh = 256u, specular_material = 512u,
+        specular_bounces = 1024u, specular_last_ray = 2048u, specular_all = 4095u
+    };
+    struct gbuffer_specular_result {
+        std::size_t views = 0, width = 0, height = 0;
+        std::vector<float> depth, position, normal, surface_position, surface_normal, albedo, bary, last_ray;
+        std::vector<std::uint32_t> tri, mesh, material, bounces;
+    };
+    [[nodiscard]] gbuffer_specular_result render_gbuffer_specular(const rtk_render_params &params, std::int32_t sample,
+                                                                  std::span<const camera<F>> views, unsigned planes = specular_all) const {
+        std::size_t n = 0;
+        check(rtk_render_output_floats(accel_.get(), &params, &n));
+        gbuffer_specular_result r;
+        r.views = views.empty() ? 1 : views.size();
+        r.width = params.width > 0 ? static_cast<std::size_t>(params.width) : scene_ptr->config.image_width;
+        r.height = n / 3 / r.width;
+        const std::size_t pixels = r.views * r.width * r.height;
+        rtk_gbuffer_specular out{};
+        const auto want = [&](unsigned bit, auto &plane, std::size_t comps) {
+            if (planes & bit) plane.resize(pixels * comps + 1);              // (+ 1: a valid pointer for a call without pixels)
+            return (planes & bit) ? plane.data() : nullptr;
+        };
+        out.depth = want(specular_depth, r.depth, 1); out.position = want(specular_position, r.position, 3);
+        out.normal = want(specular_normal, r.normal, 3); out.surface_position = want(specular_surface_position, r.surface_position, 3);
+        out.surface_normal = want(specular_surface_normal, r.surface_normal, 3); out.albedo = want(specular_albedo, r.albedo, 3);
+        out.bary = want(specular_bary, r.bary, 2); out.tri = want(specular_tri, r.tri, 1); out.mesh = want(specular_mesh, r.mesh, 1);
+        out.material = want(specular_material, r.material, 1); out.bounces = want(specular_bounces, r.bounces, 1);
+        out.last_ray = want(specular_last_ray, r.last_ray, 6);
+        std::vector<rtk_view> in(views.size());
+        for (std::size_t v = 0; v < views.size(); ++v) in[v] = to_view(views[v]);
+        check(rtk_render_gbuffer_specular(accel_.get(), &params, sample, in.empty() ? nullptr : in.data(), static_cast<std::int32_t>(r.views), &out));
+        const auto trim = [&](auto &plane, std::size_t comps) { if (!plane.empty()) plane.resize(pixels * comps); };
+        trim(r.depth, 1); trim(r.position, 3); trim(r.normal, 3); trim(r.surface_position, 3); trim(r.surface_normal, 3); trim(r.albedo, 3);
+        trim(r.bary, 2); trim(r.tri, 1); trim(r.mesh, 1); trim(r.material, 1); trim(r.bounces, 1); trim(r.last_ray, 6);
+        return r;
+    }
+
     // Where each pixel's surface point was in the previous pose (rtk_render_motion): from ONE view of a render_gbuffer result with
     // its tri and bary planes, the vertices of the previous pose (all meshes concatenated in mesh order, as update_vertices takes
     // them) and, for `motion`, the previous camera.  prev_position [h][w] x 3 floats (0 on a miss) is what rtk_temporal_accumulate
